@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: event-tokens/sec of one full MusicAttrRegGMVAE training step (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|decode]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|decode] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else the benchmark measures or checks runs with
+--full only (see below).  --dump-outputs DIR writes what the timed path computed in its LAST timed step as DIR/<name>.npy (float32 /
+float64; the inputs are seeded, so two builds can be compared output for output): train mode `loss` (the 8 numbers train() returns),
+`grad_norm` and `params.<key>` (every trainable parameter after the update, 46 MB at this size); decode mode `tokens` and `z0` of the
+last fader-sweep pass.
 
 --gpus N > 1 without a launcher environment re-executes itself under ``torch.distributed.run`` (one rank per GPU, RCCL); when the
 driver launches it under ``torch.distributed.run`` already, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* are taken from the environment.
@@ -14,14 +20,15 @@ mode decode (BASELINE configs[4]): a "step" = encode 256 sequences (T=256), 8 fa
 
 --arith f32 | bf16x6: the arithmetic of the deep MFMA products (music-fader-nets_amd/arith.py; default = the package default).  Both are fp32-class
 (24-bit operands, fp32 accumulation); the line says which one `value` was measured on (`arith`) and carries the other one beside it
-(`fp32_mfma_value` / `bf16x6_value`, timed in a child process on the same seeds).  A bf16 x 6 kernel is rated against the dense bf16 MFMA peak / 6
-(416.7 fp32-equivalent TFLOP/s), an fp32-MFMA kernel against 157.3.
+(`fp32_mfma_value` / `bf16x6_value`, timed in a child process on the same seeds; --full).  A bf16 x 6 kernel is rated against the dense bf16
+MFMA peak / 6 (416.7 fp32-equivalent TFLOP/s), an fp32-MFMA kernel against 157.3.
 
-Prints ONE JSON line on rank 0 with the contract fields plus `roofline` (the kernel SYMBOL - template instances merged, as rocprofv3 --stats
-lists them - with the largest time per step), `roofline_by_symbol`, `roofline_scans` (the four scan rows as one time-weighted figure),
-`roofline_all` (split by launch shape), `sustained_ms_per_step` (200 more steps behind the timed region), (N=1) `cpu_baseline`, `decode`
-(the configs[4] measurement, so that the default run records it too) and, with collectives in place, `comm` (per-bucket all-reduce time
-and how long the step's stream stood still for them).
+Prints ONE JSON line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  With --full
+it also carries `roofline` (the kernel SYMBOL - template instances merged, as rocprofv3 --stats lists them - with the largest time per
+step), `roofline_by_symbol`, `roofline_scans` (the four scan rows as one time-weighted figure), `roofline_all` (split by launch shape),
+`sustained_ms_per_step` (200 more steps behind the timed region), (N=1) `first_step_loss` checked against tests/golden/c1.npz, the other
+arithmetic, `cpu_baseline`, `decode` (the configs[4] measurement) and, with collectives in place, `comm` (per-bucket all-reduce time and
+how long the step's stream stood still for them; N>1: the data-parallel self-check).
 """
 import argparse
 import json
@@ -383,6 +390,20 @@ def make_inputs(trainer, rank, world):
     return batch, eps
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, log):
+    """--dump-outputs: name -> array as out_dir/<name>.npy, float64 arrays kept, everything else as float32 (64 MB at most in all)"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs to dump: %d bytes > %d" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log("%d outputs (%.1f MB) written to %s" % (len(arrays), total / 1e6, out_dir))
+
+
 def dp_selfcheck(pkg, ctx, dev, rank, world, log):
     """N ranks through RCCL == one process on the global batch, at a small size (hidden 64, 8 rows per rank, T = 16): every rank takes one
     data-parallel step, rank 0 repeats it alone on the concatenated batch; the first-step loss tuples must agree (trainer_gmm.py:249-251: the
@@ -430,7 +451,7 @@ def bench_train(args, pkg, ctx, local, rank, world, log):
     first = None
     for i in range(args.warmup):
         beta0, Bg = trainer.step_device(step, batch, eps)
-        if i == 0:
+        if i == 0 and (args.full or args.leg_only):
             first = trainer._tuple8(beta0, Bg, False)       # the very first optimisation step from the seeded init (one sync)
         step += 1
     torch.cuda.synchronize()
@@ -453,9 +474,28 @@ def bench_train(args, pkg, ctx, local, rank, world, log):
     assert all(np.isfinite(tup)), tup
     tokens_per_s = world * B * T * args.steps / dt
     log("timed region done: %.3f ms/step (host enqueue %.3f ms/step)" % (dt / args.steps * 1e3, t_host / args.steps * 1e3))
-    if args.leg_only:                                       # child process of the default run: the other arithmetic's timed region, nothing else
+    if args.leg_only:                                       # child process of a --full run: the other arithmetic's timed region, nothing else
         return dict(arith=arith, ms_per_step=round(dt / args.steps * 1e3, 3), value=round(tokens_per_s, 1), unit="event-tokens/s", steps=args.steps,
                     first_step_loss=None if first is None else round(first[0], 4), last_loss=round(tup[0], 4))
+    out = {
+        "metric": "event-tokens/sec GM-VAE train, seq256 b256", "value": round(tokens_per_s, 1), "unit": "event-tokens/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        # the arithmetic the path computes in: fp32 operands and fp32 accumulation in both cases; "f32/bf16x6" = every fp32 product formed exactly from bf16 pieces (DESIGN.md section 3)
+        "dtype": "f32" if arith_mod.resolve(arith) == arith_mod.F32 else "f32/bf16x6", "arith": arith_mod.describe(arith), "data": "synthetic",
+        "config": {"workload": "MusicAttrRegGMVAE train step (fwd+losses+bwd+clip+Adam), hidden 512, z 128, K=2, "
+                               "B=256/GPU, T=256, Tr=64 (BASELINE configs[1]; N>1: DP, RCCL grad all-reduce)",
+                   "global_batch": B * world, "seq_len": T, "parallelism": "dp%d" % world},
+        "last_loss": round(tup[0], 4),
+    }
+    if args.dump_outputs and rank == 0:                     # before anything of --full moves the parameters on
+        arrays = {"loss": np.array(tup, dtype=np.float64), "grad_norm": np.array([trainer.grad_norm()], dtype=np.float64)}
+        sd = dict(model.named_parameters())
+        for k in trainer.flat.names:
+            arrays["params." + k] = sd[k].detach().cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays, log)
+    if not args.full:
+        return out
     # sustained rate: >= 200 more replays right behind the timed region (clock / thermal settle: r03 soak 23.64 ms vs 22.78 in the 20-step bench)
     sustained = None
     if args.sustain > 0:
@@ -475,17 +515,6 @@ def bench_train(args, pkg, ctx, local, rank, world, log):
         log("sustained: %.3f ms/step over %d more steps" % (sustained * 1e3, args.sustain))
     rows, by_symbol = per_kernel_rooflines(trainer, batch, eps)       # every rank: the pass contains the regulariser's all-gather
     log("per-kernel timing done")
-    out = {
-        "metric": "event-tokens/sec GM-VAE train, seq256 b256", "value": round(tokens_per_s, 1), "unit": "event-tokens/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        # the arithmetic the path computes in: fp32 operands and fp32 accumulation in both cases; "f32/bf16x6" = every fp32 product formed exactly from bf16 pieces (DESIGN.md section 3)
-        "dtype": "f32" if arith_mod.resolve(arith) == arith_mod.F32 else "f32/bf16x6", "arith": arith_mod.describe(arith), "data": "synthetic",
-        "config": {"workload": "MusicAttrRegGMVAE train step (fwd+losses+bwd+clip+Adam), hidden 512, z 128, K=2, "
-                               "B=256/GPU, T=256, Tr=64 (BASELINE configs[1]; N>1: DP, RCCL grad all-reduce)",
-                   "global_batch": B * world, "seq_len": T, "parallelism": "dp%d" % world},
-        "last_loss": round(tup[0], 4),
-    }
     if sustained is not None:
         out["sustained_ms_per_step"] = round(sustained * 1e3, 3)
         out["sustained_value"] = round(world * B * T / sustained, 1)
@@ -541,9 +570,9 @@ def bench_train(args, pkg, ctx, local, rank, world, log):
         from oracle import cpu_baseline
         out["cpu_baseline"] = _aux(lambda: cpu_baseline.time_baseline(H, Z, B, T, TR), log, "cpu baseline")
     if world == 1 and not args.no_decode:
-        # BASELINE configs[4] rides along in the default line (about 0.3 s of GPU time): 1 warm-up + 3 timed passes
+        # BASELINE configs[4] rides along in the --full line (about 0.3 s of GPU time): 1 warm-up + 3 timed passes
         del trainer
-        dargs = argparse.Namespace(steps=3, warmup=1, no_cpu_baseline=args.no_cpu_baseline, sustain=0)
+        dargs = argparse.Namespace(steps=3, warmup=1, no_cpu_baseline=args.no_cpu_baseline, sustain=0, full=True, dump_outputs=None)
         d = _aux(lambda: bench_decode(dargs, pkg, None, local, rank, world, log), log, "decode leg")
         out["decode"] = d if "error" in d else dict(metric=d["metric"], value=d["value"], unit=d["unit"], ms_per_pass=d["ms_per_step"],
                                                     workload=d["config"]["workload"], roofline=d["roofline"], cpu_baseline=d.get("cpu_baseline"))
@@ -598,7 +627,7 @@ def bench_decode(args, pkg, ctx, local, rank, world, log):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        tok, _ = fader_sweep(model, d, c, values, steps=DEC_STEPS, which="r", eps=eps)
+        tok, z0 = fader_sweep(model, d, c, values, steps=DEC_STEPS, which="r", eps=eps)
     torch.cuda.synchronize()
     if ctx is not None:
         torch.distributed.barrier()
@@ -609,6 +638,21 @@ def bench_decode(args, pkg, ctx, local, rank, world, log):
     assert int(tok.min()) >= 0 and int(tok.max()) < 342
     tokens_per_s = world * rows * DEC_STEPS * args.steps / dt
     log("timed region done: %.3f ms per pass" % (dt / args.steps * 1e3))
+    dops = model.engine().ops
+    x6cells = bool(getattr(dops, "dw_x6", False) and getattr(dops, "cell_x6", False) and rows >= getattr(dops, "cell_x6_rows", 1 << 30) and rows % 128 == 0)
+    out = {
+        "metric": "event-tokens/sec GM-VAE fader-sweep inference (encode + 8 fader values + 300-step greedy decode)",
+        "value": round(tokens_per_s, 1), "unit": "event-tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32/bf16x6" if x6cells else "f32",
+        "data": "synthetic",
+        "config": {"workload": "arousal-transfer / fader-sweep inference (BASELINE configs[4]): 256 sequences x T=256 encoded, 8 values "
+                               "of z_r[:,0] each, 2048 rows x 300 greedy steps, hipGraph replay; replicas only for N>1",
+                   "global_batch": rows * world, "seq_len": DEC_STEPS, "parallelism": "replicas%d" % world},
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"tokens": tok.cpu().numpy(), "z0": z0.cpu().numpy()}, log)
+    if not args.full:
+        return out
     # the decode kernels alone (graph replay of 300 x 5 kernels), HIP events on the launch stream, mean of 5
     z = torch.randn(rows, 2 * Z + 24, device=dev)
     greedy_decode(model, z, DEC_STEPS, want_logp=False)
@@ -622,27 +666,16 @@ def bench_decode(args, pkg, ctx, local, rank, world, log):
         ms.append(e0.elapsed_time(e1))
     ms = float(np.mean(ms))
     ach = rows * DEC_STEPS * F_ALG_DECODE_PER_TOKEN / (ms * 1e-3) / 1e12
-    dops = model.engine().ops
-    x6cells = bool(getattr(dops, "dw_x6", False) and getattr(dops, "cell_x6", False) and rows >= getattr(dops, "cell_x6_rows", 1 << 30) and rows % 128 == 0)
     dec_peak = PEAK_BF16X6_TFLOPS if x6cells else PEAK_F32_MFMA_TFLOPS      # the two cells are 93 % of a token's flops: the line is rated on their arithmetic
     dec_kernel = ("greedy decode of 2048 rows x 300 steps (graph of gru_cell_x6_kernel x 2 - the two cells on the bf16 MFMA with exact triple splits, producer / consumer form, layer 2 with "
                   "its input projection in the same K loop - and out_argmax_lds8_kernel<4> (fp32 MFMA) - output layer with the argmax in its epilogue - per token)") if x6cells else (
                   "greedy decode of 2048 rows x 300 steps (graph of gru_cell_wlds_ovl_kernel<4, 2, ...> x 2 - the two cells, weight slice in LDS "
                   "filled under the K loops, layer 2 with its input projection - and out_argmax_lds8_kernel<4> - output layer with the argmax in its epilogue - per token)")
-    out = {
-        "metric": "event-tokens/sec GM-VAE fader-sweep inference (encode + 8 fader values + 300-step greedy decode)",
-        "value": round(tokens_per_s, 1), "unit": "event-tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32/bf16x6" if x6cells else "f32",
-        "data": "synthetic",
-        "config": {"workload": "arousal-transfer / fader-sweep inference (BASELINE configs[4]): 256 sequences x T=256 encoded, 8 values "
-                               "of z_r[:,0] each, 2048 rows x 300 greedy steps, hipGraph replay; replicas only for N>1",
-                   "global_batch": rows * world, "seq_len": DEC_STEPS, "parallelism": "replicas%d" % world},
-        "roofline": dict(bound="mfma", kernel=dec_kernel, achieved=round(ach, 2), peak=round(dec_peak, 1), arith="bf16x6" if x6cells else "f32",
-                         frac_of_fp32_mfma_peak=round(ach / PEAK_F32_MFMA_TFLOPS, 4),
-                         unit="TFLOP/s", frac=round(ach / dec_peak, 4), avg_launch_us=round(ms * 1e3, 1), traffic=None,
-                         flop_per_launch=rows * DEC_STEPS * F_ALG_DECODE_PER_TOKEN,
-                         weight_stream_GBs=round(DEC_STEPS * DECODE_WEIGHT_BYTES / (ms * 1e-3) / 1e9, 1)),
-    }
+    out["roofline"] = dict(bound="mfma", kernel=dec_kernel, achieved=round(ach, 2), peak=round(dec_peak, 1), arith="bf16x6" if x6cells else "f32",
+                           frac_of_fp32_mfma_peak=round(ach / PEAK_F32_MFMA_TFLOPS, 4),
+                           unit="TFLOP/s", frac=round(ach / dec_peak, 4), avg_launch_us=round(ms * 1e3, 1), traffic=None,
+                           flop_per_launch=rows * DEC_STEPS * F_ALG_DECODE_PER_TOKEN,
+                           weight_stream_GBs=round(DEC_STEPS * DECODE_WEIGHT_BYTES / (ms * 1e-3) / 1e9, 1))
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_baseline
         out["cpu_baseline"] = cpu_baseline.time_decode_baseline(H, Z, rows, 30)      # the same 2048 rows as the GPU leg, 30 of its 300 steps
@@ -655,14 +688,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mode", choices=("train", "decode"), default="train")
-    ap.add_argument("--sustain", type=int, default=200, help="train mode: more steps timed right behind the K timed ones -> sustained_ms_per_step (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: sustained rate, per-kernel rooflines, the first step checked against tests/golden/c1.npz, "
+                         "the other arithmetic, CPU baselines, the decode leg in train mode, RCCL bucket times and (N>1) the data-parallel self-check")
+    ap.add_argument("--sustain", type=int, default=200, help="--full, train mode: more steps timed right behind the K timed ones -> sustained_ms_per_step (0 = skip)")
     ap.add_argument("--arith", choices=("f32", "bf16x6"), default=None,
                     help="arithmetic of the deep MFMA products (music-fader-nets_amd/arith.py; default: the package default).  Both are fp32-class: f32 = fp32 "
                          "MFMA chains, bf16x6 = exact bf16 triple splits, six partial products on the bf16 MFMA, fp32 accumulation")
-    ap.add_argument("--no-other-arith", "--no-x6", dest="no_other_arith", action="store_true", help="train mode: skip the leg that times the OTHER arithmetic beside the headline")
+    ap.add_argument("--no-other-arith", "--no-x6", dest="no_other_arith", action="store_true", help="--full, train mode: skip the leg that times the OTHER arithmetic beside the headline")
     ap.add_argument("--leg-only", action="store_true", help=argparse.SUPPRESS)      # internal: the child process that times the other arithmetic
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true", help="train mode: leave the configs[4] decode measurement out of the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-decode", action="store_true", help="--full, train mode: leave the configs[4] decode measurement out of the line")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_launcher(args.gpus)

@@ -4,9 +4,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r6/prof_${1:-x}
 rm -rf $O; mkdir -p $O
 cd $R
-timeout 900 python bench.py ${BENCH_ARGS:---no-cpu-baseline --no-decode} > $O/bench_train.json 2> $O/bench_train.err; tail -3 $O/bench_train.err
+timeout 900 python bench.py --full ${BENCH_ARGS:---no-cpu-baseline --no-decode} > $O/bench_train.json 2> $O/bench_train.err; tail -3 $O/bench_train.err
 cd /tmp; export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $R/bench.py --steps 3 --warmup 2 --sustain 0 --no-other-arith --no-cpu-baseline --no-decode > $O/prof_bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $R/bench.py --full --steps 3 --warmup 2 --sustain 0 --no-other-arith --no-cpu-baseline --no-decode > $O/prof_bench.log 2>&1
 python $R/scratch/prof_summary.py $O/prof/bench_results.db 45 > $O/kernel_stats.txt
 python $R/scratch/prof_timeline.py $O/prof/bench_results.db 100 3 > $O/timeline.txt
 rm -rf $O/prof

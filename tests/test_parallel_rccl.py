@@ -203,14 +203,14 @@ def _run_bench(extra, env_extra=None, timeout=900):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 2])
 def test_bench_launches_its_own_ranks(n):
-    """`python bench.py --gpus N` with no launcher environment prints ONE JSON line with n_gpus = N (N = 1 also runs with the
+    """`python bench.py --gpus N --full` with no launcher environment prints ONE JSON line with n_gpus = N (N = 1 also runs with the
     collectives forced on, FN_FORCE_DIST=1, i.e. through RCCL)."""
     if torch.cuda.device_count() < n:
         pytest.skip("needs %d visible GPUs" % n)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     if n == 1:
         env["FN_FORCE_DIST"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "2", "--sustain", "20", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "2", "--full", "--sustain", "20", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -228,6 +228,32 @@ def test_bench_launches_its_own_ranks(n):
     else:
         chk = out["comm"]["dp_selfcheck"]                           # N ranks through RCCL == one process on the global batch (small shape)
         assert chk["max_rel_diff_of_the_tuples"] <= 2e-4, chk
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `python bench.py --steps 2 --warmup 2 --dump-outputs DIR` prints the headline line without anything of --full, and DIR holds
+    what the last timed step computed: the loss tuple (its first entry = `last_loss`), the gradient norm and every trainable parameter,
+    as float32 / float64 arrays of 64 MB at most in all."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FN_FORCE_DIST")}
+    dump = os.path.join(str(tmp_path), "out")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "2", "--dump-outputs", dump],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+    assert out["unit"] == "event-tokens/s" and out["dtype"] in ("f32", "f32/bf16x6") and out["metric"]
+    for k in ("roofline", "roofline_all", "sustained_ms_per_step", "first_step_loss", "cpu_baseline", "decode", "fp32_mfma_leg", "bf16x6_leg", "comm"):
+        assert k not in out, k
+    arrays = {f[:-4]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+    assert arrays["loss"].shape == (8,) and arrays["grad_norm"].shape == (1,)
+    assert abs(arrays["loss"][0] - out["last_loss"]) <= 1e-4 * abs(out["last_loss"])
+    params = [k for k in arrays if k.startswith("params.")]
+    assert params and set(arrays) == set(params) | {"loss", "grad_norm"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
 
 
 def test_bench_respawns_under_the_launcher_without_gpus():
