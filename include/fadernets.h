@@ -150,6 +150,23 @@ int fn_sum_f32(const float* x, int64_t n, float scale, float* out, void* stream)
  * fn_frag_pack (one contiguous 1 KB run per wave load instruction); frag_ws is caller-owned scratch of
  * 2 * fn_frag_floats(B, H) floats in which the scan ping-pongs the state in the same layout.
  * ------------------------------------------------------------------------------------------ */
+/* Bits of FnGruFwd.variant / FnGruBwd.variant (scans[0]'s is used) and FnGruCell.variant.  0 = automatic; the other bits are tuning and
+ * test switches, and results never depend on them beyond fp32 rounding (tests/test_gpu_parity.py compares the forms). */
+#define FN_GRU_ROWS_MASK 0xFF         /* scans: force this many batch rows per workgroup of the single launch (16/32/64/128; not eligible ->
+                                         per-step kernels).  Cells: the forced form 1-18 (see FnGruCell)                                     */
+#define FN_GRU_ALT_TILING 0x100       /* scans: the alternative wave tiling of the 64-row configuration                                     */
+#define FN_GRU_SYNC_ZEROED 0x200      /* scans: the sync_ws counters are ALREADY zero (the caller zero-fills a pool of regions once and gives
+                                         every launch its own region: saves one memset node per launch)                                      */
+#define FN_GRU_COMPILER_LOOPS 0x400   /* scans: the compiler-scheduled K loops instead of the hand-placed ones (kloop_asm.h); no ping-pong or
+                                         register-stationary form                                                                            */
+#define FN_GRU_NO_PINGPONG 0x800      /* scans: the round-3 loops (no ping-pong forward, no register-stationary backward)                    */
+#define FN_GRU_SPREAD_XCDS 0x1000     /* scans: the workgroups of every row group are spread over all XCDs instead of sharing one (the
+                                         default placement is speed only; the tests run both and compare)                                    */
+#define FN_GRU_NO_RS_BWD 0x2000       /* backward scans: not the register-stationary kernel (gru_bwd_rs_kernel) - the 32-slice loop          */
+#define FN_GRU_BF16X6 0x4000          /* the bf16 x 6 scans / cell: exact split products on the bf16 MFMA (see below and FN_GEMM_BF16X6)    */
+#define FN_GRU_X6_SINGLE_GROUP 0x8000 /* with FN_GRU_BF16X6, forward scans: the single-group kernel instead of the ping-pong form (tests)      */
+#define FN_GRU_X6_BWD_32ROWS 0x8000   /* with FN_GRU_BF16X6, backward scans: 32-row groups are eligible too (measured slower than the fp32
+                                         kernel: only on request)                                                                            */
 typedef struct FnGruFwd {
     int32_t B, T, H;
     int32_t reverse;          /* 1: consume tokens from the end (the *_reverse direction)      */
@@ -177,20 +194,14 @@ typedef struct FnGruFwd {
                               /* floats) - saves the packing launch when a scan continues a previous call (time  */
                               /* chunks, step-by-step decoding); h0 is still needed (row-major, gate epilogue)   */
     float* h_last_frag;       /* optional: the final state, fragment-major (the next call's h0_frag)       */
-    int32_t variant;          /* 0 = automatic (scans[0]'s is used).  Tuning / tests: low byte = force this many batch rows per   */
-                              /* workgroup of the single launch (16/32/64/128; not eligible -> per-step kernels), bit 8 = the     */
-                              /* alternative wave tiling of the 64-row configuration.  Results never depend on it.               */
-                              /* bit 9: sync_ws counters are ALREADY zero (the caller zero-fills a pool of regions once and gives  */
-                              /* every launch its own region: saves one memset node per launch)                                  */
-                              /* bit 12 (tests): the workgroups of every row group are spread over all XCDs instead of sharing    */
-                              /* one (the default placement is speed only; tests/test_gpu_parity.py runs both and compares)       */
+    int32_t variant;          /* 0 = automatic (scans[0]'s is used), else FN_GRU_* bits (above)                                   */
     void* err_ws;             /* optional: sticky error word outside sync_ws (>= 4 bytes, scans[0]'s is used); NULL = the last     */
                               /* 128 bytes of sync_ws                                                                            */
 } FnGruFwd;
 
 /* fragment-major operand image: floats needed for a [rows][K] matrix, and the packing kernel
  * (src row-major with leading dimension ld, K % 32 == 0; rows are zero-padded to a multiple of 16) */
-/* OPT-IN (FnGruFwd.variant bit 14 = 0x4000): the forward scan with exact split products on the bf16 MFMA ("bf16 x 6", see FN_GEMM_BF16X6):
+/* OPT-IN (FnGruFwd.variant | FN_GRU_BF16X6): the forward scan with exact split products on the bf16 MFMA ("bf16 x 6", see FN_GEMM_BF16X6):
  * w_hh_frag must then be the fn_frag3_pack image of W_hh [3H][H] (bf16 triples hi | mid | lo, hi + mid + lo == W exactly; 3/2 of
  * fn_frag_floats(3H, H) floats) and frag_ws 3 * fn_frag_floats(B, H) floats (the state is exchanged as triples too).  H = 512, every
  * scan in full row groups of 64 (or 128) rows, saved gates, T >= 2 (h0_frag / h_last_frag are then triple images of 3/2 * fn_frag_floats(B, H)
@@ -204,7 +215,7 @@ int fn_frag_pack(const float* src, int rows, int K, int ld, float* dst, void* st
  *   kind 0: dst [cols][rows] = src^T                       (the one-hot column table W_ih[:, :V]^T; src [rows][cols], leading dim ld)
  *   kind 1: dst = fn_frag_pack image of src [rows][K = cols]  (cols % 32 == 0)
  *   kind 2: dst = fn_frag_pack image of src^T, the [cols][K = rows] matrix (rows % 32 == 0): W_hh^T for the backward scans
- *   kind 3: dst = fn_frag3_pack image (bf16 triples) of src [rows][K = cols]            (bf16 x 6 forward scans, variant bit 14)
+ *   kind 3: dst = fn_frag3_pack image (bf16 triples) of src [rows][K = cols]            (bf16 x 6 forward scans, FN_GRU_BF16X6)
  *   kind 4: dst = fn_frag3_pack image of src^T, the [cols][K = rows] matrix              (bf16 x 6 backward scans: W_hh^T)
  *   kind 5: dst [rows][cols] dense = src [rows][cols] (leading dim ld)                   (round 6: 16-byte aligned image of a column slice, W_ih[:, V:])
  * up to 56 jobs; dst of kinds 1 / 2 16-byte aligned with fn_frag_floats(...) floats, of kinds 3 / 4 with 3/2 of that. */
@@ -224,7 +235,7 @@ size_t fn_gru_gates_floats(int B, int H);
  * launch whose workgroups gave up waiting (results of that and later calls are invalid until it is cleared). */
 size_t fn_gru_sync_ws_bytes(void);
 int fn_gru_seq_fwd(const FnGruFwd* scans, int n_scans, void* stream);
-/* 1 when fn_gru_seq_fwd would take this call with variant bit 14 (bf16 x 6) on the current device, else 0 (shapes and gates != NULL only;
+/* 1 when fn_gru_seq_fwd would take this call with FN_GRU_BF16X6 (bf16 x 6) on the current device, else 0 (shapes and gates != NULL only;
  * nothing is enqueued).  A scan that is cut into several calls (time chunks with h_last_frag -> h0_frag hand-over) must run ALL of its
  * calls on one arithmetic - the hand-over images differ (bf16 triples / fp32 fragments) - so the caller asks for every call of the chain first. */
 int fn_gru_fwd_x6_ok(const FnGruFwd* scans, int n_scans);
@@ -260,7 +271,7 @@ typedef struct FnGruCell {
                                  loop (4, 6: 128 rows x 32 units per workgroup, 1 / 2 k steps in flight; 5, 7: 64 rows, 4 / 2), 9-12 the loop with
                                  the weight slice in LDS (9, 11: 256 rows x 16 units, 2 steps; 10, 12: 128 rows, 4 / 8; 13, 14: 192 rows, 4 / 2), 15-18 the same with
                                  the slice fills under the K loops (K1 = H = 512; 15, 18: 128 rows, 4 / 2 steps; 16: 192 rows; 17: 256 rows) where eligible.
-                                 | 0x4000 (bit 14, as in FnGruFwd): the cell on the bf16 MFMA with exact triple splits (gru.hip: gru_cell_x6_kernel) where
+                                 | FN_GRU_BF16X6 (as in FnGruFwd): the cell on the bf16 MFMA with exact triple splits (gru.hip: gru_cell_x6_kernel) where
                                  B % 128 == 0, H % 32 == 0, K1 % 32 == 0 and the operands are 16-byte aligned; other shapes run as without the bit */
     const uint64_t* idx_best; /* NULL, or the packed argmax words of the previous token (fn_out_argmax_f32): the token of row b is
                                  best_v - 1 - (uint32_t)idx_best[b]; takes precedence over idx                                */
@@ -309,9 +320,9 @@ typedef struct FnGruBwd {
 } FnGruBwd;
 
 int fn_gru_seq_bwd(const FnGruBwd* scans, int n_scans, void* stream);
-/* variant bit 14 (0x4000), as in FnGruFwd: the backward scan with exact split products on the bf16 MFMA (gru_bwd_x6_kernel).  w_hh_t_frag must then be
+/* variant | FN_GRU_BF16X6, as in FnGruFwd: the backward scan with exact split products on the bf16 MFMA (gru_bwd_x6_kernel).  w_hh_t_frag must then be
  * the bf16 TRIPLE image of W_hh^T [H][3H] (fn_weight_images kind 4; 3/2 of fn_frag_floats(H, 3H) floats) and frag_ws 3 * fn_frag_floats(B, 3H) floats
- * (the gate gradients are exchanged as triples).  H = 512, every scan in full groups of 64 rows (with variant bit 15 also: of 32 rows - that form
+ * (the gate gradients are exchanged as triples).  H = 512, every scan in full groups of 64 rows (with FN_GRU_X6_BWD_32ROWS also: of 32 rows - that form
  * measured slower than the fp32 kernel and is not chosen on its own), T >= 2, 9..16 row groups that are all resident at once (the shapes of the
  * register-stationary fp32 kernel); anything else returns FN_E_UNSUPPORTED.  fn_gru_bwd_x6_ok answers without
  * enqueuing anything (1 / 0).  Same element-wise gate arithmetic; gradients differ from the default kernels by fp32 rounding only. */

@@ -16,6 +16,17 @@ GEMM_BF16X6 = 0x20000        # FN_GEMM_BF16X6 (exact bf16 triple split on the bf
 GEMM_X6_WIDE = 0x80000       # FN_GEMM_X6_WIDE (128 x 256 output tiles per workgroup)
 GEMM_X6_PERTILE = 0x100000   # FN_GEMM_X6_PERTILE (tests / A-B: one workgroup per tile / (tile, K range) item instead of one per CU walking its items)
 GEMM_X6_PERWAVE = 0x40000    # FN_GEMM_X6_PERWAVE (tests / A-B: the round-5 kernel, every wavefront splits its own operands)
+# FnGruFwd / FnGruBwd / FnGruCell .variant bits (FN_GRU_* in include/fadernets.h)
+GRU_ROWS_MASK = 0xFF         # forced rows per workgroup (scans) / forced form 1-18 (cells)
+GRU_ALT_TILING = 0x100       # the alternative wave tiling of the 64-row configuration
+GRU_SYNC_ZEROED = 0x200      # the sync_ws counters are already zero
+GRU_COMPILER_LOOPS = 0x400   # compiler-scheduled K loops
+GRU_NO_PINGPONG = 0x800      # the round-3 loops
+GRU_SPREAD_XCDS = 0x1000     # every row group spread over all XCDs (placement test)
+GRU_NO_RS_BWD = 0x2000       # backward: not the register-stationary kernel
+GRU_BF16X6 = 0x4000          # bf16 x 6 scans / cell
+GRU_X6_SINGLE_GROUP = 0x8000  # with GRU_BF16X6, forward: the single-group kernel (no ping-pong)
+GRU_X6_BWD_32ROWS = 0x8000   # with GRU_BF16X6, backward: 32-row groups eligible too
 FN_E_NULL, FN_E_SHAPE, FN_E_ALIGN, FN_E_WORKSPACE, FN_E_COUNT = -1, -2, -3, -4, -5
 FN_E_UNSUPPORTED = -6
 FN_E_COMM = -7

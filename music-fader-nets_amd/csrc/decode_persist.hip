@@ -526,10 +526,10 @@ __global__ __launch_bounds__(NT) void decode_greedy_kernel(const DArgs a) {
 template <int MT>
 int launch_decode(const DArgs& a, int grid, hipStream_t st) {
     auto k = decode_greedy_kernel<MT>;
-    static std::atomic<int> fits[32];              // write-once per device (zero-initialised): 1 = at least one workgroup of this kernel fits a CU, -1 = it does not
+    static std::atomic<int> fits[FN_MAX_DEVICES];  // write-once per device (zero-initialised): 1 = at least one workgroup of this kernel fits a CU, -1 = it does not
     const size_t lds = ((size_t)3 * a.H * 16 + (size_t)4 * MT * 3 * RT) * 4 + 16 + 64 * 4;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_UNSUPPORTED;
+    const int dev = fn_device();
+    if (dev < 0) return FN_E_UNSUPPORTED;
     if (fits[dev].load(std::memory_order_acquire) == 0) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
         if (e != hipSuccess) return (int)e;

@@ -1,7 +1,6 @@
 // gemm.hip - dense fp32 GEMM on the f32 MFMA + small dense helpers (transpose, column sums, axpy, sum).
 // Replaces nn.Linear forward / backward of the reference (gmm_model.py:86,91,108,113,123,137 and their
 // autograd), see include/fadernets.h.
-#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -1727,15 +1726,8 @@ int fn_out_head_f32(const float* h, int ldh, const float* W, int ldw, const floa
     if (dlogits && (((uintptr_t)dlogits) & 15)) return FN_E_ALIGN;
     const long R = (long)B * T;
     if (R > 0x7fffffff) return FN_E_SHAPE;
-    static std::atomic<bool> attr_set[32];         // write-once per device; setting the attribute twice is harmless
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
     const size_t lds = out_head_lds_bytes();
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(out_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (const int rc = fn_set_max_lds<out_head_kernel>((int)lds, FN_E_SHAPE)) return rc;
     hipLaunchKernelGGL(out_head_kernel, dim3((unsigned)((R + OH_BM - 1) / OH_BM)), dim3(NT), lds, (hipStream_t)stream, h, (long)ldh, W, (long)ldw,
                        bias, (int)R, V, H, B, T, target, grad_scale, nll_rows, dlogits, (long)ld);
     FN_CHECK_LAUNCH();
@@ -1778,21 +1770,6 @@ int fn_gemm_multi(int a_kmajor, int b_kmajor, const FnGemmJob* jobs, int n_jobs,
 }
 
 // grid of a TN launch: 1-D (K ranges dealt to the XCDs, see gemm_tn_body) when the K ranges divide by 8, else tiles x 1 x K ranges
-// compute units of the current device (write-once per device, as gru_persist.hip's cu_count)
-static int gemm_cu_count() {
-    static std::atomic<int> n[32];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return 0;
-    int c = n[dev].load(std::memory_order_acquire);
-    if (c == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        c = prop.multiProcessorCount;
-        n[dev].store(c, std::memory_order_release);
-    }
-    return c;
-}
-
 static dim3 tn_grid(int tiles, int splitk) {
     return splitk > 1 && (splitk & 7) == 0 ? dim3(tiles * splitk, 1, 1) : dim3(tiles, 1, splitk > 1 ? splitk : 1);
 }
@@ -1807,20 +1784,12 @@ static int launch_tn_x6(int mode, int tiles, int splitk, hipStream_t st, int M, 
     }
     const bool wide = (mode & FN_GEMM_X6_WIDE) != 0;
     const size_t lds = wide ? (size_t)2 * X6V_STAGE * 16 : (size_t)X6W_STAGES * X6W_STAGE * 16;
-    const void* fn = wide ? reinterpret_cast<const void*>(gemm_tn_x6v_kernel) : reinterpret_cast<const void*>(gemm_tn_x6w_kernel);
-    static std::atomic<bool> attr_set[2][32];      // write-once per device and kernel; setting the attribute twice is harmless
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
-    if (!attr_set[wide][dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set[wide][dev].store(true, std::memory_order_release);
-    }
+    if (const int rc = wide ? fn_set_max_lds<gemm_tn_x6v_kernel>((int)lds, FN_E_SHAPE) : fn_set_max_lds<gemm_tn_x6w_kernel>((int)lds, FN_E_SHAPE)) return rc;
     // 1-D launches (K ranges dealt to the XCDs): one workgroup per CU walking its (tile, K range) items instead of one workgroup per item - the next
     // item's first blocks are requested and cut while the consumers store the finished one (FN_GEMM_X6_PERTILE: one workgroup per item, A/B and tests)
     const int wtiles = wide ? ((M + 127) / 128) * ((N + 255) / 256) : tiles;
     dim3 grid = tn_grid(wtiles, splitk);
-    const int cus = gemm_cu_count();
+    const int cus = fn_cu_count();
     if (grid.y == 1 && grid.z == 1 && slabs != nullptr && !(mode & FN_GEMM_X6_PERTILE) && cus >= 8 && (cus & 7) == 0 && (int)grid.x > cus) grid.x = cus;
     if (wide) {
         hipLaunchKernelGGL(gemm_tn_x6v_kernel, grid, dim3(X6W_NT), lds, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, klen, slabs, A2, lda2, msplit);
@@ -1872,17 +1841,10 @@ int fn_gemm_f32(int a_kmajor, int b_kmajor, int M, int N, int K, float alpha, co
     if (x6 && a_kmajor && b_kmajor && splitk <= 1 && (M % 128) == 0 && (N % 128) == 0 && (K % 32) == 0 && K >= 128 && (lda % 4) == 0 && (ldb % 4) == 0 &&
         (ldc % 4) == 0 && (((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) == 0) && (long)(M / 128) * (N / 128) >= 128) {
         const size_t lds = (size_t)X6W_STAGES * X6W_STAGE * 16;
-        static std::atomic<bool> attr_set[32];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_x6w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            attr_set[dev].store(true, std::memory_order_release);
-        }
+        if (const int rc = fn_set_max_lds<gemm_nt_x6w_kernel>((int)lds, FN_E_SHAPE)) return rc;
         // one workgroup per CU (144 KB of LDS each) walking its tiles, unless asked for one workgroup per tile (FN_GEMM_X6_PERTILE) or the CU count is not a
         // multiple of the 8 XCDs
-        const int ntiles = (M / 128) * (N / 128), cus = gemm_cu_count();
+        const int ntiles = (M / 128) * (N / 128), cus = fn_cu_count();
         const int grid = (ntiles > cus && cus >= 8 && (cus & 7) == 0 && !(x6_mode & FN_GEMM_X6_PERTILE)) ? cus : ntiles;
         hipLaunchKernelGGL(gemm_nt_x6w_kernel, dim3(grid), dim3(X6W_NT), lds, st, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C, (long)ldc, bias);
         FN_CHECK_LAUNCH();

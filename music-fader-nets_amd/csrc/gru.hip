@@ -21,9 +21,6 @@
 //   * the saved gates use a private blocked layout in which every wave store / load instruction is one
 //     contiguous 256-byte run (see gate_off).
 #include <cstdio>
-#include <cstdlib>
-
-#include <atomic>
 
 #include "gru_layout.h"
 #include "x6w_core.h"
@@ -1481,15 +1478,8 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_kernel(const CellArgs a, int
 
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
 int launch_cell_wlds_inst(const CellArgs& a, int kmax, size_t lds, hipStream_t st) {
-    static std::atomic<bool> attr_set[32];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
     auto k = gru_cell_wlds_kernel<RT, PF, HAS_TAB, HAS_RB>;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (const int rc = fn_set_max_lds<gru_cell_wlds_kernel<RT, PF, HAS_TAB, HAS_RB>>(160 * 1024, FN_E_SHAPE)) return rc;
     const int tiles = ((a.B + 64 * RT - 1) / (64 * RT)) * (a.H / 16);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), lds, st, a, kmax);
     FN_CHECK_LAUNCH();
@@ -1513,7 +1503,7 @@ int launch_cell_wlds(const CellArgs& a, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// One GRUCell step of a large batch on the bf16 MFMA with exact triple splits (round 6; FnGruCell.variant bit 14): the producer / consumer form of the
+// One GRUCell step of a large batch on the bf16 MFMA with exact triple splits (round 6; FnGruCell.variant | FN_GRU_BF16X6): the producer / consumer form of the
 // round-6 GEMMs (x6w_core.h, gemm.hip) with the gate epilogue behind it.  Workgroup = 128 rows x 32 hidden units; its "N tile" is 128 columns:
 // [r | z | n_x | n_h] of those 32 units, where r and z accumulate the dense-input part x W_ih^T AND the recurrent part h W_hh^T (one K loop over
 // K1 + H), n_x only the input part and n_h only the recurrent part (their weight rows count as zeros in the other part: a quarter of the MFMAs multiply
@@ -1713,15 +1703,8 @@ static bool cell_x6_ok(const CellArgs& a) {
 template <bool HAS_TAB, bool HAS_RB>
 int launch_cell_x6_inst(const CellArgs& a, hipStream_t st) {
     const size_t lds = (size_t)X6W_STAGES * X6W_STAGE * 16;
-    static std::atomic<bool> attr_set[32];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
     auto k = gru_cell_x6_kernel<HAS_TAB, HAS_RB>;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (const int rc = fn_set_max_lds<gru_cell_x6_kernel<HAS_TAB, HAS_RB>>((int)lds, FN_E_SHAPE)) return rc;
     hipLaunchKernelGGL(k, dim3((a.B / 128) * (a.H / 32)), dim3(X6W_NT), lds, st, a);
     FN_CHECK_LAUNCH();
     return FN_OK;
@@ -1878,15 +1861,8 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_ovl_kernel(const CellArgs a)
 
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
 int launch_cell_wlds_ovl_inst(const CellArgs& a, hipStream_t st) {
-    static std::atomic<bool> attr_set[32];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
     auto k = gru_cell_wlds_ovl_kernel<RT, PF, HAS_TAB, HAS_RB>;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (const int rc = fn_set_max_lds<gru_cell_wlds_ovl_kernel<RT, PF, HAS_TAB, HAS_RB>>(160 * 1024, FN_E_SHAPE)) return rc;
     const int tiles = ((a.B + 64 * RT - 1) / (64 * RT)) * (a.H / 16);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), (size_t)48 * 512 * 4 + 4 * 4 * 320 * 4, st, a);
     FN_CHECK_LAUNCH();
@@ -1907,15 +1883,8 @@ int launch_cell_wlds_ovl(const CellArgs& a, hipStream_t st) {
 template <int BM, int WM, int WN>
 int launch_cell(const CellArgs& a, hipStream_t st) {
     const size_t lds = (size_t)2 * (Stage<BM, GC_BK, true, NT>::WORDS + Stage<GC_BN, GC_BK, true, NT>::WORDS) * sizeof(float);
-    static std::atomic<bool> attr_set[32];         // write-once per device; setting the attribute twice is harmless
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
     auto k = gru_cell_kernel<BM, WM, WN>;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (const int rc = fn_set_max_lds<gru_cell_kernel<BM, WM, WN>>((int)lds, FN_E_SHAPE)) return rc;
     const int tiles = ((a.B + BM - 1) / BM) * (a.H / 32);
     hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), lds, st, a);
     FN_CHECK_LAUNCH();
@@ -1995,6 +1964,10 @@ bool launch_bwd(const Cfg& c, const BwdArgs& a, int tiles, hipStream_t st) {
     return false;
 }
 
+// eligibility of the forced cell forms with the weight slice in LDS (fn_gru_cell_f32)
+bool cell_wlds_fits(const CellArgs& a) { return cell_direct_ok(a) && cell_wlds_ok(a); }
+bool cell_ovl_fits(const CellArgs& a) { return cell_direct_ok(a) && cell_wlds_ovl_ok(a); }
+
 }  // namespace
 
 extern "C" {
@@ -2012,65 +1985,51 @@ int fn_gru_cell_f32(const FnGruCell* c, void* stream) {
     a.h_out = c->h_out; a.ldo = c->ldo; a.B = c->B; a.H = c->H;
     a.best = reinterpret_cast<const unsigned long long*>(c->idx_best); a.best_v = c->best_v;
     if (c->idx_best && (c->best_v <= 0 || !c->gx_table)) return FN_E_SHAPE;
-    // variant bit 14 (as in FnGruFwd): the cell on the bf16 MFMA with exact triple splits where the shape allows it (else the fp32 cells below, as if the bit were clear)
-    const int variant = c->variant & ~0x4000;
-    if ((c->variant & 0x4000) && cell_x6_ok(a)) return launch_cell_x6(a, (hipStream_t)stream);
+    const hipStream_t st = (hipStream_t)stream;
+    // FN_GRU_BF16X6 (as in FnGruFwd): the cell on the bf16 MFMA with exact triple splits where the shape allows it (else the fp32 cells below, as if the bit were clear)
+    const int variant = c->variant & ~FN_GRU_BF16X6;
+    if ((c->variant & FN_GRU_BF16X6) && cell_x6_ok(a)) return launch_cell_x6(a, st);
     // measured (scratch/prof_decode_cells.sh, us per token of the tokens-only decode, profiles/r04_decode_cells_lds_free.txt): the form with the weight slice in
     // LDS wants ONE workgroup per CU: 64 RT rows x 16 units with RT = ceil(rows / 512) - 1024 rows 71.5 (staged 82, LDS-free 77), 1152-1536 rows 88-89 (LDS-free 101-102);
     // at 2048 rows (RT = 4) it is behind the LDS-free 128-row form (108 against 103)
     if (variant == 0 && c->B > 512 && c->B <= 2048 && cell_direct_ok(a) && cell_wlds_ovl_ok(a)) {
         // K1 = H = 512: the slice fills under the K loops - 640-1024 rows 60 (71), 1280-1536 rows 78-80 (88), 2048 rows 99.8 (102.9 LDS-free)
-        if (c->B <= 1024) return launch_cell_wlds_ovl<2, 2>(a, (hipStream_t)stream);
-        if (c->B <= 1536) return launch_cell_wlds_ovl<3, 2>(a, (hipStream_t)stream);
-        return launch_cell_wlds_ovl<4, 2>(a, (hipStream_t)stream);
+        if (c->B <= 1024) return launch_cell_wlds_ovl<2, 2>(a, st);
+        if (c->B <= 1536) return launch_cell_wlds_ovl<3, 2>(a, st);
+        return launch_cell_wlds_ovl<4, 2>(a, st);
     }
     if (variant == 0 && c->B > 512 && cell_direct_ok(a)) {
-        if (c->B > 1536 || !cell_wlds_ok(a)) return c->B > 1024 ? launch_cell_direct<4, 2>(a, (hipStream_t)stream) : launch_cell_direct<2, 4>(a, (hipStream_t)stream);
-        return c->B > 1024 ? launch_cell_wlds<3, 2>(a, (hipStream_t)stream) : launch_cell_wlds<2, 4>(a, (hipStream_t)stream);
+        if (c->B > 1536 || !cell_wlds_ok(a)) return c->B > 1024 ? launch_cell_direct<4, 2>(a, st) : launch_cell_direct<2, 4>(a, st);
+        return c->B > 1024 ? launch_cell_wlds<3, 2>(a, st) : launch_cell_wlds<2, 4>(a, st);
     }
-    switch (variant) {                                  // tuning / tests: the staged forms agree bit for bit, the LDS-free forms 4-7 among themselves (another k order)
-        case 15: if (cell_direct_ok(a) && cell_wlds_ovl_ok(a)) return launch_cell_wlds_ovl<2, 4>(a, (hipStream_t)stream); break;
-        case 16: if (cell_direct_ok(a) && cell_wlds_ovl_ok(a)) return launch_cell_wlds_ovl<3, 2>(a, (hipStream_t)stream); break;
-        case 17: if (cell_direct_ok(a) && cell_wlds_ovl_ok(a)) return launch_cell_wlds_ovl<4, 2>(a, (hipStream_t)stream); break;
-        case 18: if (cell_direct_ok(a) && cell_wlds_ovl_ok(a)) return launch_cell_wlds_ovl<2, 2>(a, (hipStream_t)stream); break;
-        case 13: if (cell_direct_ok(a) && cell_wlds_ok(a)) return launch_cell_wlds<3, 4>(a, (hipStream_t)stream); break;
-        case 14: if (cell_direct_ok(a) && cell_wlds_ok(a)) return launch_cell_wlds<3, 2>(a, (hipStream_t)stream); break;
-        case 9: if (cell_direct_ok(a) && cell_wlds_ok(a)) return launch_cell_wlds<4, 2>(a, (hipStream_t)stream); break;      // (<4, 4> needs AGPR copies: not built)
-        case 10: if (cell_direct_ok(a) && cell_wlds_ok(a)) return launch_cell_wlds<2, 4>(a, (hipStream_t)stream); break;
-        case 11: if (cell_direct_ok(a) && cell_wlds_ok(a)) return launch_cell_wlds<4, 2>(a, (hipStream_t)stream); break;
-        case 12: if (cell_direct_ok(a) && cell_wlds_ok(a)) return launch_cell_wlds<2, 8>(a, (hipStream_t)stream); break;
-        case 4: if (cell_direct_ok(a)) return launch_cell_direct<4, 1>(a, (hipStream_t)stream); break;
-        case 5: if (cell_direct_ok(a)) return launch_cell_direct<2, 4>(a, (hipStream_t)stream); break;
-        case 6: if (cell_direct_ok(a)) return launch_cell_direct<4, 2>(a, (hipStream_t)stream); break;
-        case 7: if (cell_direct_ok(a)) return launch_cell_direct<2, 2>(a, (hipStream_t)stream); break;
-        default: break;
-    }
-    switch (variant) {
-        case 1: return launch_cell<128, 4, 1>(a, (hipStream_t)stream);
-        case 2: return launch_cell<128, 2, 2>(a, (hipStream_t)stream);
-        case 3: return launch_cell<64, 4, 1>(a, (hipStream_t)stream);
-        default: return launch_cell<64, 2, 2>(a, (hipStream_t)stream);
-    }
+    // tuning / tests: the forced forms, by kernel family (the staged forms agree bit for bit, the LDS-free forms 4-7 among themselves: another k order).
+    // A form this shape is not eligible for, and any other variant, runs the staged default.
+    static const struct { int variant; int (*launch)(const CellArgs&, hipStream_t); bool (*ok)(const CellArgs&); } forms[] = {
+        {15, launch_cell_wlds_ovl<2, 4>, cell_ovl_fits}, {16, launch_cell_wlds_ovl<3, 2>, cell_ovl_fits},
+        {17, launch_cell_wlds_ovl<4, 2>, cell_ovl_fits}, {18, launch_cell_wlds_ovl<2, 2>, cell_ovl_fits},
+        {13, launch_cell_wlds<3, 4>, cell_wlds_fits}, {14, launch_cell_wlds<3, 2>, cell_wlds_fits},
+        {9, launch_cell_wlds<4, 2>, cell_wlds_fits},           // (<4, 4> needs AGPR copies: not built)
+        {10, launch_cell_wlds<2, 4>, cell_wlds_fits}, {11, launch_cell_wlds<4, 2>, cell_wlds_fits}, {12, launch_cell_wlds<2, 8>, cell_wlds_fits},
+        {4, launch_cell_direct<4, 1>, cell_direct_ok}, {5, launch_cell_direct<2, 4>, cell_direct_ok},
+        {6, launch_cell_direct<4, 2>, cell_direct_ok}, {7, launch_cell_direct<2, 2>, cell_direct_ok},
+        {1, launch_cell<128, 4, 1>, nullptr}, {2, launch_cell<128, 2, 2>, nullptr}, {3, launch_cell<64, 4, 1>, nullptr}, {8, launch_cell<64, 2, 2>, nullptr},
+    };
+    for (const auto& f : forms)
+        if (f.variant == variant && (!f.ok || f.ok(a))) return f.launch(a, st);
+    return launch_cell<64, 2, 2>(a, st);
 }
 
-static bool fn_out_argmax_force_direct = getenv("FN_OUT_ARGMAX_DIRECT") != nullptr;     // measurements: the LDS-free form
 int fn_out_argmax_f32(const float* h, int ldh, const float* W, int ldw, const float* bias, int B, int V, int K, uint64_t* best, void* stream) {
     if (!h || !W || !bias || !best) return FN_E_NULL;
     if (B <= 0 || V <= 0 || K <= 0 || (K % 16) != 0 || ldh < K || ldw < K || (ldh & 3) || (ldw & 3)) return FN_E_SHAPE;
     if ((long)B * ldh * 4 >= (1L << 32) || (long)V * ldw * 4 >= (1L << 32)) return FN_E_SHAPE;
     if (((((uintptr_t)h) | ((uintptr_t)W)) & 15) || (((uintptr_t)best) & 7)) return FN_E_ALIGN;
     const size_t lds = (size_t)48 * K * sizeof(float);
-    if (lds <= (size_t)128 * 1024 && !fn_out_argmax_force_direct) {          // weight slice of a workgroup resident in LDS
-        static std::atomic<bool> attr_set[2][32];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return FN_E_SHAPE;
-        const bool eight = (K % 32) == 0 && !getenv("FN_OUT_ARGMAX_4WAVES");
+    if (lds <= (size_t)128 * 1024) {          // weight slice of a workgroup resident in LDS
+        const bool eight = (K % 32) == 0;
         auto k = eight ? out_argmax_lds8_kernel<4> : out_argmax_lds_kernel<8>;
-        if (!attr_set[eight][dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_set[eight][dev].store(true, std::memory_order_release);
-        }
+        if (const int rc = eight ? fn_set_max_lds<out_argmax_lds8_kernel<4>>(144 * 1024, FN_E_SHAPE) : fn_set_max_lds<out_argmax_lds_kernel<8>>(144 * 1024, FN_E_SHAPE))
+            return rc;
         const int grid = ((B + 63) / 64) * ((V + 47) / 48);
         hipLaunchKernelGGL(k, dim3(grid), dim3(eight ? 2 * NT : NT), lds + (eight ? 4 * 3 * 64 * 16 : 0), (hipStream_t)stream, h, (long)ldh, W, (long)ldw, bias, B, V, K,
                            reinterpret_cast<unsigned long long*>(best));
@@ -2123,7 +2082,7 @@ int fn_gru_seq_fwd(const FnGruFwd* scans, int n_scans, void* stream) {
     {   // weight-stationary single launch when the configuration fits one workgroup per CU (gru_persist.hip)
         const int rc = fn_gru_fwd_persist(scans, n_scans, st);
         if (rc != FN_PERSIST_NA) return rc;
-        if (scans[0].variant & 0x4000) return FN_E_UNSUPPORTED;      // the per-step kernels below do not read triple images
+        if (scans[0].variant & FN_GRU_BF16X6) return FN_E_UNSUPPORTED;      // the per-step kernels below do not read triple images
     }
     for (int s = 0; s < n_scans; ++s)          // initial states -> fragment-major (slot 0 of the ping-pong scratch)
         if (scans[s].h0 && !scans[s].h0_frag) {
@@ -2186,7 +2145,7 @@ int fn_gru_seq_bwd(const FnGruBwd* scans, int n_scans, void* stream) {
     {
         const int rc = fn_gru_bwd_persist(scans, n_scans, st);
         if (rc != FN_PERSIST_NA) return rc;
-        if (scans[0].variant & 0x4000) return FN_E_UNSUPPORTED;      // the per-step kernels below do not read triple images
+        if (scans[0].variant & FN_GRU_BF16X6) return FN_E_UNSUPPORTED;      // the per-step kernels below do not read triple images
     }
     for (int it = 0; it <= Tmax; ++it) {
         long big_tiles = 0;

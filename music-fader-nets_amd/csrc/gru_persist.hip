@@ -77,7 +77,7 @@ struct PArgs {
     PScan s[FN_MAX_SCANS];
     int n, ngroups, H;
     int no_hand;          // tuning / tests: the compiler-scheduled K loop instead of kloop_asm.h
-    int spread;           // tests: deal the block ids so that every row group is spread over all XCDs (variant bit 12; see block_group)
+    int spread;           // tests: deal the block ids so that every row group is spread over all XCDs (FN_GRU_SPREAD_XCDS; see block_group)
     u32* sync;            // [ngroups * 32] arrival counters (one per 128-byte line), zero at launch
     u32* err;             // sticky error word
 };
@@ -85,7 +85,7 @@ constexpr int FN_MAX_GROUPS = 64;
 
 // Which (row group, slice) a workgroup is.  Default: group = id mod groups - with 8 (or 16) groups every row group sits on ONE XCD (workgroups are
 // dealt to the XCDs round robin by id), its exchange slab then lives in that XCD's L2.  That is speed only: the hand-over protocol is agent-scope
-// (sc1 stores and loads, agent-scope counters).  spread (FnGruFwd / FnGruBwd.variant bit 12) deals consecutive ids to the slices of one group, so
+// (sc1 stores and loads, agent-scope counters).  spread (FN_GRU_SPREAD_XCDS) deals consecutive ids to the slices of one group, so
 // that every group is spread over all XCDs: the test that correctness does not depend on the placement.
 FN_DEVINL int block_group(int ngroups, int spread) { return spread ? (int)blockIdx.x / ((int)gridDim.x / ngroups) : (int)blockIdx.x % ngroups; }
 FN_DEVINL int block_slice(int ngroups, int spread) { return spread ? (int)blockIdx.x % ((int)gridDim.x / ngroups) : (int)blockIdx.x / ngroups; }
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(NT) void gru_fwd_persist_kernel(const PArgs args) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Forward scan with EXACT split products on the bf16 MFMA ("bf16 x 6", gemm.hip / DESIGN.md; OPT-IN: FnGruFwd.variant bit 14).  Weights and
+// Forward scan with EXACT split products on the bf16 MFMA ("bf16 x 6", gemm.hip / DESIGN.md; OPT-IN: FN_GRU_BF16X6).  Weights and
 // recurrent operand are bf16 TRIPLES (x = hi + mid + lo exactly; fn_frag3_pack image = [row tile 16][k block 32][piece 3][64 lanes][8 bf16]:
 // lane (i, g) of a v_mfma_f32_16x16x32_bf16 operand = row i, k values 8 g .. 8 g + 7 of the block): the W_hh slice is split ONCE per optimiser
 // step (144 KB of LDS per workgroup at H = 512), the new state is split by the gate epilogue that publishes it (6 instead of 4 bytes per
@@ -1948,22 +1948,6 @@ __global__ __launch_bounds__(NT) void gru_bwd_x6_kernel(const QArgs args) {
     }
 }
 
-constexpr int FN_MAX_DEVICES = 32;
-
-int cu_count() {
-    static std::atomic<int> n[FN_MAX_DEVICES];       // write-once per device (a process may drive several GPUs); zero-initialised
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FN_MAX_DEVICES) return 0;
-    int c = n[dev].load(std::memory_order_acquire);
-    if (c == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        c = prop.multiProcessorCount;
-        n[dev].store(c, std::memory_order_release);
-    }
-    return c;
-}
-
 // The weight-stationary kernels spin on counters that OTHER workgroups of the same launch advance: every workgroup of the grid
 // must be resident at the same time.  This is what a cooperative launch would assert; here the occupancy calculator is asked how
 // many workgroups of this kernel (with its dynamic LDS) fit one CU, and a grid beyond cus x that is refused (FN_PERSIST_NA -> the
@@ -1975,8 +1959,8 @@ int launch_k(const Args& a, int grid, size_t lds, int cus, hipStream_t st) {
     // per kernel instance and device: (blocks per CU << 32 | LDS bytes asked for), packed into ONE atomic word so that a reader never
     // pairs the answer for one LDS size with another; recomputed (idempotently) when the LDS size differs
     static std::atomic<unsigned long long> cache[FN_MAX_DEVICES];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FN_MAX_DEVICES) return FN_PERSIST_NA;
+    const int dev = fn_device();
+    if (dev < 0) return FN_PERSIST_NA;
     unsigned long long w = cache[dev].load(std::memory_order_acquire);
     if (w == 0 || (size_t)(w & 0xffffffffull) != lds) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
@@ -1994,6 +1978,13 @@ int launch_k(const Args& a, int grid, size_t lds, int cus, hipStream_t st) {
     return FN_OK;
 }
 
+// compute units the launch of these scans may occupy: the device's, or scans[0].cu_budget when that is smaller
+template <class Scan>
+int budget_cus(const Scan* scans) {
+    const int cus = fn_cu_count();
+    return scans[0].cu_budget > 0 && scans[0].cu_budget < cus ? scans[0].cu_budget : cus;
+}
+
 // bf16 x 6 forward scans: row tiles per wave (1 = 64-row groups, 2 = 128-row groups) of the launch, 0 = not eligible.  H = 512, every scan in
 // full row groups, saved gates, T >= 2, all row groups resident at once.
 int x6_row_tiles(const FnGruFwd* scans, int n_scans, int maxgroups) {
@@ -2009,10 +2000,11 @@ int x6_row_tiles(const FnGruFwd* scans, int n_scans, int maxgroups) {
     return (d64 && g64 <= maxgroups) ? 1 : ((d128 && g128 <= maxgroups) ? 2 : 0);
 }
 
-
-// bf16 x 6 backward scans: row tiles per half (2 = 64-row groups, 1 = 32-row groups), 0 = not eligible.  The shapes gru_bwd_rs_kernel takes: H = 512,
-// every scan in full row groups, T >= 2, more than half of the chip and at most all of it (16 slices x <= 16 groups, all resident).
-int x6_bwd_tiles(const FnGruBwd* scans, int n_scans, int cus) {
+// The shapes of the register-stationary backward (gru_bwd_rs_kernel and its bf16 x 6 form gru_bwd_x6_kernel): row tiles per half (2 = 64-row groups,
+// 1 = 32-row groups), 0 = not eligible.  H = 512, every scan in full row groups, T >= 2, more than half of the chip and at most all of it (16 slices
+// x <= 16 groups, all resident).  half_chip_ok: exactly half of the chip too (g64 * 16 == cus: the caller asked for exactly this with a CU budget -
+// the half-chip launches of the decoder pipeline's backward, 8 groups on 128 CUs); rows32_ok: 32-row groups too.
+int bwd_rs_tiles(const FnGruBwd* scans, int n_scans, int cus, bool half_chip_ok, bool rows32_ok) {
     if (scans[0].H != 512) return 0;
     long g64 = 0, g32 = 0;
     bool d64 = true, d32 = true;
@@ -2023,23 +2015,102 @@ int x6_bwd_tiles(const FnGruBwd* scans, int n_scans, int cus) {
         d64 = d64 && d.B % 64 == 0;
         d32 = d32 && d.B % 32 == 0;
     }
-    // 64-row groups (the encoder shape: 4 scans x 256 rows): 3.05 ms against 3.5 ms on the fp32 MFMA.  32-row groups (a decoder-pipeline launch: 2 scans x
-    // 256 rows x 32 steps) measured SLOWER than the fp32 kernel (353 against 322-337 us: both are bound by the exchange stream through the XCD's L2, which
-    // the triples make 1.5 x wider, and the 12-unit K loops are too short for the store -> arrival -> counter chain): only on request (variant bit 15)
-    const bool th1_ok = (scans[0].variant & 0x8000) != 0;
-    // (g64 * 16 == cus: the caller asked for exactly this with a CU budget - the half-chip launches of the decoder pipeline's backward, 8 groups on 128 CUs)
-    return (d64 && (g64 > 8 || g64 * 16 == cus) && g64 <= 16 && g64 * 16 <= cus) ? 2 : (th1_ok && d32 && g32 > 8 && g32 <= 16 && g32 * 16 <= cus) ? 1 : 0;
+    if (d64 && (g64 > 8 || (half_chip_ok && g64 * 16 == cus)) && g64 <= 16 && g64 * 16 <= cus) return 2;
+    return (rows32_ok && d32 && g32 > 8 && g32 <= 16 && g32 * 16 <= cus) ? 1 : 0;
+}
+
+// bf16 x 6 backward scans.  64-row groups (the encoder shape: 4 scans x 256 rows): 3.05 ms against 3.5 ms on the fp32 MFMA.  32-row groups (a
+// decoder-pipeline launch: 2 scans x 256 rows x 32 steps) measured SLOWER than the fp32 kernel (353 against 322-337 us: both are bound by the exchange
+// stream through the XCD's L2, which the triples make 1.5 x wider, and the 12-unit K loops are too short for the store -> arrival -> counter chain):
+// only on request (FN_GRU_X6_BWD_32ROWS)
+int x6_bwd_tiles(const FnGruBwd* scans, int n_scans, int cus) {
+    return bwd_rs_tiles(scans, n_scans, cus, true, (scans[0].variant & FN_GRU_X6_BWD_32ROWS) != 0);
+}
+
+// smallest row block of the 32-slice kernels whose group count fits on the chip with one workgroup per CU (FN_GRU_ROWS_MASK: that block or none);
+// 0 = none fits
+template <class Scan>
+int pick_rows(const Scan* scans, int n_scans, int maxgroups) {
+    const int force_rows = scans[0].variant & FN_GRU_ROWS_MASK;
+    for (const int rpw : {16, 32, 64, 128}) {
+        if (force_rows && force_rows != rpw) continue;
+        long groups = 0;
+        for (int s = 0; s < n_scans; ++s) groups += (scans[s].B + rpw - 1) / rpw;
+        if (groups <= maxgroups) return rpw;
+    }
+    return 0;
+}
+
+// K split of the 32-slice kernels' tiling for a row block
+int k_split(int rpw, int variant) { return rpw == 16 ? 4 : rpw == 32 ? 2 : (rpw == 64 && !(variant & FN_GRU_ALT_TILING)) ? 2 : 1; }
+
+// The per-scan fields of a forward launch, its row groups of rows_per_group rows (the last one of a scan possibly partial) and sizes.  The initial
+// states that do not come as images (h0_frag) are packed into slab 0 of each scan's frag_ws (what step 0 reads), one launch per scan in scan order:
+// as bf16 triples for the bf16 x 6 kernels, as fp32 fragments otherwise.  FN_OK or the packing launch's error.
+int fill_fwd_args(PArgs& a, const FnGruFwd* scans, int n_scans, int rows_per_group, bool x6, hipStream_t st) {
+    a.n = n_scans;
+    a.H = scans[0].H;
+    int groups = 0;
+    for (int s = 0; s < n_scans; ++s) {
+        const FnGruFwd& d = scans[s];
+        PScan& f = a.s[s];
+        f.w_frag = d.w_hh_frag; f.b_hh = d.b_hh; f.b_ih = d.b_ih; f.h0 = d.h0;
+        f.gx_dense = d.gx_dense; f.gx_table = d.gx_table; f.idx = d.idx; f.gx_rowbias = d.gx_rowbias;
+        f.h_all = d.h_all; f.gates = d.gates; f.xf = d.frag_ws; f.h0f = d.h0_frag; f.hlf = d.h_last_frag;
+        f.idx_ld = d.idx_ld; f.idx_shift = d.idx_shift; f.start_token = d.start_token; f.reverse = d.reverse;
+        f.B = d.B; f.T = d.T;
+        f.group0 = groups;
+        groups += (d.B + rows_per_group - 1) / rows_per_group;
+        if (d.h0 && !d.h0_frag) {
+            const int rc = x6 ? fn_frag3_pack(d.h0, d.B, d.H, d.H, d.frag_ws, st) : launch_pack(d.h0, d.B, d.H, d.H, d.frag_ws, st);
+            if (rc != FN_OK) return rc;
+        }
+    }
+    a.ngroups = groups;
+    return FN_OK;
+}
+
+// the same for a backward launch (nothing to pack)
+void fill_bwd_args(QArgs& a, const FnGruBwd* scans, int n_scans, int rows_per_group) {
+    a.n = n_scans;
+    a.H = scans[0].H;
+    int groups = 0;
+    for (int s = 0; s < n_scans; ++s) {
+        const FnGruBwd& d = scans[s];
+        QScan& f = a.s[s];
+        f.wt_frag = d.w_hh_t_frag; f.h0 = d.h0; f.h_all = d.h_all; f.gates = d.gates;
+        f.dh_last = d.dh_last; f.dh_ext = d.dh_ext;
+        f.dgx_all = d.dgx_all; f.dghn_all = d.dghn_all; f.dh0 = d.dh0;
+        f.rowsum = d.dgx_rowsum; f.rowsum_n = d.dghn_rowsum; f.xf = d.frag_ws;
+        f.B = d.B; f.T = d.T;
+        f.group0 = groups;
+        groups += (d.B + rows_per_group - 1) / rows_per_group;
+    }
+    a.ngroups = groups;
+}
+
+// The arrival counters (scans[0]'s sync_ws), the sticky error word (err_ws, or the last 128 bytes of sync_ws) and the block placement of a launch.
+// The counters are zero-filled on the stream unless the caller hands over zeroed ones (FN_GRU_SYNC_ZEROED); the error word never (it is sticky).
+template <class Args, class Scan>
+int begin_sync(Args& a, const Scan& s0, hipStream_t st) {
+    a.sync = reinterpret_cast<u32*>(s0.sync_ws);
+    a.err = s0.err_ws ? reinterpret_cast<u32*>(s0.err_ws) : a.sync + FN_MAX_GROUPS * 32;
+    a.spread = (s0.variant & FN_GRU_SPREAD_XCDS) ? 1 : 0;
+    if (!(s0.variant & FN_GRU_SYNC_ZEROED)) {
+        const hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)FN_MAX_GROUPS * 32 * 4, st);
+        if (me != hipSuccess) return (int)me;
+    }
+    return FN_OK;
 }
 
 }  // namespace
 
 extern "C" size_t fn_gru_sync_ws_bytes() { return ((size_t)FN_MAX_GROUPS * 32 + 32) * 4; }
 
-// would fn_gru_seq_fwd run this call with variant bit 14 (bf16 x 6)?  Shapes only: pointers are not looked at beyond NULL-ness of `gates`.
+// would fn_gru_seq_fwd run this call with FN_GRU_BF16X6 (bf16 x 6)?  Shapes only: pointers are not looked at beyond NULL-ness of `gates`.
 extern "C" int fn_gru_fwd_x6_ok(const FnGruFwd* scans, int n_scans) {
     if (!scans || n_scans < 1 || n_scans > FN_MAX_SCANS) return 0;
-    int cus = cu_count();
-    if (scans[0].cu_budget > 0 && scans[0].cu_budget < cus) cus = scans[0].cu_budget;
+    const int cus = budget_cus(scans);
     if (cus < 32) return 0;
     const int maxgroups = cus / 32 < FN_MAX_GROUPS ? cus / 32 : FN_MAX_GROUPS;
     return x6_row_tiles(scans, n_scans, maxgroups) != 0;
@@ -2047,9 +2118,7 @@ extern "C" int fn_gru_fwd_x6_ok(const FnGruFwd* scans, int n_scans) {
 
 extern "C" int fn_gru_bwd_x6_ok(const FnGruBwd* scans, int n_scans) {
     if (!scans || n_scans < 1 || n_scans > FN_MAX_SCANS) return 0;
-    int cus = cu_count();
-    if (scans[0].cu_budget > 0 && scans[0].cu_budget < cus) cus = scans[0].cu_budget;
-    return x6_bwd_tiles(scans, n_scans, cus) != 0;
+    return x6_bwd_tiles(scans, n_scans, budget_cus(scans)) != 0;
 }
 
 int fn_gru_fwd_persist(const FnGruFwd* scans, int n_scans, hipStream_t st) {
@@ -2068,102 +2137,43 @@ int fn_gru_fwd_persist(const FnGruFwd* scans, int n_scans, hipStream_t st) {
         Tmax = d.T > Tmax ? d.T : Tmax;
     }
     if (Tmax < 2) return FN_PERSIST_NA;                 // nothing to keep stationary
-    int cus = cu_count();
-    if (scans[0].cu_budget > 0 && scans[0].cu_budget < cus) cus = scans[0].cu_budget;
+    const int cus = budget_cus(scans);
     const int nslices = H / 16;
     if (cus <= 0 || nslices > cus) return FN_PERSIST_NA;
     const int maxgroups = cus / nslices < FN_MAX_GROUPS ? cus / nslices : FN_MAX_GROUPS;
-    if (scans[0].variant & 0x4000) {
+    const int variant = scans[0].variant;
+    PArgs a;
+    if (variant & FN_GRU_BF16X6) {
         // exact split products on the bf16 MFMA (gru_fwd_x6_kernel).  The caller hands over w_hh_frag = fn_frag3_pack image and
         // frag_ws of 3 * fn_frag_floats(B, H) floats.  Eligibility: x6_row_tiles() (the same predicate fn_gru_fwd_x6_ok answers with).
-        for (int s = 0; s < n_scans; ++s) {
-            const FnGruFwd& d = scans[s];
-            if (d.h0_frag && !d.h0) return FN_E_NULL;
-            if ((((uintptr_t)d.h0_frag) | ((uintptr_t)d.h_last_frag) | (uintptr_t)d.h0) & 15) return FN_E_ALIGN;
-        }
         const int mt = x6_row_tiles(scans, n_scans, maxgroups);
         if (!mt) return FN_E_UNSUPPORTED;
-        PArgs a;
-        a.n = n_scans; a.H = H; a.no_hand = 0; a.spread = (scans[0].variant & 0x1000) ? 1 : 0;
-        a.sync = reinterpret_cast<u32*>(scans[0].sync_ws);
-        int groups = 0;
-        for (int s = 0; s < n_scans; ++s) {
-            const FnGruFwd& d = scans[s];
-            PScan& f = a.s[s];
-            f.w_frag = d.w_hh_frag; f.b_hh = d.b_hh; f.b_ih = d.b_ih; f.h0 = d.h0;
-            f.gx_dense = d.gx_dense; f.gx_table = d.gx_table; f.idx = d.idx; f.gx_rowbias = d.gx_rowbias;
-            f.h_all = d.h_all; f.gates = d.gates; f.xf = d.frag_ws; f.h0f = d.h0_frag; f.hlf = d.h_last_frag;
-            if (d.h0 && !d.h0_frag) {                   // the initial state as triples into slab 0 (what step 0 reads)
-                const int rc = fn_frag3_pack(d.h0, d.B, d.H, d.H, d.frag_ws, st);
-                if (rc != FN_OK) return rc;
-            }
-            f.idx_ld = d.idx_ld; f.idx_shift = d.idx_shift; f.start_token = d.start_token; f.reverse = d.reverse;
-            f.B = d.B; f.T = d.T;
-            f.group0 = groups;
-            groups += d.B / (64 * mt);
-        }
-        a.ngroups = groups;
-        a.err = scans[0].err_ws ? reinterpret_cast<u32*>(scans[0].err_ws) : a.sync + FN_MAX_GROUPS * 32;
-        if (!(scans[0].variant & 0x200)) {
-            hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)FN_MAX_GROUPS * 32 * 4, st);
-            if (me != hipSuccess) return (int)me;
-        }
+        a.no_hand = 0;
+        int rc = fill_fwd_args(a, scans, n_scans, 64 * mt, true, st);
+        if (rc == FN_OK) rc = begin_sync(a, scans[0], st);
+        if (rc != FN_OK) return rc;
+        const int grid = a.ngroups * nslices;
         const size_t lds = (size_t)3 * 16 * 3 * 1024 + (size_t)4 * 3 * RT * 4 + 16;
-        // ping-pong form (kloop3_asm.h): exactly one input source per scan; variant bit 15 keeps the single-group kernel (tests)
-        bool pp = !(scans[0].variant & 0x8000) && 2 * groups <= FN_MAX_GROUPS;
+        // ping-pong form (kloop3_asm.h): exactly one input source per scan; FN_GRU_X6_SINGLE_GROUP keeps the single-group kernel (tests)
+        bool pp = !(variant & FN_GRU_X6_SINGLE_GROUP) && 2 * a.ngroups <= FN_MAX_GROUPS;
         for (int s = 0; s < n_scans && pp; ++s) pp = (scans[s].gx_table != nullptr) != (scans[s].gx_dense != nullptr);
-        int rc;
-        if (pp) rc = mt == 1 ? launch_k<PArgs, gru_fwd_x6pp_kernel<2>>(a, groups * nslices, lds, cus, st)
-                             : launch_k<PArgs, gru_fwd_x6pp_kernel<1>>(a, groups * nslices, lds, cus, st);
-        else rc = mt == 1 ? launch_k<PArgs, gru_fwd_x6_kernel<1>>(a, groups * nslices, lds, cus, st)
-                          : launch_k<PArgs, gru_fwd_x6_kernel<2>>(a, groups * nslices, lds, cus, st);
+        if (pp) rc = mt == 1 ? launch_k<PArgs, gru_fwd_x6pp_kernel<2>>(a, grid, lds, cus, st)
+                             : launch_k<PArgs, gru_fwd_x6pp_kernel<1>>(a, grid, lds, cus, st);
+        else rc = mt == 1 ? launch_k<PArgs, gru_fwd_x6_kernel<1>>(a, grid, lds, cus, st)
+                          : launch_k<PArgs, gru_fwd_x6_kernel<2>>(a, grid, lds, cus, st);
         return rc == FN_PERSIST_NA ? FN_E_UNSUPPORTED : rc;
     }
-    // smallest row block whose group count fits on the chip with one workgroup per CU
-    int rpw = 0;
-    const int cand[4] = {16, 32, 64, 128};
-    const int force_rows = scans[0].variant & 0xFF;         // tuning / tests: take this row block or none
-    for (int c = 0; c < 4 && !rpw; ++c) {
-        if (force_rows && force_rows != cand[c]) continue;
-        long groups = 0;
-        for (int s = 0; s < n_scans; ++s) groups += (scans[s].B + cand[c] - 1) / cand[c];
-        if (groups <= maxgroups) rpw = cand[c];
-    }
+    const int rpw = pick_rows(scans, n_scans, maxgroups);
     if (!rpw) return FN_PERSIST_NA;
-
-    PArgs a;
-    a.n = n_scans;
-    a.H = H;
-    a.no_hand = (scans[0].variant & 0x400) ? 1 : 0;
-    a.spread = (scans[0].variant & 0x1000) ? 1 : 0;
-    a.sync = reinterpret_cast<u32*>(scans[0].sync_ws);
-    int groups = 0;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruFwd& d = scans[s];
-        PScan& f = a.s[s];
-        f.w_frag = d.w_hh_frag; f.b_hh = d.b_hh; f.b_ih = d.b_ih; f.h0 = d.h0;
-        f.gx_dense = d.gx_dense; f.gx_table = d.gx_table; f.idx = d.idx; f.gx_rowbias = d.gx_rowbias;
-        f.h_all = d.h_all; f.gates = d.gates; f.xf = d.frag_ws; f.h0f = d.h0_frag; f.hlf = d.h_last_frag;
-        f.idx_ld = d.idx_ld; f.idx_shift = d.idx_shift; f.start_token = d.start_token; f.reverse = d.reverse;
-        f.B = d.B; f.T = d.T;
-        f.group0 = groups;
-        groups += (d.B + rpw - 1) / rpw;
-        if (d.h0 && !d.h0_frag) {
-            const int rc = launch_pack(d.h0, d.B, d.H, d.H, d.frag_ws, st);
-            if (rc != FN_OK) return rc;
-        }
-    }
-    a.ngroups = groups;
-    a.err = scans[0].err_ws ? reinterpret_cast<u32*>(scans[0].err_ws) : a.sync + FN_MAX_GROUPS * 32;
-    if (!(scans[0].variant & 0x200)) {                      // bit 9: the caller hands over counters that are already zero
-        hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)FN_MAX_GROUPS * 32 * 4, st);      // counters only: err is sticky
-        if (me != hipSuccess) return (int)me;
-    }
-    const int grid = groups * nslices;
-    const int wk = rpw == 16 ? 4 : rpw == 32 ? 2 : (rpw == 64 && !(scans[0].variant & 0x100)) ? 2 : 1;     // K split of the chosen tiling
+    a.no_hand = (variant & FN_GRU_COMPILER_LOOPS) ? 1 : 0;
+    if (const int rc = fill_fwd_args(a, scans, n_scans, rpw, false, st)) return rc;
+    if (const int rc = begin_sync(a, scans[0], st)) return rc;
+    const int grid = a.ngroups * nslices;
+    const int wk = k_split(rpw, variant);
     const size_t lds = ((size_t)3 * H * 16 + (size_t)wk * (rpw / 16) * 3 * RT) * 4 + 16;
     // ping-pong form (two halves per workgroup, kloop2_asm.h): H = 512, 128- or 64-row groups, full row groups, saved gates, one input source
-    bool pp = H == 512 && (rpw == 128 || (rpw == 64 && wk == 2)) && !(scans[0].variant & 0xC00) && 2 * groups <= FN_MAX_GROUPS;
+    bool pp = H == 512 && (rpw == 128 || (rpw == 64 && wk == 2)) && !(variant & (FN_GRU_COMPILER_LOOPS | FN_GRU_NO_PINGPONG)) &&
+              2 * a.ngroups <= FN_MAX_GROUPS;
     for (int s = 0; s < n_scans && pp; ++s) {
         const FnGruFwd& d = scans[s];
         pp = d.B % rpw == 0 && d.gates && d.T >= 2 && ((d.gx_table != nullptr) != (d.gx_dense != nullptr));
@@ -2172,7 +2182,7 @@ int fn_gru_fwd_persist(const FnGruFwd* scans, int n_scans, hipStream_t st) {
     switch (rpw) {
         case 128: return launch_k<PArgs, gru_fwd_persist_kernel<4, 1, 2, 4>>(a, grid, lds, cus, st);
         case 64:
-            if (scans[0].variant & 0x100) return launch_k<PArgs, gru_fwd_persist_kernel<4, 1, 1, 4>>(a, grid, lds, cus, st);
+            if (variant & FN_GRU_ALT_TILING) return launch_k<PArgs, gru_fwd_persist_kernel<4, 1, 1, 4>>(a, grid, lds, cus, st);
             return launch_k<PArgs, gru_fwd_persist_kernel<2, 2, 2, 4>>(a, grid, lds, cus, st);
         case 32: return launch_k<PArgs, gru_fwd_persist_kernel<2, 2, 1, 4>>(a, grid, lds, cus, st);
         default: return launch_k<PArgs, gru_fwd_persist_kernel<1, 4, 1, 4>>(a, grid, lds, cus, st);
@@ -2192,122 +2202,46 @@ int fn_gru_bwd_persist(const FnGruBwd* scans, int n_scans, hipStream_t st) {
         Tmax = d.T > Tmax ? d.T : Tmax;
     }
     if (Tmax < 2) return FN_PERSIST_NA;
-    int cus = cu_count();
-    if (scans[0].cu_budget > 0 && scans[0].cu_budget < cus) cus = scans[0].cu_budget;
+    const int cus = budget_cus(scans);
     const int nslices = H / 16;
     if (cus <= 0 || nslices > cus) return FN_PERSIST_NA;
-    const int force_rows = scans[0].variant & 0xFF;         // tuning / tests: take this row block or none
-    if (scans[0].variant & 0x4000) {
+    const int variant = scans[0].variant;
+    QArgs a;
+    a.no_hand = 0;
+    if (variant & FN_GRU_BF16X6) {
         // exact split products on the bf16 MFMA (gru_bwd_x6_kernel): w_hh_t_frag = the bf16 triple image of W_hh^T (fn_weight_images kind 4), frag_ws of
         // 3 * fn_frag_floats(B, 3H) floats (the gate gradients are exchanged as triples).  Eligibility = fn_gru_bwd_x6_ok.
         const int th = x6_bwd_tiles(scans, n_scans, cus);
         if (!th) return FN_E_UNSUPPORTED;
-        QArgs a;
-        a.n = n_scans; a.H = H; a.no_hand = 0; a.spread = (scans[0].variant & 0x1000) ? 1 : 0;
-        a.sync = reinterpret_cast<u32*>(scans[0].sync_ws);
-        int groups = 0;
-        for (int s = 0; s < n_scans; ++s) {
-            const FnGruBwd& d = scans[s];
-            QScan& f = a.s[s];
-            f.wt_frag = d.w_hh_t_frag; f.h0 = d.h0; f.h_all = d.h_all; f.gates = d.gates;
-            f.dh_last = d.dh_last; f.dh_ext = d.dh_ext;
-            f.dgx_all = d.dgx_all; f.dghn_all = d.dghn_all; f.dh0 = d.dh0;
-            f.rowsum = d.dgx_rowsum; f.rowsum_n = d.dghn_rowsum; f.xf = d.frag_ws;
-            f.B = d.B; f.T = d.T;
-            f.group0 = groups;
-            groups += d.B / (32 * th);
-        }
-        a.ngroups = groups;
-        a.err = scans[0].err_ws ? reinterpret_cast<u32*>(scans[0].err_ws) : a.sync + FN_MAX_GROUPS * 32;
-        if (!(scans[0].variant & 0x200)) {
-            hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)FN_MAX_GROUPS * 32 * 4, st);
-            if (me != hipSuccess) return (int)me;
-        }
+        fill_bwd_args(a, scans, n_scans, 32 * th);
+        if (const int rc = begin_sync(a, scans[0], st)) return rc;
         const size_t lds = (size_t)4 * 11 * 3072 + (size_t)4 * (2 * th) * RT * 4 + 16;
-        const int rc = th == 2 ? launch_k<QArgs, gru_bwd_x6_kernel<2>>(a, groups * 16, lds, cus, st) : launch_k<QArgs, gru_bwd_x6_kernel<1>>(a, groups * 16, lds, cus, st);
+        const int rc = th == 2 ? launch_k<QArgs, gru_bwd_x6_kernel<2>>(a, a.ngroups * 16, lds, cus, st) : launch_k<QArgs, gru_bwd_x6_kernel<1>>(a, a.ngroups * 16, lds, cus, st);
         return rc == FN_PERSIST_NA ? FN_E_UNSUPPORTED : rc;
     }
-    // Register-stationary ping-pong form (gru_bwd_rs_kernel): H = 512, 16 slices of 32 columns x up to 16 groups of 64 (or 32) rows, every group
-    // full, more than half of the chip used (smaller problems keep the 32-slice kernels).  Variant bits 10 / 11 / 13 select the older loops.
-    if (H == 512 && !(scans[0].variant & 0x2C00) && !force_rows) {
-        long g64 = 0, g32 = 0;
-        bool d64 = true, d32 = true;
-        for (int s = 0; s < n_scans; ++s) {
-            const FnGruBwd& d = scans[s];
-            g64 += d.B / 64; g32 += d.B / 32;
-            d64 = d64 && d.B % 64 == 0 && d.T >= 2;
-            d32 = d32 && d.B % 32 == 0 && d.T >= 2;
-        }
-        const int th = (d64 && g64 > 8 && g64 <= 16 && g64 * 16 <= cus) ? 2 : (d32 && g32 > 8 && g32 <= 16 && g32 * 16 <= cus) ? 1 : 0;
-        if (th) {
-            QArgs a;
-            a.n = n_scans; a.H = H; a.no_hand = 0; a.spread = (scans[0].variant & 0x1000) ? 1 : 0;
-            a.sync = reinterpret_cast<u32*>(scans[0].sync_ws);
-            int groups = 0;
-            for (int s = 0; s < n_scans; ++s) {
-                const FnGruBwd& d = scans[s];
-                QScan& f = a.s[s];
-                f.wt_frag = d.w_hh_t_frag; f.h0 = d.h0; f.h_all = d.h_all; f.gates = d.gates;
-                f.dh_last = d.dh_last; f.dh_ext = d.dh_ext;
-                f.dgx_all = d.dgx_all; f.dghn_all = d.dghn_all; f.dh0 = d.dh0;
-                f.rowsum = d.dgx_rowsum; f.rowsum_n = d.dghn_rowsum; f.xf = d.frag_ws;
-                f.B = d.B; f.T = d.T;
-                f.group0 = groups;
-                groups += d.B / (32 * th);
-            }
-            a.ngroups = groups;
-            a.err = scans[0].err_ws ? reinterpret_cast<u32*>(scans[0].err_ws) : a.sync + FN_MAX_GROUPS * 32;
-            if (!(scans[0].variant & 0x200)) {
-                hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)FN_MAX_GROUPS * 32 * 4, st);
-                if (me != hipSuccess) return (int)me;
-            }
-            const size_t lds = ((size_t)3 * H * 16 + (size_t)2 * 4 * (2 * th) * RT) * 4 + 16;
-            const int rc = th == 2 ? launch_k<QArgs, gru_bwd_rs_kernel<2>>(a, groups * 16, lds, cus, st) : launch_k<QArgs, gru_bwd_rs_kernel<1>>(a, groups * 16, lds, cus, st);
-            if (rc != FN_PERSIST_NA) return rc;
-        }
+    // Register-stationary ping-pong form (gru_bwd_rs_kernel): 16 slices of 32 columns x up to 16 groups of 64 (or 32) rows, the shapes of
+    // bwd_rs_tiles (smaller problems keep the 32-slice kernels).  FN_GRU_COMPILER_LOOPS / _NO_PINGPONG / _NO_RS_BWD and a forced row block select the
+    // 32-slice loops.
+    const int th = (variant & (FN_GRU_COMPILER_LOOPS | FN_GRU_NO_PINGPONG | FN_GRU_NO_RS_BWD | FN_GRU_ROWS_MASK)) ? 0 : bwd_rs_tiles(scans, n_scans, cus, false, true);
+    if (th) {
+        fill_bwd_args(a, scans, n_scans, 32 * th);
+        if (const int rc = begin_sync(a, scans[0], st)) return rc;
+        const size_t lds = ((size_t)3 * H * 16 + (size_t)2 * 4 * (2 * th) * RT) * 4 + 16;
+        const int rc = th == 2 ? launch_k<QArgs, gru_bwd_rs_kernel<2>>(a, a.ngroups * 16, lds, cus, st) : launch_k<QArgs, gru_bwd_rs_kernel<1>>(a, a.ngroups * 16, lds, cus, st);
+        if (rc != FN_PERSIST_NA) return rc;
     }
     const int maxgroups = cus / nslices < FN_MAX_GROUPS ? cus / nslices : FN_MAX_GROUPS;
-    int rpw = 0;
-    const int cand[4] = {16, 32, 64, 128};
-    for (int c = 0; c < 4 && !rpw; ++c) {
-        if (force_rows && force_rows != cand[c]) continue;
-        long groups = 0;
-        for (int s = 0; s < n_scans; ++s) groups += (scans[s].B + cand[c] - 1) / cand[c];
-        if (groups <= maxgroups) rpw = cand[c];
-    }
+    const int rpw = pick_rows(scans, n_scans, maxgroups);
     if (!rpw) return FN_PERSIST_NA;
-
-    QArgs a;
-    a.n = n_scans;
-    a.H = H;
-    a.no_hand = (scans[0].variant & 0x400) ? 1 : 0;
-    a.spread = (scans[0].variant & 0x1000) ? 1 : 0;
-    a.sync = reinterpret_cast<u32*>(scans[0].sync_ws);
-    int groups = 0;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruBwd& d = scans[s];
-        QScan& f = a.s[s];
-        f.wt_frag = d.w_hh_t_frag; f.h0 = d.h0; f.h_all = d.h_all; f.gates = d.gates;
-        f.dh_last = d.dh_last; f.dh_ext = d.dh_ext;
-        f.dgx_all = d.dgx_all; f.dghn_all = d.dghn_all; f.dh0 = d.dh0;
-        f.rowsum = d.dgx_rowsum; f.rowsum_n = d.dghn_rowsum; f.xf = d.frag_ws;
-        f.B = d.B; f.T = d.T;
-        f.group0 = groups;
-        groups += (d.B + rpw - 1) / rpw;
-    }
-    a.ngroups = groups;
-    a.err = scans[0].err_ws ? reinterpret_cast<u32*>(scans[0].err_ws) : a.sync + FN_MAX_GROUPS * 32;
-    if (!(scans[0].variant & 0x200)) {
-        hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)FN_MAX_GROUPS * 32 * 4, st);
-        if (me != hipSuccess) return (int)me;
-    }
-    const int grid = groups * nslices;
-    const int wk = rpw == 16 ? 4 : rpw == 32 ? 2 : (rpw == 64 && !(scans[0].variant & 0x100)) ? 2 : 1;
-    const size_t lds = ((size_t)3 * H * 16 + (size_t)2 * wk * (rpw / 16) * RT) * 4 + 16;
+    a.no_hand = (variant & FN_GRU_COMPILER_LOOPS) ? 1 : 0;
+    fill_bwd_args(a, scans, n_scans, rpw);
+    if (const int rc = begin_sync(a, scans[0], st)) return rc;
+    const int grid = a.ngroups * nslices;
+    const size_t lds = ((size_t)3 * H * 16 + (size_t)2 * k_split(rpw, variant) * (rpw / 16) * RT) * 4 + 16;
     switch (rpw) {
         case 128: return launch_k<QArgs, gru_bwd_persist_kernel<4, 1, 2, 8>>(a, grid, lds, cus, st);
         case 64:
-            if (scans[0].variant & 0x100) return launch_k<QArgs, gru_bwd_persist_kernel<4, 1, 1, 8>>(a, grid, lds, cus, st);
+            if (variant & FN_GRU_ALT_TILING) return launch_k<QArgs, gru_bwd_persist_kernel<4, 1, 1, 8>>(a, grid, lds, cus, st);
             return launch_k<QArgs, gru_bwd_persist_kernel<2, 2, 2, 8>>(a, grid, lds, cus, st);
         case 32: return launch_k<QArgs, gru_bwd_persist_kernel<2, 2, 1, 8>>(a, grid, lds, cus, st);
         default: return launch_k<QArgs, gru_bwd_persist_kernel<1, 4, 1, 8>>(a, grid, lds, cus, st);

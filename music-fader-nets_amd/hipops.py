@@ -54,7 +54,7 @@ class HipOps:
         self._ws = {}
         self._retired = []
         self.cell_variant = 0     # FnGruCell.variant (tuning / tests)
-        self.dw_x6 = arith.default() == arith.BF16X6        # arithmetic of the deep products (the package default; a model sets its own choice: arith.py): True = exact bf16 triple splits on the bf16 MFMA (FN_GEMM_BF16X6, FnGruFwd.variant bit 14), False = fp32 MFMA
+        self.dw_x6 = arith.default() == arith.BF16X6        # arithmetic of the deep products (the package default; a model sets its own choice: arith.py): True = exact bf16 triple splits on the bf16 MFMA (FN_GEMM_BF16X6, FN_GRU_BF16X6), False = fp32 MFMA
         self.x6_wide = True       # with dw_x6: 128 x 256 output tiles (FN_GEMM_X6_WIDE) where the product has >= 256 columns - with TWICE the K ranges the caller asked for (the same number of workgroups); False: 128 x 128 tiles
         self.nt_x6 = True         # with dw_x6: the big Linear-forward / dX products (whole 128 x 128 tiles, K % 32 == 0) on the bf16 x 6 kernel too; False: fp32 MFMA (A/B measurements)
         self.x6_per_tile = False  # A/B, tests: the producer / consumer bf16 x 6 kernels as one workgroup per output tile / (tile, K range) item (round 6: one per CU walking its items)
@@ -262,7 +262,7 @@ class HipOps:
             ent["pool"].zero_()
         region = ent["pool"][ent["next"]]
         ent["next"] = (ent["next"] + 1) % self.SYNC_REGIONS
-        return region, err, 0x200
+        return region, err, _lib.GRU_SYNC_ZEROED
 
     def gru_sync_error(self, clear=False):
         """True when a weight-stationary launch (scan or single-launch decode) gave up waiting: ONE D2H copy of all the sticky
@@ -324,7 +324,7 @@ class HipOps:
             d.frag_ws = _p(self._frag_ws("fragf", i, 3 * self.frag_floats(s["B"], s["H"])))      # 2 slabs of fp32 fragments, or 2 of bf16 triples (x6)
             d.sync_ws, d.err_ws, d.variant = (_p(sync[0]), _p(sync[1]), int(variant) | sync[2]) if persistent else (None, None, int(variant))
             if x6:
-                d.w_hh_frag, d.variant = _p(s["w_hh_frag3"]), d.variant | 0x4000
+                d.w_hh_frag, d.variant = _p(s["w_hh_frag3"]), d.variant | _lib.GRU_BF16X6
         _lib.check(self.lib.fn_gru_seq_fwd(arr, len(scans), self.stream()), "fn_gru_seq_fwd (bf16 x 6)" if x6 else "fn_gru_seq_fwd")
 
     def frag3_pack(self, src, dst):
@@ -358,11 +358,11 @@ class HipOps:
         c.gx_table, c.gx_rowbias, c.start_token = _p(gx_table), _p(gx_rowbias), int(start_token)
         c.variant = int(self.cell_variant if variant is None else variant)
         if self.dw_x6 and self.cell_x6 and variant is None and B >= self.cell_x6_rows:
-            # FnGruCell.variant bit 14: the cell on the bf16 MFMA with exact triple splits where the shape allows it (B % 128 == 0, H % 32 == 0, K1 % 32 == 0), else
+            # FnGruCell.variant | FN_GRU_BF16X6: the cell on the bf16 MFMA with exact triple splits where the shape allows it (B % 128 == 0, H % 32 == 0, K1 % 32 == 0), else
             # the fp32 cells.  Measured (scratch/r6_bench_decode_cells.py, us per token of the tokens-only decode): 2048 rows 90.0 against 95.7, 1536 rows 87.2
             # against 76.6, 1024 rows 87.2 against 59.5 - one 128-row workgroup per CU takes ~28 / 48 us for the 16 / 32 blocks of the two cells whatever the row
             # count, so it only pays where the fp32 cells need every CU: from 2048 rows on
-            c.variant |= 0x4000
+            c.variant |= _lib.GRU_BF16X6
         if idx is not None:
             if idx.dtype != torch.int32 or idx.dim() != 1 or idx.shape[0] != B:
                 raise RuntimeError("gru_cell: idx must be a [B] int32 column")
@@ -425,13 +425,13 @@ class HipOps:
             d.frag_ws = _p(self._frag_ws("fragb", i, 3 * self.frag_floats(s["B"], 3 * s["H"])))      # 2 slabs of fp32 fragments, or 2 of bf16 triples (x6)
             d.sync_ws, d.err_ws, d.variant = (_p(sync[0]), _p(sync[1]), int(variant) | sync[2]) if persistent else (None, None, int(variant))
             if x6:
-                d.w_hh_t_frag, d.variant = _p(s["w_hh_t_frag3"]), d.variant | 0x4000
+                d.w_hh_t_frag, d.variant = _p(s["w_hh_t_frag3"]), d.variant | _lib.GRU_BF16X6
         rc = self.lib.fn_gru_seq_bwd(arr, len(scans), self.stream())
         if rc == _lib.FN_E_UNSUPPORTED and x6 and auto:
             # the shape predicate said yes, a launch-time check (alignment, occupancy) said no: nothing was launched, and a backward launch hands only
             # fp32 tensors on - the fp32 kernels take it (a FORCED x6=True still raises)
             for d, s in zip(arr, scans):
-                d.w_hh_t_frag, d.variant = _p(s["w_hh_t_frag"]), d.variant & ~0x4000
+                d.w_hh_t_frag, d.variant = _p(s["w_hh_t_frag"]), d.variant & ~_lib.GRU_BF16X6
             x6 = False
             rc = self.lib.fn_gru_seq_bwd(arr, len(scans), self.stream())
         _lib.check(rc, "fn_gru_seq_bwd (bf16 x 6)" if x6 else "fn_gru_seq_bwd")

@@ -19,6 +19,17 @@ def test_header_symbols_exported():
     assert lib.fn_strerror(-2) == b"unsupported or inconsistent sizes"
 
 
+def test_flag_constants_match_the_header():
+    """every FN_GRU_* / FN_GEMM_* bit of include/fadernets.h has its _lib mirror (GRU_* / GEMM_*) with the same value"""
+    load_package()
+    from music_fader_nets_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "fadernets.h")).read()
+    flags = dict(re.findall(r"^#define FN_((?:GRU|GEMM)_[A-Z0-9_]+)\s+(0x[0-9A-Fa-f]+)\b", hdr, re.M))
+    assert sum(k.startswith("GRU_") for k in flags) == 10 and sum(k.startswith("GEMM_") for k in flags) == 5, sorted(flags)
+    for name, value in flags.items():
+        assert getattr(_lib, name) == int(value, 16), name
+
+
 def test_argument_errors_without_gpu():
     """Argument validation happens before any launch, so it is testable on the CPU box."""
     load_package()

@@ -148,7 +148,7 @@ def test_gru_cell_dense(ops, B, H, K1, mode, variant):
 @pytest.mark.parametrize("B,H,K1,mode", [(2048, 512, 512, "dense"), (1024, 512, 0, "table"), (768, 512, 0, "table0"), (128, 64, 32, "dense"), (256, 96, 64, "dense"),
                                          (1280, 512, 512, "dense_rb")])
 def test_gru_cell_bf16x6(ops, B, H, K1, mode):
-    """gru_cell_x6_kernel (round 6; FnGruCell.variant bit 14): one GRUCell step of a large batch on the bf16 MFMA with exact triple splits - producer / consumer
+    """gru_cell_x6_kernel (round 6; FnGruCell.variant | FN_GRU_BF16X6): one GRUCell step of a large batch on the bf16 MFMA with exact triple splits - producer / consumer
     form, [r | z | n_x | n_h] column tiles, gate epilogue on the producer wavefronts - against tests/fake_ops.py (torch nn.GRUCell semantics) at the fp32
     cells' tolerance and against the fp32 cell itself (agreement to fp32 rounding: the products are exact, the sums run in another order); dense input,
     token row + row bias, start token, both; repeated launches bit-identical; a shape it does not take (B % 128 != 0) falls back to the fp32 cells."""
@@ -577,11 +577,12 @@ def test_gemm_bf16x6_kernels_random_shapes():
 
 @pytest.mark.parametrize("n,B,T", [(4, 256, 14), (2, 256, 9), (1, 128, 6), (3, 64, 5)])
 def test_forward_scan_bf16x6(ops, n, B, T):
-    """the opt-in forward scan with exact split products on the bf16 MFMA (FnGruFwd.variant bit 14: weights and exchanged state as bf16 triples,
+    """the opt-in forward scan with exact split products on the bf16 MFMA (FnGruFwd.variant | FN_GRU_BF16X6: weights and exchanged state as bf16 triples,
     fn_frag3_pack) against the default weight-stationary kernels at H = 512: states and saved gates agree to fp32 rounding (the products are
     exact, the sums run in another order); 128-row groups (4 x 256 rows), 64-row groups, table / dense inputs, reverse scans, row biases,
     shifted tokens, initial states, two chunks with the state handed over as a triple image (bit-identical to one launch); repeated launches on warm
     slabs are bit-identical; a scan without saved gates makes the call fall back to the default kernels"""
+    from music_fader_nets_amd import _lib
     H, V = 512, 57
     rng = np.random.RandomState(n * 100 + B + T)
     torch.manual_seed(n + B)
@@ -617,7 +618,7 @@ def test_forward_scan_bf16x6(ops, n, B, T):
         ref = run(False)
         got = run(True)
         again = run(True)
-        single = run(True, 0x8000)                         # the single-group bf16 x 6 kernel (no ping-pong)
+        single = run(True, _lib.GRU_X6_SINGLE_GROUP)       # the single-group bf16 x 6 kernel (no ping-pong)
         assert not ops.gru_sync_error()
         differs = False
         for a, b, c, e in zip(ref, got, again, single):
@@ -682,11 +683,12 @@ def test_forward_scan_bf16x6(ops, n, B, T):
 
 @pytest.mark.parametrize("n,B,Ts", [(4, 256, (7, 7, 7, 7)), (4, 256, (2, 9, 5, 3)), (2, 256, (6, 4)), (3, 128, (5, 8, 3)), (2, 512, (4, 4))])
 def test_backward_scan_bf16x6(ops, n, B, Ts):
-    """the backward scan with exact split products on the bf16 MFMA (FnGruBwd.variant bit 14: gate gradients exchanged as bf16 triples, W_hh^T as a
+    """the backward scan with exact split products on the bf16 MFMA (FnGruBwd.variant | FN_GRU_BF16X6: gate gradients exchanged as bf16 triples, W_hh^T as a
     triple image, gru_bwd_x6_kernel) against the default register-stationary fp32 kernel on the SAME saved activations at H = 512: gate gradients,
     dL/dh0 and the per-sequence row sums agree to fp32 rounding (exact products, another summation order); 64-row groups (4 x 256 rows: 16
     groups) and 32-row groups (2 x 256, 3 x 128, 2 x 512 rows), scans of different lengths in one launch, with / without dh_last, dh_ext, h0, dh0;
     repeated launches on warm slabs are bit-identical; the sync-error word stays clear"""
+    from music_fader_nets_amd import _lib
     H, V = 512, 57
     torch.manual_seed(n * 1000 + B)
     fwd, bwd = [], []
@@ -714,7 +716,7 @@ def test_backward_scan_bf16x6(ops, n, B, Ts):
 
     def run(x6):
         ops.dw_x6 = x6
-        ops.variant = 0x8000 if x6 else 0                  # bit 15: the 32-row-group form too (not chosen on its own: no faster than the fp32 kernel)
+        ops.variant = _lib.GRU_X6_BWD_32ROWS if x6 else 0  # the 32-row-group form too (not chosen on its own: no faster than the fp32 kernel)
         for b in bwd:
             for k in keys:
                 if b[k] is not None:
@@ -748,9 +750,10 @@ def test_backward_scan_bf16x6(ops, n, B, Ts):
 @pytest.mark.parametrize("n,B,T", [(2, 256, 12), (4, 256, 9)])
 def test_scan_results_do_not_depend_on_the_xcd_placement(ops, n, B, T, x6):
     """the weight-stationary scans deal their workgroups so that a row group (its exchange slab, its arrival counters) sits on ONE XCD - speed
-    only: with FnGruFwd / FnGruBwd.variant bit 12 the slices of every row group are spread over all 8 XCDs and every hand-over crosses
+    only: with FnGruFwd / FnGruBwd.variant | FN_GRU_SPREAD_XCDS the slices of every row group are spread over all 8 XCDs and every hand-over crosses
     XCDs; forward states, saved gates, gate gradients and row sums must come out bit-identical (ping-pong forward on both arithmetics,
     register-stationary backward with 32- and 64-row groups, the bf16 x 6 backward), the sync-error word clear"""
+    from music_fader_nets_amd import _lib
     H = 512
     torch.manual_seed(77 + n)
     fwd, bwd = [], []
@@ -784,7 +787,7 @@ def test_scan_results_do_not_depend_on_the_xcd_placement(ops, n, B, T, x6):
         torch.cuda.synchronize()
         return out + [b[k].clone() for b in bwd for k in bk]
     try:
-        ref, spread = run(0), run(0x1000)
+        ref, spread = run(0), run(_lib.GRU_SPREAD_XCDS)
         assert not ops.gru_sync_error()
         for i, (a, b) in enumerate(zip(ref, spread)):
             assert not torch.isnan(b).any(), i
@@ -1937,13 +1940,14 @@ def _pp_forward_scans(ops, n, B, H, Ts, seed, kinds):
                                           (3, 128, (4,), ("table", "dense", "table_rev")), (8, 128, (6, 3), ("table", "table_shift"))])
 def test_ping_pong_scans_are_bit_identical_to_the_single_group_loops(ops, n, B, Ts, kinds):
     """round 4: the forward scans whose workgroups alternate between two halves of their row group (gru_fwd_pp_kernel: H = 512, 128- and 64-row
-    groups) against the round-3 loops (variant bit 0x800), three launches in a row on the same buffers: bit-identical; the backward scans of
+    groups) against the round-3 loops (variant FN_GRU_NO_PINGPONG), three launches in a row on the same buffers: bit-identical; the backward scans of
     the same shapes: the 32-slice loop bit-identical to the round-3 form, the register-stationary default within rounding and bit-stable from
     launch to launch.  (A ping-pong form of the 32-slice backward existed until round 4: never the default, and it differed from the loop in
     about 1 % of its launches at the encoder shape - removed, scratch/gru_bwd_pp_kernel_removed.hip.txt.)"""
+    from music_fader_nets_amd import _lib
     H = 512
     scans = _pp_forward_scans(ops, n, B, H, Ts, 7 * n + B, kinds)
-    ops.gru_seq_fwd(scans, variant=0x800)
+    ops.gru_seq_fwd(scans, variant=_lib.GRU_NO_PINGPONG)
     ref = [(d["h_all"].clone(), d["gates"].clone()) for d in scans]
     for rep in range(3):
         for d in scans:
@@ -1968,14 +1972,14 @@ def test_ping_pong_scans_are_bit_identical_to_the_single_group_loops(ops, n, B, 
                        dgx_rowsum=torch.zeros(B, 3 * H, device=DEV) if i & 1 else None, dghn_rowsum=torch.zeros(B, H, device=DEV) if i != 2 else None,
                        scratch=torch.zeros(B, H, device=DEV)))
     outs = ("dgx_all", "dghn_all", "dh0", "dgx_rowsum", "dghn_rowsum")
-    ops.gru_seq_bwd(bw, variant=0x800)
+    ops.gru_seq_bwd(bw, variant=_lib.GRU_NO_PINGPONG)
     refb = [{k: b[k].clone() for k in outs if b[k] is not None} for b in bw]
     for rep in range(3):
         for b in bw:
             for k in outs:
                 if b[k] is not None:
                     b[k].zero_() if "rowsum" in k else b[k].fill_(float("nan"))
-        ops.gru_seq_bwd(bw, variant=0x2000)            # bit 13: not the register-stationary kernel - the 32-slice loop of the automatic dispatch
+        ops.gru_seq_bwd(bw, variant=_lib.GRU_NO_RS_BWD)  # not the register-stationary kernel - the 32-slice loop of the automatic dispatch
         assert not ops.gru_sync_error()
         for i, (r, b) in enumerate(zip(refb, bw)):
             for k, v in r.items():
