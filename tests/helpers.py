@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests: golden loading, model construction, comparisons."""
 import os
+import time
 
 import numpy as np
 import torch
@@ -172,6 +173,140 @@ def tokens_match_upto_near_tie(tok, ref_tok, ref_gap, thr=1e-4):
         assert np.array_equal(row[:upto], rrow[:upto]), (row[:upto].tolist(), rrow[:upto].tolist())
         n += upto
     return n
+
+
+REPLAY_ROWS = 256          # rows replayed per decode above this batch size: a fixed-seed sample (decode rows are independent)
+REPLAY_BLOCK = 32          # pipeline blocks (32 / 64 rows) and cell row tiles (multiples of 64 / 128 rows) all start at multiples of 32
+REPLAY_CAP = 0.02          # at most this share of the checked positions may sit at an fp64 top-2 gap below delta
+_DECODER_KEYS = ("linear_init_global.", "grucell_g.", "grucell_g_2.", "linear_out_g.")
+
+
+def replay_rows(Bi, n=REPLAY_ROWS, seed=0):
+    """every row when Bi <= n; else n rows drawn with a fixed seed that include the first and last row of every 32-row block (so of every
+    32- / 64-row pipeline block and every cell row tile) and the last row of the batch"""
+    if Bi <= n:
+        return np.arange(Bi)
+    must = set()
+    for r0 in range(0, Bi, REPLAY_BLOCK):
+        must.update((r0, min(r0 + REPLAY_BLOCK, Bi) - 1))
+    must.add(Bi - 1)
+    assert len(must) <= n
+    rest = np.setdiff1d(np.arange(Bi), np.fromiter(must, dtype=np.int64))
+    extra = np.random.RandomState(seed).choice(rest, n - len(must), replace=False)
+    return np.sort(np.concatenate([np.fromiter(must, dtype=np.int64), extra]))
+
+
+def replay_decode_check(sd, z, tokens, logp=None, rows=None):
+    """Every step of a greedy decode against an fp64 replay of its own tokens.
+
+    Step i of the greedy decoder consumes token i-1, which is what the teacher-forced oracle decoder does with teacher=tokens: replaying
+    the tokens a kernel chose gives the exact log-probs it should have computed at every position, whatever it chose earlier.  The
+    tokens are replayed twice: in fp64 (the reference) and in fp32 (the plain CPU restatement), whose distance e_ref = max |lp32 - lp64|
+    is what fp32 rounding alone costs on these inputs.  tol_lp = min(1e-4, 16 e_ref): 1e-4 is the absolute tolerance the suite already
+    applies to these paths against the oracle, 16 is headroom for the kernels' other summation orders (split-K partials through LDS,
+    bf16 x 6 products whose dropped terms are fp32-class).  At every replayed position:
+      (a) logp given: |lp_gpu - lp64| <= tol_lp over all 342 entries;
+      (b) logp given: the token is the first-index argmax of the kernel's own log-prob row;
+      (c) lp64[tok] >= max(lp64) - delta, delta = 2 tol_lp (log-prob differences are logit differences, each side off by at most tol_lp):
+          wherever the fp64 top-2 gap exceeds delta the token IS the fp64 argmax.
+    And a condition on the inputs: at most 2 % of the positions have an fp64 top-2 gap below delta (only there is a token unconstrained).
+    sd: the model's state dict; z (Bi, 2Z+24); tokens (Bi, steps); logp (Bi, steps, 342) or None; rows: indices or None (replay_rows).
+    Returns the figures as a dict."""
+    t0 = time.time()
+    tokens = torch.as_tensor(tokens).detach().cpu().long()
+    Bi, steps = tokens.shape
+    rows = torch.as_tensor(replay_rows(Bi) if rows is None else rows, dtype=torch.long)
+    tk = tokens[rows]
+    E = orc.E
+    assert int(tk.min()) >= 0 and int(tk.max()) < E, ("token out of range", int(tk.min()), int(tk.max()))
+    zr = torch.as_tensor(z).detach().cpu()[rows]
+    dec = {k: v.detach().cpu() for k, v in sd.items() if k.startswith(_DECODER_KEYS)}
+    threads = torch.get_num_threads()
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))         # what a GPU machine allows a test
+    try:
+        with torch.no_grad():
+            lp64 = orc.global_decoder({k: v.double() for k, v in dec.items()}, zr.double(), steps, teacher=tk)
+            lp32 = orc.global_decoder({k: v.float() for k, v in dec.items()}, zr.float(), steps, teacher=tk)
+    finally:
+        torch.set_num_threads(threads)
+    assert lp64.dtype == torch.float64 and lp32.dtype == torch.float32
+    e_ref = float((lp32.double() - lp64).abs().max())
+    tol = min(1e-4, 16.0 * e_ref)
+    delta = 2.0 * tol
+    top2 = lp64.topk(2, dim=-1).values
+    gap = top2[..., 0] - top2[..., 1]
+    share = float((gap < delta).double().mean())
+    st = dict(Bi=Bi, steps=steps, rows=len(rows), positions=tk.numel(), e_ref=e_ref, tol_lp=tol, delta=delta, share_below_delta=share,
+              max_dlp=float("nan"), ratio=float("nan"))
+
+    def where(mask):
+        r, s = (int(x) for x in torch.nonzero(mask)[0])
+        return "row %d step %d" % (int(rows[r]), s)
+
+    if logp is not None:
+        lg = torch.as_tensor(logp).detach().cpu()[rows].double()
+        assert tuple(lg.shape) == (len(rows), steps, E), tuple(lg.shape)
+        err = (lg - lp64).abs().amax(-1)                                   # NaN stays NaN: fails the bound below
+        st["max_dlp"] = float(err.max())
+        st["ratio"] = st["max_dlp"] / max(e_ref, 1e-30)
+        bad = ~(err <= tol)
+        assert not bool(bad.any()), "(a) |lp_gpu - lp64| = %.3e > tol_lp %.3e (e_ref %.3e) at %s, %d positions" % (
+            float(err[bad].max()), tol, e_ref, where(bad), int(bad.sum()))
+        own = torch.from_numpy(np.argmax(lg.numpy(), axis=-1))             # numpy: first index of the maximum
+        bad = own != tk
+        assert not bool(bad.any()), "(b) token is not the first-index argmax of the kernel's own log-probs at %s, %d positions" % (
+            where(bad), int(bad.sum()))
+    short = top2[..., 0] - lp64.gather(-1, tk.unsqueeze(-1)).squeeze(-1)
+    bad = short > delta
+    assert not bool(bad.any()), "(c) lp64[tok] is %.3e below the fp64 best (delta %.3e) at %s, %d positions" % (
+        float(short[bad].max()), delta, where(bad), int(bad.sum()))
+    assert share <= REPLAY_CAP, "cap: %.2f %% of the positions have an fp64 top-2 gap below delta %.3e" % (100 * share, delta)
+    st["seconds"] = time.time() - t0
+    return st
+
+
+# the decode cases test_gpu_parity.test_decode_paths_every_step_vs_fp64_replay forces, (path, weights, Bi, steps):
+#   one_launch  fn_decode_greedy, one block of <= 32 rows        pipeline32 / pipeline64  its block pipeline, 32- / 64-row blocks
+#   scan_steps  per-token scan-step kernels + projection GEMM     cells_f32 / cells_x6     per-token fn_gru_cell_f32 cells, fp32 / bf16 x 6
+# the graph paths (scan_steps, cells_*) also replay their cached graph on a second latent batch (seed Bi + 1)
+REPLAY_CASES = [
+    ("one_launch", "h64", 1, 300), ("one_launch", "h64", 17, 300), ("one_launch", "h64", 32, 300),
+    ("one_launch", "h512", 1, 300), ("one_launch", "h512", 17, 300), ("one_launch", "h512", 32, 300),
+    ("pipeline32", "h512", 33, 300), ("pipeline32", "h64", 200, 250), ("pipeline32", "h512", 352, 200),
+    ("pipeline64", "h512", 353, 150), ("pipeline64", "h512", 704, 300), ("pipeline64", "h64", 1500, 120), ("pipeline64", "h512", 2048, 100),
+    ("scan_steps", "h64", 17, 300), ("scan_steps", "h512", 300, 150),
+    ("cells_f32", "h512", 705, 200), ("cells_f32", "h512", 1000, 150), ("cells_f32", "h512", 1280, 120),
+    ("cells_x6", "h512", 2048, 300),
+    ("pipeline32", "trained64", 40, 300),
+]
+REPLAY_GRAPH_PATHS = ("scan_steps", "cells_f32", "cells_x6")
+REPLAY_OUT_SCALE = 8.0     # linear_out_g.weight x 8: wider logit spreads, fewer near-ties (seeded H=512: 1.8 % of the gaps below 2e-4 -> 0.4 %)
+
+
+def replay_inputs(weights):
+    """(H, Z, state dict) of a replay case, on the CPU: 'h64' / 'h512' = the seeded model (seed 7 / 1234) with linear_out_g.weight x 8,
+    'trained64' = the trained weights tests/golden/epoch.npz ends with (wend/), unscaled"""
+    if weights == "trained64":
+        sd = sd_from(load_golden("epoch"), "wend/")
+    else:
+        H = int(weights[1:])
+        m = make_model(H, 32 if H == 64 else 128, seed=7 if H == 64 else 1234)
+        sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+        sd["linear_out_g.weight"] = sd["linear_out_g.weight"] * REPLAY_OUT_SCALE
+    H, Zc = sd["linear_init_global.weight"].shape
+    return int(H), (int(Zc) - 24) // 2, sd
+
+
+def replay_z(Bi, Z, seed):
+    """the latent rows of a replay case: N(0, 1), (Bi, 2Z + 24), from their own generator"""
+    return torch.randn(Bi, 2 * Z + 24, generator=torch.Generator().manual_seed(seed))
+
+
+def replay_line(path, H, st):
+    """one line of profiles/decode_replay_errors.txt"""
+    return ("%-26s Bi %4d H %3d steps %3d rows %3d  e_ref %.3e  max|dlogp| %.3e  ratio %6.3f  below_delta %.3f %%  delta %.3e  replay %.1f s"
+            % (path, st["Bi"], H, st["steps"], st["rows"], st["e_ref"], st["max_dlp"], st["ratio"], 100 * st["share_below_delta"], st["delta"],
+               st["seconds"]))
 
 
 def eval_golden(tag):

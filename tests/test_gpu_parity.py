@@ -3,7 +3,8 @@
 Tolerances (fp32): kernel outputs vs an fp64/CPU restatement of the same op: 2e-5 relative to the tensor's max;
 end-to-end gradients vs the reference's autograd: 5e-4 relative to each tensor's max; greedy-decode token ids
 bit-exact wherever the reference's own top-2 log-prob gap exceeds 1e-4 (a flipped near-tie changes every later token,
-so rows are compared up to the first sub-threshold gap).
+so rows are compared up to the first sub-threshold gap); past those near-ties, every step of every decode path against an fp64 replay
+of its own tokens (helpers.replay_decode_check).
 """
 import math
 import os
@@ -13,7 +14,8 @@ import pytest
 import torch
 
 from fake_ops import FakeOps
-from helpers import NOISE_PARAMS, batch_of, grad_tolerances, load_golden, make_model, oracle_grads_f64, relerr, sd_from
+from helpers import (NOISE_PARAMS, REPLAY_CASES, REPLAY_GRAPH_PATHS, batch_of, grad_tolerances, load_golden, make_model, oracle_grads_f64, relerr,
+                     replay_decode_check, replay_inputs, replay_line, replay_z, sd_from)
 from mfn_import import load_package
 from oracle import gmvae_oracle as orc
 
@@ -1419,6 +1421,8 @@ def test_single_launch_decode_block_pipeline(H, Bi, steps):
     close(lp1[keep], lp0[keep], 2e-5)
     _, tk3 = pkg.greedy_decode(m, z, steps, want_logp=False)          # the ARG role without the log-probability output
     assert torch.equal(tk3, tk1)
+    st = replay_decode_check({k: v.detach().cpu() for k, v in m.state_dict().items()}, z.cpu(), tk1, lp1)      # every position, past the near-ties too
+    print("\n" + replay_line("block_pipeline", H, st))
 
 
 @pytest.mark.parametrize("H,Bi,steps", [(64, 1100, 14), (512, 1024, 10)])
@@ -1545,6 +1549,61 @@ def test_large_decode_paths_vs_oracle(path, Bi, steps):
     got_tk, got_lp = tk.cpu().long(), lp.cpu()
     assert torch.equal(got_tk[keep], ref_tk[keep]), int((got_tk[keep] != ref_tk[keep]).sum())
     np.testing.assert_allclose(got_lp[keep].numpy(), ref_lp[keep].numpy(), rtol=0, atol=1e-4)
+    st = replay_decode_check(sd, z, tk, lp)                                                  # and every position, past the near-ties too
+    print("\n" + replay_line("large_decode_%s[%s]" % (path, _arith_tag(eng)), 512, st))
+
+
+def _arith_tag(eng):
+    return "bf16x6" if eng.ops.dw_x6 else "f32"
+
+
+@pytest.mark.parametrize("path,weights,Bi,steps", REPLAY_CASES, ids=["%s-%s-%d" % (p, w, b) for p, w, b, _ in REPLAY_CASES])
+def test_decode_paths_every_step_vs_fp64_replay(path, weights, Bi, steps):
+    """Every decode path, forced by the engine switches, checked at EVERY position of its replayed rows against an fp64 replay of the
+    tokens it chose (helpers.replay_decode_check): log-probs within tol_lp = min(1e-4, 16 x the fp32 restatement's own error), each token
+    its own log-prob row's first argmax and within delta = 2 tol_lp of the fp64 best; the tokens-only form the same way.  The one-launch
+    pipeline reuses its exchange slabs and per-block counters for every step, so 100 - 300 steps, ragged last blocks and up to 32 blocks;
+    the graph paths replay their cached graph on a second latent batch, which must pass as well (nothing of the first call baked in).
+    Weights: seeded with the output layer x 8 (fewer near-ties), or the trained H = 64 weights of epoch.npz."""
+    pkg = load_package()
+    H, Z, sd = replay_inputs(weights)
+    m = make_model(H, Z, sd, device=DEV, arith="bf16x6" if path == "cells_x6" else None)
+    m.eval()
+    eng = m.engine()
+    one_launch = path in ("one_launch", "pipeline32", "pipeline64")
+    if one_launch:
+        eng.single_launch_decode, eng.single_launch_skip = True, (0, -1)
+        if Bi > eng.single_launch_rows:
+            eng.single_launch_rows = 2048
+        assert (Bi <= 32) == (path == "one_launch") and (Bi >= 353) == (path == "pipeline64")
+    elif path == "scan_steps":
+        eng.single_launch_decode, eng.cell_decode_rows = False, 1 << 30
+    else:
+        eng.single_launch_decode = False
+        assert Bi >= eng.cell_decode_rows
+        x6 = eng.ops.dw_x6 and eng.ops.cell_x6 and Bi >= eng.ops.cell_x6_rows
+        assert x6 == (path == "cells_x6")
+    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
+    z = replay_z(Bi, Z, Bi)
+    lp, tk = pkg.greedy_decode(m, z.to(DEV), steps, want_logp=True)
+    _, tk_only = pkg.greedy_decode(m, z.to(DEV), steps, want_logp=False)
+    assert not eng.ops.gru_sync_error()
+    graphs = eng.__dict__.get("_decode_graphs", {})
+    assert (len(graphs) == 0) == one_launch                  # the one-launch paths did not fall back to the per-token kernels
+    tag = "%s[%s]/%s" % (path, _arith_tag(eng), weights)
+    st = replay_decode_check(sd, z, tk, lp)
+    print("\n" + replay_line(tag, H, st), end="")
+    if not torch.equal(tk_only, tk):
+        st = replay_decode_check(sd, z, tk_only)
+        print("\n" + replay_line(tag + " tokens", H, st), end="")
+    if path in REPLAY_GRAPH_PATHS:
+        n = len(graphs)
+        z2 = replay_z(Bi, Z, Bi + 1)
+        lp2, tk2 = pkg.greedy_decode(m, z2.to(DEV), steps, want_logp=True)
+        assert len(eng._decode_graphs) == n and not eng.ops.gru_sync_error()
+        st = replay_decode_check(sd, z2, tk2, lp2)
+        print("\n" + replay_line(tag + " graph z2", H, st), end="")
+    print()
 
 
 def test_configs4_sized_fader_sweep_properties():
@@ -1583,6 +1642,13 @@ def test_configs4_sized_fader_sweep_properties():
     keep = torch.arange(24).view(1, -1) < first.view(-1, 1)
     assert float(keep.float().mean()) > 0.9
     assert torch.equal(tok[seqs].reshape(64, 300)[:, :24].cpu().long()[keep], ref_tk[keep])
+    # every step of 256 of the 2048 rows against an fp64 replay of their tokens, the latent rows built the same way for all sequences
+    zr = (dis_r.mean + dis_r.stddev * eps[0]).unsqueeze(1).repeat(1, 8, 1)
+    zn = (dis_n.mean + dis_n.stddev * eps[1]).unsqueeze(1).repeat(1, 8, 1)
+    zr[:, :, 0] = torch.tensor(values, device=DEV)
+    z_all = torch.cat([zr, zn, c.unsqueeze(1).repeat(1, 8, 1)], dim=2).view(2048, -1)
+    st = replay_decode_check(sd, z_all.cpu(), tok.reshape(2048, 300))
+    print("\n" + replay_line("configs4_sweep[%s]" % _arith_tag(m.engine()), 512, st))
 
 
 def test_full_size_properties():
