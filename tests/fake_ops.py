@@ -163,7 +163,7 @@ class FakeOps:
     def gru_dwhh(self, dgx, dghn, hprev, dW, beta=0.0, splitk=1, lean=False):
         H = hprev.shape[1]
         g = torch.cat([dgx[:, : 2 * H], dghn], dim=1)
-        dW.copy_(beta * dW + g.t() @ hprev)
+        dW.copy_(beta * dW + g.t() @ hprev if beta != 0.0 else g.t() @ hprev)          # dW may be uninitialised memory when beta == 0 (0 x NaN is NaN)
 
     def embed_grad(self, dgx_all, idx, idx_shift, start_token, reverse, V, out):
         T, B, N3 = dgx_all.shape

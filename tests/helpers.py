@@ -779,3 +779,512 @@ def check_epoch_v2_run(pkg, family, g, tmp_path, device="cpu", ops=None, rtol=5e
     stamped = [f for f in os.listdir(str(tmp_path)) if f.startswith("golden_%s_" % family) and f.endswith(".pt")]
     assert len(stamped) == int(g[P + "stamped"]) == 1
     return m
+
+
+# ---- GRU scans: every step of every output against an fp64 scan + autograd (tests/test_scan_reference.py, test_gpu_parity.py) ---------------
+# A *logical scan* is a dict of CPU fp32 tensors that states one whole scan of fn_gru_seq_fwd / fn_gru_seq_bwd (include/fadernets.h), unchunked:
+#   B, T, H, w_hh [3H][H], b_hh [3H], optional b_ih [3H], h0 [B][H], gx_dense [T][B][3H], gx_table [V][3H] + idx [B][>=T] int32 (+ reverse,
+#   idx_shift, start_token), gx_rowbias [B][3H]; for the backward optional dh_last [B][H], dh_ext [T][B][H] and the flags want_dh0, want_rowsums.
+# run_scans() turns a list of them into the descriptors of a backend (FakeOps on a row subset, HipOps on the device), in one launch or in time
+# chunks with the hand-overs the decoder pipeline uses, and returns per scan the outputs named in SCAN_QUANTITIES on the CPU.
+# factor of check_scan_vs_f64 = the smallest power of two >= 2 x the worst err_kernel / e_ref measured on an MI355X (profiles/scan_fp64_errors.txt),
+# at most SCAN_F_CAP.  Measured worst: 4.6 forward, 7.7 dh0, 1.7 row sums -> 16; dgx_all / dghn_all 13.2 would ask for 32: capped, the headroom
+# there is 1.2 x
+SCAN_F = 16
+SCAN_F_CAP = 16            # the margin replay_decode_check already uses
+SCAN_EPS = 2.0 ** -23
+SCAN_MIN_REF = 2.0 ** -100           # input condition: every per-step block maximum of the fp64 reference is at least this
+SCAN_BLOCK = 32            # 32 consecutive checked rows form one block of the per-step metric: every row of a scan of <= 64 rows, else (two rows per
+                           # 16-row tile) the checked rows of 256 rows of the batch
+SCAN_FWD_QUANTITIES = ("h_all", "gate_r", "gate_z", "gate_n", "gate_hn")
+SCAN_BWD_QUANTITIES = ("dgx_all", "dghn_all", "dh0", "dgx_rowsum", "dghn_rowsum")
+SCAN_QUANTITIES = SCAN_FWD_QUANTITIES + SCAN_BWD_QUANTITIES
+
+
+def scan_rows(B, seed=0):
+    """the rows of a B-row scan that get referenced: all of them when B <= 64, else of every 16-row tile its first row and one more row
+    drawn with a fixed seed - no 16-row patch of any step or column is without two checked rows"""
+    if B <= 64:
+        return np.arange(B)
+    rng = np.random.RandomState(seed)
+    rows = []
+    for r0 in range(0, B, 16):
+        n = min(16, B - r0)
+        rows.append(r0)
+        if n > 1:
+            rows.append(r0 + 1 + int(rng.randint(n - 1)))
+    return np.asarray(rows, dtype=np.int64)
+
+
+def _scan_tok(s, p, rows):
+    tau = (s["T"] - 1 - p if s.get("reverse", 0) else p) + s.get("idx_shift", 0)
+    if tau < 0:
+        return torch.full((len(rows),), int(s.get("start_token", 0)), dtype=torch.long)
+    return s["idx"][rows, tau].long()
+
+
+def scan_reference_f64(scans, rows=None, device="cpu"):
+    """float64 restatement of fn_gru_seq_fwd on rows[i] of logical scan i (rows of a scan do not interact), and its backward by torch
+    autograd of   sum_p <dh_ext[p], h_p> + <dh_last, h_{T-1}>   through that forward: dgx_all = d/d(input-side gate pre-activations) (the leaf
+    gx_dense, or a zero probe added to them), dghn_all = d/d(zero probe added to W_hn h + b_hn), dh0 = d/d(h0), the row sums = their sums over
+    time.  Chunked launches are referenced as the one scan they are equivalent to.  device: where plain torch evaluates it (float64 on the GPU is as
+    independent of the HIP kernels as on the CPU, and much faster at the 256-step shapes).  Returns per scan {quantity: float64 CPU tensor}."""
+    out = []
+    for i, s in enumerate(scans):
+        rw = torch.as_tensor(np.arange(s["B"]) if rows is None else rows[i], dtype=torch.long)
+        R, T, H = len(rw), s["T"], s["H"]
+        f = lambda k: None if s.get(k) is None else s[k].to(device).double()
+        W, b_hh, b_ih, tab = f("w_hh"), f("b_hh"), f("b_ih"), f("gx_table")
+        rb = None if s.get("gx_rowbias") is None else s["gx_rowbias"][rw].to(device).double()
+        backward = s.get("dh_last") is not None or s.get("dh_ext") is not None
+        with torch.enable_grad():
+            pgx = (s["gx_dense"][:, rw].to(device).double() if s.get("gx_dense") is not None else torch.zeros(T, R, 3 * H, dtype=torch.float64, device=device)).requires_grad_(backward)
+            phn = torch.zeros(T, R, H, dtype=torch.float64, device=device, requires_grad=backward)
+            h0 = (s["h0"][rw].to(device).double() if s.get("h0") is not None else torch.zeros(R, H, dtype=torch.float64, device=device)).requires_grad_(backward)
+            h, hs, gs = h0, [], []
+            for p in range(T):
+                gx = pgx[p]
+                if b_ih is not None:
+                    gx = gx + b_ih
+                if tab is not None:
+                    gx = gx + tab[_scan_tok(s, p, rw).to(device)]
+                if rb is not None:
+                    gx = gx + rb
+                gh = h @ W.t() + b_hh
+                hn = gh[:, 2 * H:] + phn[p]
+                r = torch.sigmoid(gx[:, :H] + gh[:, :H])
+                z = torch.sigmoid(gx[:, H:2 * H] + gh[:, H:2 * H])
+                n = torch.tanh(gx[:, 2 * H:] + r * hn)
+                h = (1 - z) * n + z * h
+                hs.append(h)
+                gs.append((r.detach(), z.detach(), n.detach(), hn.detach()))
+            o = {"h_all": torch.stack([x.detach() for x in hs])}
+            for j, k in enumerate(SCAN_FWD_QUANTITIES[1:]):
+                o[k] = torch.stack([g_[j] for g_ in gs])
+            if backward:
+                loss = torch.zeros((), dtype=torch.float64, device=device)
+                if s.get("dh_last") is not None:
+                    loss = loss + (s["dh_last"][rw].to(device).double() * hs[-1]).sum()
+                if s.get("dh_ext") is not None:
+                    loss = loss + (s["dh_ext"][:, rw].to(device).double() * torch.stack(hs)).sum()
+                o["dgx_all"], o["dghn_all"], dh0 = torch.autograd.grad(loss, [pgx, phn, h0])
+                if s.get("want_dh0"):
+                    o["dh0"] = dh0
+                if s.get("want_rowsums", True):
+                    o["dgx_rowsum"], o["dghn_rowsum"] = o["dgx_all"].sum(0), o["dghn_all"].sum(0)
+        out.append({k: v.detach().cpu() for k, v in o.items()})
+    return out
+
+
+def _unblock_gates(g, B, H, rows=None):
+    """the HIP kernels' private gate layout (gate_off in csrc/gru.hip) -> [T][B][4][H] (rows given: [T][len(rows)][4][H], those rows only)"""
+    T = g.shape[0]
+    nrt = (B + 15) // 16
+    b = (torch.arange(B) if rows is None else torch.as_tensor(rows, dtype=torch.long)).view(-1, 1, 1)
+    q = torch.arange(4).view(1, 4, 1)
+    u = torch.arange(H).view(1, 1, H)
+    off = ((((u // 16) * nrt + (b // 16)) * 4 + q) * 4 + (b % 4)) * 64 + ((b % 16) // 4) * 16 + (u % 16)
+    return g[:, off.reshape(-1).to(g.device)].view(T, b.shape[0], 4, H)
+
+
+def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=None, bwd_kw=None, carry_fault=None):
+    """The logical scans through a backend: ops = FakeOps (device "cpu", restricted to rows[i] of scan i) or HipOps (all rows on `device`; the
+    outputs are cut to rows[i] afterwards).  chunk = None: one forward and one backward launch.  chunk = CH: time chunks of CH steps, the forward
+    state handed from launch to launch as operand images (h_last_frag -> h0_frag), the backward state gradient through dh0 -> dh_last with time
+    running backwards over the chunks - what the decoder pipeline does (engine.py, _bwd_chunk).  x6: the arithmetic asked for, explicitly
+    (HipOps: dw_x6 and x6= of both calls; a launch that cannot take it raises).  carry_fault(ci, tensor): test hook, edits the CPU carry that
+    leaves backward chunk ci (FakeOps only).  The backward consumes the backend's OWN saved gates.  Returns per scan {quantity: CPU tensor}."""
+    fake = device == "cpu"
+    fwd_kw, bwd_kw = dict(fwd_kw or {}), dict(bwd_kw or {})
+    if not fake:
+        fwd_kw["x6"], bwd_kw["x6"] = x6, x6
+    rws = [torch.as_tensor(np.arange(s["B"]) if rows is None else rows[i], dtype=torch.long) for i, s in enumerate(scans)]
+    dev = lambda t: t.to(device).contiguous()
+    zeros = lambda *shape: torch.zeros(*shape, device=device)
+    fw, bw, sub = [], [], []
+    for s, rw in zip(scans, rws):
+        take = (lambda t, dim=0: t.index_select(dim, rw)) if fake else (lambda t, dim=0: t)     # FakeOps runs the referenced rows only
+        B, T, H = (len(rw) if fake else s["B"]), s["T"], s["H"]
+        sub.append((B, T, H))
+        d = dict(B=B, T=T, H=H, reverse=int(s.get("reverse", 0)), b_hh=dev(s["b_hh"]), idx_shift=int(s.get("idx_shift", 0)), start_token=int(s.get("start_token", 0)),
+                 h_all=zeros(T, B, H), gates=zeros(T, ops.gates_floats(B, H)))
+        w = dev(s["w_hh"])
+        d["w_hh_frag"] = zeros(ops.frag_floats(3 * H, H))
+        b = dict(B=B, T=T, H=H, w_hh_t_frag=zeros(ops.frag_floats(H, 3 * H)))
+        if fake:
+            ops.frag_pack(w, d["w_hh_frag"]), ops.frag_pack(w.t().contiguous(), b["w_hh_t_frag"])
+        else:
+            jobs = [("frag", w, d["w_hh_frag"]), ("frag_t", w, b["w_hh_t_frag"])]
+            if x6:
+                d["w_hh_frag3"], b["w_hh_t_frag3"] = zeros(ops.frag_floats(3 * H, H) * 3 // 2), zeros(ops.frag_floats(H, 3 * H) * 3 // 2)
+                jobs += [("frag3", w, d["w_hh_frag3"]), ("frag3_t", w, b["w_hh_t_frag3"])]
+            ops.weight_images(jobs)
+        for k in ("b_ih", "gx_table"):
+            if s.get(k) is not None:
+                d[k] = dev(s[k])
+        for k in ("h0", "gx_rowbias", "idx"):
+            if s.get(k) is not None:
+                d[k] = dev(take(s[k]))
+        if s.get("gx_dense") is not None:
+            d["gx_dense"] = dev(take(s["gx_dense"], 1))
+        fw.append(d)
+        if s.get("dh_last") is not None or s.get("dh_ext") is not None:
+            b.update(h0=d.get("h0"), h_all=d["h_all"], gates=d["gates"], dh_last=None if s.get("dh_last") is None else dev(take(s["dh_last"])),
+                     dh_ext=None if s.get("dh_ext") is None else dev(take(s["dh_ext"], 1)), dgx_all=zeros(T, B, 3 * H), dghn_all=zeros(T, B, H),
+                     dh0=zeros(B, H) if s.get("want_dh0") else None, scratch=zeros(B, H))
+            if s.get("want_rowsums", True):
+                b["dgx_rowsum"], b["dghn_rowsum"] = zeros(B, 3 * H), zeros(B, H)
+            bw.append(b)
+        else:
+            bw.append(None)
+    if chunk is None:
+        ops.gru_seq_fwd(fw, **fwd_kw)
+    else:
+        T = scans[0]["T"]
+        assert all(s["T"] == T and not s.get("reverse", 0) for s in scans), "chunked chains: forward scans of one length"
+        hand = [[zeros(ops.frag_floats(B, H) * (3 if x6 and not fake else 2) // 2) for _ in range(2)] for B, _, H in sub]
+        for ci, t0 in enumerate(range(0, T, chunk)):
+            t1 = min(T, t0 + chunk)
+            part = []
+            for d, hb in zip(fw, hand):
+                c = dict(d, T=t1 - t0, h_all=d["h_all"][t0:t1], gates=d["gates"][t0:t1], idx_shift=d["idx_shift"] + t0)
+                if d.get("gx_dense") is not None:
+                    c["gx_dense"] = d["gx_dense"][t0:t1]
+                if t0 > 0:
+                    c["h0"], c["h0_frag"] = d["h_all"][t0 - 1], hb[(ci - 1) & 1]
+                if t1 < T:
+                    c["h_last_frag"] = hb[ci & 1]
+                part.append(c)
+            ops.gru_seq_fwd(part, **fwd_kw)
+    live = [b for b in bw if b is not None]
+    if live and chunk is None:
+        ops.gru_seq_bwd(live, **bwd_kw)
+    elif live:
+        assert len(live) == len(bw)
+        carry = [[zeros(B, H) for _ in range(2)] for B, _, H in sub]
+        starts = list(reversed(range(0, T, chunk)))
+        for ci, t0 in enumerate(starts):
+            t1 = min(T, t0 + chunk)
+            part = []
+            for b, cr in zip(bw, carry):
+                c = dict(b, T=t1 - t0)
+                for k in ("h_all", "gates", "dh_ext", "dgx_all", "dghn_all"):
+                    if b.get(k) is not None:
+                        c[k] = b[k][t0:t1]
+                if t0 > 0:
+                    c["h0"] = b["h_all"][t0 - 1]
+                    c["dh0"] = cr[ci & 1]
+                if t1 < T:
+                    c["dh_last"] = cr[(ci - 1) & 1]
+                part.append(c)
+            ops.gru_seq_bwd(part, **bwd_kw)
+            if carry_fault is not None and t0 > 0:
+                for cr in carry:
+                    carry_fault(ci, cr[ci & 1])
+    out = []
+    for s, rw, d, b, (B, T, H) in zip(scans, rws, fw, bw, sub):
+        cut = (lambda t, dim=0: t.cpu()) if fake else (lambda t, dim=0: t.index_select(dim, rw.to(device)).cpu())
+        o = {"h_all": cut(d["h_all"], 1)}
+        gt = d["gates"][:, : B * 4 * H].reshape(T, B, 4, H) if fake else _unblock_gates(d["gates"], B, H, rw).cpu()
+        for j, k in enumerate(SCAN_FWD_QUANTITIES[1:]):
+            o[k] = gt[:, :, j]
+        if b is not None:
+            for k in SCAN_BWD_QUANTITIES:
+                if b.get(k) is not None:
+                    o[k] = cut(b[k], 1 if k.endswith("_all") else 0)
+        out.append(o)
+    return out
+
+
+def scan_step_errors(got, ref64, rows):
+    """{(scan, quantity): (err, refmax)}, both [steps][blocks] float64 arrays (one step for dh0 and the row sums): for every step and every
+    block of SCAN_BLOCK consecutive checked rows   err = max |got - ref64| / max |ref64|   over THAT block of THAT step, all
+    columns - never over the whole tensor.  A quantity the reference has and `got` lacks is an error."""
+    res = {}
+    for i, (g_, r_) in enumerate(zip(got, ref64)):
+        blk = np.arange(len(rows[i])) // SCAN_BLOCK
+        ids = np.unique(blk)
+        for k, ref in r_.items():
+            assert k in g_, "scan %d: output %s missing" % (i, k)
+            a, ref = g_[k].double(), ref.double()
+            if a.dim() == 2:
+                a, ref = a.unsqueeze(0), ref.unsqueeze(0)
+            assert a.shape == ref.shape, (i, k, tuple(a.shape), tuple(ref.shape))
+            err, den = np.zeros((a.shape[0], len(ids))), np.zeros((a.shape[0], len(ids)))
+            for j, bid in enumerate(ids):
+                m = torch.from_numpy(np.nonzero(blk == bid)[0])
+                dd = (a[:, m] - ref[:, m]).abs().flatten(1)
+                num = torch.where(torch.isnan(dd).any(1), torch.full((dd.shape[0],), float("nan"), dtype=torch.float64), dd.amax(1))
+                den[:, j] = ref[:, m].abs().flatten(1).amax(1).numpy()
+                err[:, j] = num.numpy() / den[:, j]
+            res[(i, k)] = (err, den)
+    return res
+
+
+_SCAN_REF_CACHE = {}
+
+
+def scan_references(scans, rows, chunk=None, key=None, ref_device="cpu"):
+    """(fp64 reference, e_ref) of a case: e_ref = scan_step_errors of FakeOps in fp32 on the same inputs, rows and chunking - what fp32 rounding
+    alone costs at every step and block.  Asserts the input condition: every per-step block maximum of the fp64 reference >= 2**-100 and every
+    e_ref finite and non-zero (but for the one output that is a copy of an input: gate_hn at step 0 of a scan that starts from the zero state).  key: cache name (the cases of a test module share inputs between launch variants)."""
+    if key is not None and key in _SCAN_REF_CACHE:
+        return _SCAN_REF_CACHE[key]
+    from fake_ops import FakeOps
+    threads = torch.get_num_threads()
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    try:
+        ref64 = scan_reference_f64(scans, rows, ref_device)
+        fake = run_scans(FakeOps(), scans, rows, chunk=chunk)
+    finally:
+        torch.set_num_threads(threads)
+    e_ref = scan_step_errors(fake, ref64, rows)
+    for (i, k), (e, den) in e_ref.items():
+        assert den.min() >= SCAN_MIN_REF, "input condition: scan %d %s has a per-step block maximum of %.3e < 2**-100 (step %d)" % (
+            i, k, den.min(), int(np.argwhere(den == den.min())[0][0]))
+        ok = np.isfinite(e) & (e > 0)
+        if k == "gate_hn" and scans[i].get("h0") is None:
+            ok[0] = np.isfinite(e[0])        # from a zero state W_hn h + b_hn IS the input b_hn: exact in every arithmetic, e_ref = 0 (the bound is then F * 2**-23)
+        assert ok.all(), "input condition: scan %d %s: e_ref is 0 or not finite at step %d" % (i, k, int(np.argwhere(~ok)[0][0]))
+    if key is not None:
+        _SCAN_REF_CACHE[key] = (ref64, fake, e_ref)
+    return ref64, fake, e_ref
+
+
+def check_scan_vs_f64(scans, got, rows, chunk=None, key=None, F=None, ref_device="cpu"):
+    """Every output of a scan launch (or chain of launches) against the fp64 scan + autograd, step by step:
+      (new)  err[p, block] <= F * max(e_ref[p, block], 2**-23)   for every scan, quantity, step p and row block (scan_step_errors), where e_ref is
+             the fp32 CPU restatement's own distance from fp64 on the same inputs: the margin F covers another summation order and another
+             draw of inputs, not a wrong term;
+      (old)  the whole-tensor bound the suite already applies, unchanged: max |got - ref| <= 2e-5 (forward) / 5e-5 (backward) of the tensor's max.
+    Returns {(scan, quantity): (worst err / max(e_ref, 2**-23), step, block)}."""
+    F = SCAN_F if F is None else F
+    assert F <= SCAN_F_CAP
+    ref64, fake, e_ref = scan_references(scans, rows, chunk, key, ref_device)
+    err = scan_step_errors(got, ref64, rows)
+    worst, bad = {}, []
+    for (i, k), (e, den) in err.items():
+        ratio = e / np.maximum(e_ref[(i, k)][0], SCAN_EPS)
+        flat = np.where(np.isnan(ratio), np.inf, ratio)
+        p, j = np.unravel_index(int(np.argmax(flat)), flat.shape)
+        worst[(i, k)] = (float(flat[p, j]), int(p), int(j))
+        if not flat[p, j] <= F:
+            cols = (got[i][k].double() - ref64[i][k]).abs()
+            bad.append("scan %d %s: err %.3e = %.1f x e_ref %.3e at step %d, row block %d (%d of %d steps x blocks over F = %g; worst column %d)" % (
+                i, k, e[p, j], flat[p, j], e_ref[(i, k)][0][p, j], p, j, int((~(flat <= F)).sum()), flat.size, F,
+                int((cols[p] if cols.dim() == 3 else cols).amax(0).argmax())))
+        tol = 2e-5 if k in SCAN_FWD_QUANTITIES else 5e-5
+        whole = relerr(got[i][k].double().numpy(), ref64[i][k].numpy())
+        if not whole < tol:
+            bad.append("scan %d %s: whole-tensor rel err %.3e >= %g" % (i, k, whole, tol))
+    assert not bad, "\n".join(bad)
+    return worst
+
+
+def scan_lines(case, kernels, worst):
+    """the lines of profiles/scan_fp64_errors.txt for one case: per quantity the worst ratio over the scans and where it occurred"""
+    out = []
+    for q in SCAN_QUANTITIES:
+        hits = [(v, i) for (i, k), v in worst.items() if k == q]
+        if hits:
+            (ratio, p, j), i = max(hits)
+            out.append("%-34s %-58s %-12s ratio %6.3f  scan %d step %3d block %d" % (case, kernels[0] if q in SCAN_FWD_QUANTITIES else kernels[1], q, ratio, i, p, j))
+    return out
+
+
+def _logical_scan(gen, B, T, H, kind, h0=True, rowbias=False, b_ih=True, dh_last=0.0, dh_ext=0.0, want_dh0=False, want_rowsums=True, V=57):
+    """one seeded logical scan; kind: "table" / "table_rev" / "table_shift" (idx_shift -1 + start_token) / "dense"; dh_last / dh_ext: the scale of
+    the N(0, 1) gradient seeds, 0 = absent.  Weights randn / sqrt(H), as the kernel tests of test_gpu_parity.py draw them."""
+    rn = lambda *shape: torch.randn(*shape, generator=gen)
+    s = dict(B=B, T=T, H=H, w_hh=rn(3 * H, H) / H ** 0.5, b_hh=rn(3 * H) * 0.1, want_dh0=want_dh0, want_rowsums=want_rowsums)
+    if b_ih:
+        s["b_ih"] = rn(3 * H) * 0.1
+    if h0:
+        s["h0"] = rn(B, H) * 0.5
+    if rowbias:
+        s["gx_rowbias"] = rn(B, 3 * H) * 0.3
+    if kind == "dense":
+        s["gx_dense"] = rn(T, B, 3 * H) * 0.5
+    else:
+        s["gx_table"] = rn(V, 3 * H) * 0.5
+        s["idx"] = torch.randint(0, V, (B, T), generator=gen, dtype=torch.int32)
+        s["reverse"] = int(kind == "table_rev")
+        if kind == "table_shift":
+            s["idx_shift"], s["start_token"] = -1, V - 1
+    if dh_last:
+        s["dh_last"] = rn(B, H) * dh_last
+    if dh_ext:
+        s["dh_ext"] = rn(T, B, H) * dh_ext
+    return s
+
+
+def _ws_scans(gen, B, H, T=70, n=2):
+    """the inputs of the 32-slice / per-step cases: a reverse table scan with h0, row bias, dh_last only and dL/dh0, beside (n = 2) a dense scan
+    from a zero state with dh_ext only"""
+    sc = [_logical_scan(gen, B, T, H, "table_rev", rowbias=True, dh_last=1.0, want_dh0=True)]
+    if n > 1:
+        sc.append(_logical_scan(gen, B, T, H, "dense", h0=False, b_ih=False, dh_ext=0.5))
+    return sc
+
+
+# name -> (seed, builder(gen) -> logical scans, chunk).  The shapes are the production launches of engine.py and the edges of the dispatch in
+# csrc/gru_persist.hip; tests/test_scan_reference.py runs every one of them on the CPU, tests/test_gpu_parity.py on the kernels.
+SCAN_INPUTS = {
+    # encoder: 4 scans x 256 rows x 256 steps, token tables, two reverse, gradient from the last state only.  dh_last x 2**40 (exact in fp32): with
+    # w_hh = randn / sqrt(H) the gate gradients shrink by ~2**-0.47 per step, 2**-120 over the launch - the scale keeps every step's maximum
+    # above 2**-100, away from the subnormal range where a flush-to-zero GPU and the CPU differ for reasons that are no bugs
+    "enc": (11, lambda g: [_logical_scan(g, 256, 256, 512, k, h0=False, dh_last=2.0 ** 40) for k in ("table", "table_rev", "table", "table_rev")], None),
+    # decoder pipeline: 2 scans x 256 rows x 256 steps as 8 chained launches of 32 steps (226 steps: a tail chunk of 2), dh_ext at every step
+    "dec": (12, lambda g: [_logical_scan(g, 256, 256, 512, "table_shift", rowbias=True, dh_ext=0.5, want_dh0=True),
+                           _logical_scan(g, 256, 256, 512, "dense", b_ih=False, dh_ext=0.5, want_dh0=True)], 32),
+    "dec_tail": (13, lambda g: [_logical_scan(g, 256, 226, 512, "table_shift", rowbias=True, dh_ext=0.5, want_dh0=True),
+                                _logical_scan(g, 256, 226, 512, "dense", b_ih=False, dh_ext=0.5, want_dh0=True)], 32),
+    # attribute sub-decoders: 2 scans x 256 rows x 64 steps, h0 given, dh_ext every step, dL/dh0 wanted
+    "attr": (14, lambda g: [_logical_scan(g, 256, 64, 512, "table", rowbias=True, dh_ext=0.5, want_dh0=True) for _ in range(2)], None),
+    "ws_256x2": (15, lambda g: _ws_scans(g, 256, 512), None),
+    "ws_256x4": (16, lambda g: _ws_scans(g, 256, 512) + _ws_scans(g, 256, 512), None),
+    "t2": (17, lambda g: _ws_scans(g, 256, 512, T=2), None),
+    "t1": (18, lambda g: _ws_scans(g, 256, 512, T=1), None),
+    # 8 scans of different lengths in one call: every input kind, h0 beside none, a scan without dh_last beside one without dh_ext
+    "eight": (19, lambda g: [_logical_scan(g, 64, 3 + 2 * i, 512, ("table", "table_rev", "table_shift", "dense")[i % 4], h0=bool(i & 1), rowbias=i % 3 == 0,
+                                           dh_last=float(i % 3 != 1), dh_ext=0.5 * (i % 3 != 0), want_dh0=bool(i & 1), want_rowsums=i != 5) for i in range(8)], None),
+}
+for _B in (1, 33, 200):
+    for _H in (64, 96, 512):
+        SCAN_INPUTS["ws_%d_%d" % (_B, _H)] = (100 + _B + _H, (lambda g, B=_B, H=_H: _ws_scans(g, B, H, n=1 if (B, H) == (200, 512) else 2)), None)
+_SCAN_INPUT_CACHE = {}
+
+
+def scan_inputs(name):
+    """(logical scans, checked rows per scan, chunk) of a named case, built once"""
+    if name not in _SCAN_INPUT_CACHE:
+        seed, build, chunk = SCAN_INPUTS[name]
+        scans = build(torch.Generator().manual_seed(seed))
+        _SCAN_INPUT_CACHE[name] = (scans, [scan_rows(s["B"], seed + i) for i, s in enumerate(scans)], chunk)
+    return _SCAN_INPUT_CACHE[name]
+
+
+# FnGruFwd / FnGruBwd .variant bits (music-fader-nets_amd/_lib.py; repeated here so that the CPU tests need no library)
+_V_ROWS, _V_ALT, _V_LOOPS, _V_NOPP, _V_NORS, _V_X6ALT = 0xFF, 0x100, 0x400, 0x800, 0x2000, 0x8000
+
+
+def scan_kernel_names(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persistent=True, T=None, cus=256):
+    """(forward, backward) kernel instance a launch of these scans takes: the dispatch of fn_gru_fwd_persist / fn_gru_bwd_persist
+    (csrc/gru_persist.hip) restated on shapes, for the labels of profiles/scan_fp64_errors.txt and so that a case can assert that its shape
+    reaches the kernel it is meant for.  (What it cannot know: a launch the occupancy check refuses falls back to the per-step kernels
+    silently unless bf16 x 6 was forced.)  T: the steps per launch of a chunked chain; variants, cu_budget: (forward, backward)."""
+    H = scans[0]["H"]
+    Bs = [s["B"] for s in scans]
+    Ts = [s["T"] if T is None else T for s in scans]
+    one_src = all((s.get("gx_table") is not None) != (s.get("gx_dense") is not None) for s in scans)
+    ceil = lambda a, b: (a + b - 1) // b
+    names = []
+    for back in (False, True):
+        variant = variants[back]
+        step = "gru_bwd_step_kernel" if back else "gru_fwd_step_kernel"
+        budget = cu_budget[back]
+        c = budget if 0 < budget < cus else cus
+        nsl = H // 16
+        if not persistent or H > 512 or max(Ts) < 2 or nsl > c:
+            assert not x6
+            names.append(step)
+            continue
+        maxgroups = min(c // nsl, 64)
+
+        def pick_rows():
+            for rpw in (16, 32, 64, 128):
+                if variant & _V_ROWS in (0, rpw) and sum(ceil(B, rpw) for B in Bs) <= maxgroups:
+                    return rpw
+            return 0
+        ksplit = lambda rpw: 4 if rpw == 16 else 2 if rpw == 32 else 2 if (rpw == 64 and not variant & _V_ALT) else 1
+        full = lambda r: all(B % r == 0 for B in Bs)
+        if not back:
+            if x6:
+                ok = H == 512 and min(Ts) >= 2
+                mt = 1 if ok and full(64) and sum(Bs) // 64 <= min(c // 32, 64) else 2 if ok and full(128) and sum(Bs) // 128 <= min(c // 32, 64) else 0
+                assert mt, "not eligible for the bf16 x 6 forward"
+                pp = not variant & _V_X6ALT and 2 * sum(Bs) // (64 * mt) <= 64 and one_src
+                names.append("gru_fwd_x6pp_kernel<%d>" % (3 - mt) if pp else "gru_fwd_x6_kernel<%d>" % mt)
+                continue
+            rpw = pick_rows()
+            if not rpw:
+                names.append(step)
+                continue
+            wk = ksplit(rpw)
+            pp = H == 512 and (rpw == 128 or (rpw == 64 and wk == 2)) and not variant & (_V_LOOPS | _V_NOPP) and 2 * sum(ceil(B, rpw) for B in Bs) <= 64 \
+                and full(rpw) and min(Ts) >= 2 and one_src
+            tiling = {128: "4, 1, 2", 64: "4, 1, 1" if variant & _V_ALT else "2, 2, 2", 32: "2, 2, 1", 16: "1, 4, 1"}[rpw]
+            names.append("gru_fwd_pp_kernel<%d>" % (1 if rpw == 128 else 2) if pp else "gru_fwd_persist_kernel<%s, 4>" % tiling)
+            continue
+
+        def rs_tiles(half_chip_ok, rows32_ok):
+            if H != 512 or min(Ts) < 2:
+                return 0
+            g64, g32 = sum(Bs) // 64, sum(Bs) // 32
+            if full(64) and (g64 > 8 or (half_chip_ok and g64 * 16 == c)) and g64 <= 16 and g64 * 16 <= c:
+                return 2
+            return 1 if rows32_ok and full(32) and g32 > 8 and g32 <= 16 and g32 * 16 <= c else 0
+        if x6:
+            th = rs_tiles(True, bool(variant & _V_X6ALT))
+            assert th, "not eligible for the bf16 x 6 backward"
+            names.append("gru_bwd_x6_kernel<%d>" % th)
+            continue
+        th = 0 if variant & (_V_LOOPS | _V_NOPP | _V_NORS | _V_ROWS) else rs_tiles(False, True)
+        if th:
+            names.append("gru_bwd_rs_kernel<%d>" % th)
+            continue
+        rpw = pick_rows()
+        tiling = {128: "4, 1, 2", 64: "4, 1, 1" if variant & _V_ALT else "2, 2, 2", 32: "2, 2, 1", 16: "1, 4, 1", 0: ""}[rpw]
+        names.append("gru_bwd_persist_kernel<%s, 8>" % tiling if rpw else step)
+    return tuple(names)
+
+
+# The GPU cases of test_gpu_parity.test_scans_every_step_vs_fp64: (case id, inputs, both arithmetics?, launch keywords, kernels the case is for).
+# A case whose shape does not reach the kernels named here fails (scan_kernel_names).
+def _sc(cid, inputs, fwd, bwd, x6=False, variant=0, bvariant=None, budget=0, persistent=True):
+    """variant: of the forward and (bvariant None) the backward launches; budget: cu_budget of the backward launches, as engine.py gives the decoder
+    pipeline's backward half of the chip"""
+    return dict(id=cid, inputs=inputs, x6=x6, variants=(variant, variant if bvariant is None else bvariant), budget=(0, budget), persistent=persistent,
+                kernels=(fwd, bwd))
+
+
+_P4, _P8 = "gru_fwd_persist_kernel<%s, 4>", "gru_bwd_persist_kernel<%s, 8>"
+SCAN_CASES = [
+    _sc("enc-f32", "enc", "gru_fwd_pp_kernel<1>", "gru_bwd_rs_kernel<2>"),
+    _sc("enc-x6", "enc", "gru_fwd_x6pp_kernel<1>", "gru_bwd_x6_kernel<2>", x6=True),
+    _sc("dec-f32", "dec", "gru_fwd_pp_kernel<2>", "gru_bwd_rs_kernel<1>"),
+    _sc("dec-f32-half", "dec", "gru_fwd_pp_kernel<2>", _P8 % "4, 1, 2", budget=128),
+    _sc("dec-x6-32rows", "dec", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<1>", x6=True, bvariant=_V_X6ALT),
+    _sc("dec-x6-half", "dec", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<2>", x6=True, budget=128),
+    _sc("dec_tail-f32", "dec_tail", "gru_fwd_pp_kernel<2>", "gru_bwd_rs_kernel<1>"),
+    _sc("dec_tail-x6-32rows", "dec_tail", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<1>", x6=True, bvariant=_V_X6ALT),
+    _sc("dec_tail-x6-half", "dec_tail", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<2>", x6=True, budget=128),
+    _sc("attr-f32", "attr", "gru_fwd_pp_kernel<2>", "gru_bwd_rs_kernel<1>"),
+    _sc("attr-x6-32rows", "attr", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<1>", x6=True, bvariant=_V_X6ALT),
+    # the 32-slice weight-stationary kernels: every forced row block and every switch, T = 70
+    _sc("ws-256x2-rows64", "ws_256x2", "gru_fwd_pp_kernel<2>", _P8 % "2, 2, 2", variant=64),
+    _sc("ws-256x2-rows64-alt", "ws_256x2", _P4 % "4, 1, 1", _P8 % "4, 1, 1", variant=64 | _V_ALT),
+    _sc("ws-256x2-rows128", "ws_256x2", "gru_fwd_pp_kernel<1>", _P8 % "4, 1, 2", variant=128),
+    _sc("ws-256x2-compiler-loops", "ws_256x2", _P4 % "2, 2, 2", _P8 % "2, 2, 2", variant=_V_LOOPS),
+    _sc("ws-256x2-no-pingpong", "ws_256x2", _P4 % "2, 2, 2", _P8 % "2, 2, 2", variant=_V_NOPP),
+    _sc("ws-256x2-no-rs-bwd", "ws_256x2", "gru_fwd_pp_kernel<2>", _P8 % "2, 2, 2", variant=_V_NORS),
+    _sc("ws-256x2-x6-single-group", "ws_256x2", "gru_fwd_x6_kernel<1>", "gru_bwd_x6_kernel<1>", x6=True, variant=_V_X6ALT),
+    _sc("ws-256x4-no-pingpong", "ws_256x4", _P4 % "4, 1, 2", _P8 % "4, 1, 2", variant=_V_NOPP),
+    _sc("ws-256x4-x6-single-group", "ws_256x4", "gru_fwd_x6_kernel<2>", "gru_bwd_x6_kernel<2>", x6=True, variant=_V_X6ALT),
+]
+for _B, _H, _rows in ((33, 64, (16, 32, 64, 128)), (200, 64, (16, 32, 64, 128)), (33, 96, (16, 32, 64, 128)), (200, 96, (16, 32, 64, 128)),
+                      (33, 512, (16, 32, 64, 128)), (200, 512, (32, 64, 128))):      # (1 x 200 rows in 16-row groups: 13 groups > the 8 that fit at H = 512)
+    _til = {16: "1, 4, 1", 32: "2, 2, 1", 64: "2, 2, 2", 128: "4, 1, 2"}
+    for _r in _rows:
+        SCAN_CASES.append(_sc("ws-%d-%d-rows%d" % (_B, _H, _r), "ws_%d_%d" % (_B, _H), _P4 % _til[_r], _P8 % _til[_r], variant=_r))
+    SCAN_CASES.append(_sc("ws-%d-%d-rows64-alt" % (_B, _H), "ws_%d_%d" % (_B, _H), _P4 % "4, 1, 1", _P8 % "4, 1, 1", variant=64 | _V_ALT))
+    SCAN_CASES.append(_sc("ws-%d-%d-compiler-loops" % (_B, _H), "ws_%d_%d" % (_B, _H), None, None, variant=_V_LOOPS))
+SCAN_CASES += [_sc("step-%d-%d" % (_B, _H), "ws_%d_%d" % (_B, _H), "gru_fwd_step_kernel", "gru_bwd_step_kernel", persistent=False)
+               for _B in (1, 33, 200) for _H in (64, 96, 512)]
+SCAN_CASES += [
+    _sc("t2-f32", "t2", "gru_fwd_pp_kernel<2>", "gru_bwd_rs_kernel<1>"),
+    _sc("t2-x6-32rows", "t2", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<1>", x6=True, bvariant=_V_X6ALT),
+    _sc("t1-falls-back", "t1", "gru_fwd_step_kernel", "gru_bwd_step_kernel"),
+    _sc("eight-f32", "eight", "gru_fwd_pp_kernel<2>", "gru_bwd_rs_kernel<1>"),
+    _sc("eight-x6-32rows", "eight", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<1>", x6=True, bvariant=_V_X6ALT),
+]

@@ -1,6 +1,8 @@
 """Parity of the HIP path (through the C ABI) against the oracle / golden fixtures on a real MI355X.
 
-Tolerances (fp32): kernel outputs vs an fp64/CPU restatement of the same op: 2e-5 relative to the tensor's max;
+Tolerances (fp32): kernel outputs vs the fp32 CPU restatement of the same op (tests/fake_ops.py) or fp64 torch: 2e-5 relative to the tensor's
+max (backward scans 5e-5); the GRU scan kernels additionally at EVERY step and 32-row block against an fp64 scan + autograd, normalised by that
+block of that step alone: err <= SCAN_F x max(the fp32 restatement's own error there, 2**-23) (helpers.check_scan_vs_f64);
 end-to-end gradients vs the reference's autograd: 5e-4 relative to each tensor's max; greedy-decode token ids
 bit-exact wherever the reference's own top-2 log-prob gap exceeds 1e-4 (a flipped near-tie changes every later token,
 so rows are compared up to the first sub-threshold gap); past those near-ties, every step of every decode path against an fp64 replay
@@ -14,8 +16,9 @@ import pytest
 import torch
 
 from fake_ops import FakeOps
-from helpers import (NOISE_PARAMS, REPLAY_CASES, REPLAY_GRAPH_PATHS, batch_of, grad_tolerances, load_golden, make_model, oracle_grads_f64, relerr,
-                     replay_decode_check, replay_inputs, replay_line, replay_z, sd_from)
+from helpers import (NOISE_PARAMS, REPLAY_CASES, REPLAY_GRAPH_PATHS, SCAN_CASES, _unblock_gates, batch_of, check_scan_vs_f64, grad_tolerances, load_golden,
+                     make_model, oracle_grads_f64, relerr, replay_decode_check, replay_inputs, replay_line, replay_z, run_scans, scan_inputs, scan_kernel_names,
+                     scan_lines, sd_from)
 from mfn_import import load_package
 from oracle import gmvae_oracle as orc
 
@@ -297,17 +300,6 @@ def _pack(backend, mat, device):
     return out
 
 
-def _unblock_gates(g, B, H):
-    """the HIP kernels' private gate layout (gate_off in csrc/gru.hip) -> [T][B][4][H]"""
-    T = g.shape[0]
-    nrt = (B + 15) // 16
-    b = torch.arange(B).view(B, 1, 1)
-    q = torch.arange(4).view(1, 4, 1)
-    u = torch.arange(H).view(1, 1, H)
-    off = ((((u // 16) * nrt + (b // 16)) * 4 + q) * 4 + (b % 4)) * 64 + ((b % 16) // 4) * 16 + (u % 16)
-    return g[:, off.reshape(-1)].view(T, B, 4, H)
-
-
 @pytest.mark.parametrize("mode", ["per_step", "stationary", "stationary_half_chip"])
 @pytest.mark.parametrize("B,T,H", [(6, 5, 64), (70, 9, 96), (256, 4, 512), (40, 37, 512)])
 def test_gru_scan_fwd_bwd_kernels(ops, B, T, H, mode):
@@ -353,6 +345,62 @@ def test_gru_scan_fwd_bwd_kernels(ops, B, T, H, mode):
         fake.embed_grad(bc[i]["dgx_all"], cpu[i]["idx"], cpu[i]["idx_shift"], 20, cpu[i]["reverse"], 21, out_c)
         ops.embed_grad(bd[i]["dgx_all"], dev[i]["idx"], cpu[i]["idx_shift"], 20, cpu[i]["reverse"], 21, out_d)
         close(out_d, out_c, 5e-5, "embed_grad[%d]" % i)
+
+
+@pytest.mark.parametrize("case", SCAN_CASES, ids=[c["id"] for c in SCAN_CASES])
+def test_scans_every_step_vs_fp64(ops, case):
+    """Every scan kernel instance fn_gru_seq_fwd / fn_gru_seq_bwd can launch, at its production launch shape, against an fp64 scan and torch
+    autograd through it (helpers.scan_reference_f64, evaluated by plain torch in float64), at EVERY step and 32-row block of the checked rows
+    (two rows of every 16-row tile, all columns): h_all, the four saved-gate planes, dgx_all, dghn_all, dh0 and both row sums within
+    SCAN_F x max(e_ref, 2**-23) of the reference, e_ref = the fp32 CPU restatement's own error at that step and block, and within the whole-tensor
+    bound as before (helpers.check_scan_vs_f64).  The cases (helpers.SCAN_CASES): the encoder launch (4 x 256 rows x 256 steps, dh_last only), the
+    decoder pipeline (2 x 256 rows, 256 and 226 steps as chained 32-step launches with operand-image and state-gradient hand-overs, backward on
+    the whole and on half of the chip), the attribute decoders (64 steps, dL/dh0), the 32-slice kernels in every forced row block and switch at
+    70 steps with ragged batches, the per-step kernels, T = 2 and T = 1, 8 scans of different lengths.  The arithmetic and the variant bits are
+    asked for explicitly, so a launch that cannot take the bf16 x 6 kernel raises; a bf16 x 6 case must also differ in some bit from the fp32
+    kernels' result (it really ran).  Each case prints the lines of profiles/scan_fp64_errors.txt."""
+    scans, rows, chunk = scan_inputs(case["inputs"])
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    Ts = [None] if chunk is None else sorted({chunk, scans[0]["T"] % chunk or chunk})
+    names = [scan_kernel_names(scans, case["variants"], case["x6"], case["budget"], case["persistent"], T=T, cus=cus) for T in Ts]
+    for nm in names:
+        for want, have in zip(case["kernels"], nm):
+            assert want is None or want == have, (want, have)      # the shape reaches the kernel the case is for on this device
+    kw = [dict(persistent=case["persistent"], cu_budget=case["budget"][i], variant=case["variants"][i]) for i in (0, 1)]
+    try:
+        ops.dw_x6 = case["x6"]
+        got = run_scans(ops, scans, rows, device=DEV, chunk=chunk, x6=case["x6"], fwd_kw=kw[0], bwd_kw=kw[1])
+        torch.cuda.synchronize()
+        assert not ops.gru_sync_error()
+        if case["x6"]:
+            ops.dw_x6 = False
+            f32 = run_scans(ops, scans, rows, device=DEV, chunk=chunk, x6=False)
+            torch.cuda.synchronize()
+            assert not ops.gru_sync_error()
+            assert any(not torch.equal(a[k], b[k]) for a, b in zip(got, f32) for k in ("h_all", "dgx_all"))      # results are not bit-identical
+    finally:
+        ops.dw_x6 = _x6_default()
+    worst = check_scan_vs_f64(scans, got, rows, chunk, key=case["inputs"], ref_device=DEV)
+    print()
+    for line in scan_lines(case["id"], names[0], worst):
+        print(line)
+
+
+def test_nine_scans_in_one_call_are_refused(ops):
+    """fn_gru_seq_fwd / fn_gru_seq_bwd take at most 8 scans: FN_E_COUNT, nothing launched"""
+    scans, rows, _ = scan_inputs("eight")
+    with pytest.raises(RuntimeError, match=r"code -5"):
+        run_scans(ops, scans + scans[:1], rows + rows[:1], device=DEV)
+    torch.cuda.synchronize()
+    assert not ops.gru_sync_error()
+    fwd_only = [{k: v for k, v in s.items() if k not in ("dh_last", "dh_ext")} for s in scans]
+    done = run_scans(ops, fwd_only, rows, device=DEV)
+    b = dict(B=64, T=3, H=512, w_hh_t_frag=torch.zeros(ops.frag_floats(512, 1536), device=DEV), h_all=torch.zeros(3, 64, 512, device=DEV),
+             gates=torch.zeros(3, ops.gates_floats(64, 512), device=DEV), dh_last=torch.zeros(64, 512, device=DEV), dgx_all=torch.zeros(3, 64, 1536, device=DEV),
+             dghn_all=torch.zeros(3, 64, 512, device=DEV), scratch=torch.zeros(64, 512, device=DEV))
+    with pytest.raises(RuntimeError, match=r"code -5"):
+        ops.gru_seq_bwd([b] * 9)
+    assert len(done) == 8 and not ops.gru_sync_error()
 
 
 def test_weight_stationary_scans_random_configurations(ops):

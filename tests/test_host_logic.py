@@ -398,3 +398,32 @@ def test_isa_wait_checker_finds_an_uncovered_asm_load(tmp_path):
     assert run(asm("global_load_dwordx4 v[0:3], v[40:41], off") + "\tv_mov_b64 v[2:3], v[8:9]\n\ts_waitcnt vmcnt(0)\n") == 1
     # the build ran it on the real kernels
     assert os.path.exists(os.path.join(csrc, "isa.checked")), "run __graft_entry__.build(): csrc/Makefile checks the compiled kernels (isa.checked)"
+
+
+def test_fake_ops_do_not_read_an_output_they_overwrite():
+    """beta == 0 means the output is write-only, as in the kernels (gemm.hip: `if (beta != 0.f)`): the engine hands over uninitialised
+    buffers, and 0 x NaN is NaN.  (FakeOps.gru_dwhh once formed beta * dW: the gradient comparison above failed whenever the allocator
+    returned memory that held a NaN.)"""
+    ops = FakeOps()
+    torch.manual_seed(0)
+    nan = lambda *s: torch.full(s, float("nan"))
+    H, R = 32, 10
+    dgx, dghn, hp = torch.randn(R, 3 * H), torch.randn(R, H), torch.randn(R, H)
+    dW = nan(3 * H, H)
+    ops.gru_dwhh(dgx, dghn, hp, dW)
+    assert torch.equal(dW, torch.cat([dgx[:, :2 * H], dghn], dim=1).t() @ hp)
+    ops.gru_dwhh(dgx, dghn, hp, dW, beta=1.0)
+    assert torch.allclose(dW, 2 * torch.cat([dgx[:, :2 * H], dghn], dim=1).t() @ hp)
+    A, B = torch.randn(R, H), torch.randn(7, H)
+    Cm = nan(R, 7)
+    ops.gemm(A, B, Cm)
+    assert torch.equal(Cm, A @ B.t())
+    Cm = nan(R, 7)
+    ops.gemm_multi([dict(C=Cm, segs=[(A, B)])])
+    assert torch.equal(Cm, A @ B.t())
+    out = nan(H)
+    ops.colsum(A, out)
+    assert torch.equal(out, A.sum(0))
+    out = nan(1)
+    ops.sum(A, out)
+    assert torch.equal(out, A.sum().view(1))
