@@ -397,6 +397,22 @@ size_t fn_decode_ws_bytes(int B, int H, int V);
 size_t fn_decode_sync_ws_bytes(void);
 int fn_decode_greedy(const FnDecode* d, void* stream);
 
+/* The same decode with FORCED feedback under a per-step mask: after step i the decoder is fed a given token instead of its own argmax
+ * wherever the mask says so.  This is the reference's train-mode loop (gmm_model.py:139-148: `p = torch.rand(1)`, `if p < self.eps:
+ * out = sample[:, i]` else `out = self._sampling(out)`) with force[i] = (p_i < eps) and forced = the data tokens, and prompted
+ * continuation with force = a prefix of ones.  d->tokens / d->logp keep their meaning: the model's OWN first-index argmax and
+ * log-probabilities of every step, forced or not; the stream that was fed back is fed[b][i] = force[i] ? forced[b][i] : tokens[b][i].
+ * The mask is read from device memory at every step, so one captured graph serves any mask.  A forced token is clamped to [0, V)
+ * (as fn_token_sort clamps).  force[steps-1] is ignored (nothing is fed after the last step).  Shape, alignment and eligibility
+ * answers are fn_decode_greedy's; f, f->forced or f->force NULL: FN_E_NULL; forced_ld < steps: FN_E_SHAPE. */
+typedef struct FnDecodeForce {
+    const int32_t* forced;    /* [B][forced_ld] tokens, forced_ld >= steps                            */
+    int32_t forced_ld;
+    const uint8_t* force;     /* [steps] DEVICE bytes: force[i] != 0 -> the token fed into step i+1 is forced[b][i],
+                                 else the first-index argmax of step i (as fn_decode_greedy)          */
+} FnDecodeForce;
+int fn_decode_forced(const FnDecode* d, const FnDecodeForce* f, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Output heads
  * ------------------------------------------------------------------------------------------ */

@@ -61,6 +61,7 @@ int fn_best_tokens_host(const uint64_t* best, int steps, int B, int V, int32_t* 
 size_t fn_decode_ws_bytes_host(int B, int H, int V);                                                     /* fn_decode_ws_bytes */
 size_t fn_decode_sync_ws_bytes_host(void);                                                               /* fn_decode_sync_ws_bytes */
 int fn_decode_greedy_host(const FnDecode* d, void* stream);                                              /* fn_decode_greedy */
+int fn_decode_forced_host(const FnDecode* d, const FnDecodeForce* f, void* stream);                      /* fn_decode_forced */
 size_t fn_frag_floats_host(int rows, int K);                                                             /* fn_frag_floats */
 size_t fn_gru_gates_floats_host(int B, int H);                                                           /* fn_gru_gates_floats */
 

@@ -87,6 +87,10 @@ class FnDecode(C.Structure):
                 ("tokens", vp), ("tok_ld", C.c_int32), ("logp", vp), ("ws", vp), ("sync_ws", vp)]
 
 
+class FnDecodeForce(C.Structure):
+    _fields_ = [("forced", vp), ("forced_ld", C.c_int32), ("force", vp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fadernets.h
 SIGNATURES = {
     "fn_version": (C.c_int, []),
@@ -117,6 +121,7 @@ SIGNATURES = {
     "fn_decode_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "fn_decode_sync_ws_bytes": (C.c_size_t, []),
     "fn_decode_greedy": (C.c_int, [C.POINTER(FnDecode), vp]),
+    "fn_decode_forced": (C.c_int, [C.POINTER(FnDecode), C.POINTER(FnDecodeForce), vp]),
     "fn_gru_dwhh_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "fn_gru_dwhh_f32": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_size_t, vp]),
     "fn_embed_grad_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),

@@ -67,6 +67,10 @@ struct DArgs {
     int* tokens;
     float* logp;                                     // [B][steps][V] or null
     u32* sync;
+    // fn_decode_forced only (read by the FORCED instantiations; behind every field of the greedy kernel's argument block)
+    const int* forced;                               // [B][forced_ld] tokens
+    const unsigned char* force;                      // [steps] device bytes: force[i] != 0 -> the token fed into step i+1 is forced[b][i]
+    int forced_ld;
 };
 
 // L1-bypassing dword load WITHOUT a wait (pair with fn_wait_vm<0>()): an agent-scope atomic load is followed by its own s_waitcnt,
@@ -178,7 +182,9 @@ FN_DEVINL f32x4 gather_sum(const float* red, int tile, int n, int coff) {
     return s;
 }
 
-template <int MT>
+// FORCED (fn_decode_forced): after step t-1 the layer-1 role feeds a GIVEN token where the device mask says so (gmm_model.py:139-144, the
+// `p < self.eps` branch per step; a prompt is a mask prefix).  Only the token selection of the layer-1 role differs; every wait stays.
+template <int MT, bool FORCED>
 __global__ __launch_bounds__(NT) void decode_greedy_kernel(const DArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = a.H, nk = H >> 5, nsl = H >> 4, B = a.B;
@@ -256,6 +262,14 @@ __global__ __launch_bounds__(NT) void decode_greedy_kernel(const DArgs a) {
                 if (reload) gld4_sc1(hp, t == 0 ? a.h0 + (long)b * H + jj0 : xin + frag_off(min(rl, nrow - 1), jj0, nk));
 #pragma unroll
                 for (int q = 0; q < 3; ++q) rb[q] = a.rowbias1 ? ldv4(a.rowbias1 + (long)b * 3 * H + q * H + jj0) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                // forced step (one mask byte, the same for every thread of every layer-1 workgroup): the given token is requested here, with
+                // the per-row constants, so that its latency lies under the recurrent product and not behind the C4 / C5 wait
+                bool fstep = false;
+                int ftok_raw = 0;
+                if (FORCED && t > 0) {
+                    fstep = a.force[t - 1] != 0;
+                    if (fstep) ftok_raw = a.forced[(long)b * a.forced_ld + (t - 1)];
+                }
                 f32x4 acc[MT][3];
                 kquarter<MT, 3>(xin, wl, nk, lane, wave, acc);
                 fn_touch(hp);
@@ -268,12 +282,20 @@ __global__ __launch_bounds__(NT) void decode_greedy_kernel(const DArgs a) {
                 // the token of step t-1: every layer-1 workgroup takes the argmax of the logits itself as soon as the output slices
                 // have arrived (the ARG workgroup, which writes tokens and log-probabilities out, is off the critical chain)
                 int tok = a.start_token;
+                // forced step: the token is clamped to the table's rows
+                const int ftok = min(max(ftok_raw, 0), a.V - 1);
                 if (t > 0 && !single) {
                     // throughput regime (several blocks per replica): the token comes from the ARG workgroup - one more hand-over in a block's
                     // chain, but the 32-fold redundant argmax (12 k of this role's 26 k cycles per block) no longer bounds the pipeline
                     if (!sy.wait(C5, (u32)t)) return;
                     tok = __hip_atomic_load(a.tokens + (long)b * a.tok_ld + (t - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (FORCED && fstep) tok = ftok;
                     FN_DSTAMP(0, 5);
+                } else if (t > 0 && FORCED && fstep) {
+                    // the wait stays (the ping-pong slabs are only safe because a writer of step t+1 starts after the logits of step t-1
+                    // exist), the 32-fold redundant reduction of those logits is what a forced step saves
+                    if (!sy.wait(C4, (u32)a.nvt * (u32)t)) return;
+                    tok = ftok;
                 } else if (t > 0) {
                     if (!sy.wait(C4, (u32)a.nvt * (u32)t)) return;
                     FN_DSTAMP(0, 4);
@@ -523,9 +545,9 @@ __global__ __launch_bounds__(NT) void decode_greedy_kernel(const DArgs a) {
     }
 }
 
-template <int MT>
+template <int MT, bool FORCED>
 int launch_decode(const DArgs& a, int grid, hipStream_t st) {
-    auto k = decode_greedy_kernel<MT>;
+    auto k = decode_greedy_kernel<MT, FORCED>;
     static std::atomic<int> fits[FN_MAX_DEVICES];  // write-once per device (zero-initialised): 1 = at least one workgroup of this kernel fits a CU, -1 = it does not
     const size_t lds = ((size_t)3 * a.H * 16 + (size_t)4 * MT * 3 * RT) * 4 + 16 + 64 * 4;
     const int dev = fn_device();
@@ -555,8 +577,8 @@ size_t fn_decode_ws_bytes(int B, int H, int V) {
 
 size_t fn_decode_sync_ws_bytes(void) { return (size_t)(ERRW + 32) * 4; }
 
-int fn_decode_greedy(const FnDecode* d, void* stream) {
-    if (!d) return FN_E_NULL;
+// fn_decode_greedy (f == nullptr) and fn_decode_forced: one set of shape / alignment / eligibility answers
+static int decode_launch(const FnDecode* d, const FnDecodeForce* f, void* stream) {
     if (!d->w_hh1_frag || !d->b_hh1 || !d->table1 || !d->h0 || !d->w_ih2_frag || !d->w_hh2_frag || !d->b_hh2 || !d->w_out_frag || !d->b_out ||
         !d->tokens || !d->ws || !d->sync_ws)
         return FN_E_NULL;
@@ -593,12 +615,26 @@ int fn_decode_greedy(const FnDecode* d, void* stream) {
     (void)vp;
     a.tokens = d->tokens; a.logp = d->logp;
     a.sync = reinterpret_cast<u32*>(d->sync_ws);
+    a.forced = f ? f->forced : nullptr; a.force = f ? f->force : nullptr; a.forced_ld = f ? f->forced_ld : 0;
     // h0 -> slot 1 of the layer-1 exchange (the operand of step 0), rows padded with zeros
     int rc = launch_pack(d->h0, d->B, d->H, d->H, a.x1 + bp * d->H, st);
     if (rc != FN_OK) return rc;
     hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)ERRW * 4, st);             // counters only: the error word is sticky
     if (me != hipSuccess) return (int)me;
-    return mt == 1 ? launch_decode<1>(a, grid, st) : (mt == 2 ? launch_decode<2>(a, grid, st) : launch_decode<4>(a, grid, st));
+    if (f) return mt == 1 ? launch_decode<1, true>(a, grid, st) : (mt == 2 ? launch_decode<2, true>(a, grid, st) : launch_decode<4, true>(a, grid, st));
+    return mt == 1 ? launch_decode<1, false>(a, grid, st) : (mt == 2 ? launch_decode<2, false>(a, grid, st) : launch_decode<4, false>(a, grid, st));
+}
+
+int fn_decode_greedy(const FnDecode* d, void* stream) {
+    if (!d) return FN_E_NULL;
+    return decode_launch(d, nullptr, stream);
+}
+
+int fn_decode_forced(const FnDecode* d, const FnDecodeForce* f, void* stream) {
+    if (!d || !f) return FN_E_NULL;
+    if (!f->forced || !f->force) return FN_E_NULL;
+    if (f->forced_ld < d->steps) return FN_E_SHAPE;
+    return decode_launch(d, f, stream);
 }
 
 }  // extern "C"

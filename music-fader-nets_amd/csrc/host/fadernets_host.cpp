@@ -561,8 +561,8 @@ int fn_best_tokens_host(const uint64_t* best, int steps, int B, int V, int32_t* 
 size_t fn_decode_ws_bytes_host(int B, int H, int) { return (size_t)4 * B * H * sizeof(float) + 16; }
 size_t fn_decode_sync_ws_bytes_host(void) { return 16; }
 
-int fn_decode_greedy_host(const FnDecode* d, void*) {
-    if (!d) return FN_E_NULL;
+// fn_decode_greedy_host (f == nullptr) and fn_decode_forced_host
+static int decode_host(const FnDecode* d, const FnDecodeForce* f) {
     if (!d->w_hh1_frag || !d->b_hh1 || !d->table1 || !d->h0 || !d->w_ih2_frag || !d->w_hh2_frag || !d->b_hh2 || !d->w_out_frag || !d->b_out ||
         !d->tokens || !d->ws || !d->sync_ws)
         return FN_E_NULL;
@@ -621,9 +621,23 @@ int fn_decode_greedy_host(const FnDecode* d, void*) {
             }
             d->tokens[(long)b * d->tok_ld + t] = best;
             tok = best;
+            if (f && f->force[t] && t + 1 < d->steps)                                                    // `p < self.eps`: sample[:, i] (:139-142)
+                tok = std::min(std::max(f->forced[(long)b * f->forced_ld + t], 0), V - 1);
         }
     }
     return FN_OK;
+}
+
+int fn_decode_greedy_host(const FnDecode* d, void*) {
+    if (!d) return FN_E_NULL;
+    return decode_host(d, nullptr);
+}
+
+int fn_decode_forced_host(const FnDecode* d, const FnDecodeForce* f, void*) {
+    if (!d || !f) return FN_E_NULL;
+    if (!f->forced || !f->force) return FN_E_NULL;
+    if (f->forced_ld < d->steps) return FN_E_SHAPE;
+    return decode_host(d, f);
 }
 
 }  // extern "C"

@@ -11,9 +11,60 @@ import torch
 from .engine import E_VOCAB, LOGIT_LD
 
 
+def _force_mask(force, steps):
+    """force as greedy_decode takes it - a bool per step, or an int P = the first P steps - as a list of `steps` bools; ValueError otherwise"""
+    if not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError("steps: a positive int, got %r" % (steps,))
+    if isinstance(force, (int, np.integer)) and not isinstance(force, (bool, np.bool_)):
+        if not 0 <= int(force) <= steps:
+            raise ValueError("force = P forces the first P steps: 0 <= P <= %d, got %d" % (steps, int(force)))
+        return [i < int(force) for i in range(steps)]
+    mask = np.asarray(force.detach().cpu() if torch.is_tensor(force) else force)
+    if mask.ndim != 1 or mask.shape[0] != steps:
+        raise ValueError("force: one entry per step (%d), got shape %s" % (steps, tuple(mask.shape)))
+    return [bool(m) for m in mask]
+
+
+def _forced_args(z, steps, forced, force):
+    """validated (forced int32 (Bi, steps) on z's device, mask = tuple of `steps` bools with the ignored last entry False); ValueError
+    before anything is launched"""
+    if forced is None or force is None:
+        raise ValueError("forced and force go together: the tokens and the per-step mask that selects them")
+    if not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError("steps: a positive int, got %r" % (steps,))
+    if not torch.is_tensor(forced):
+        forced = torch.as_tensor(np.asarray(forced))
+    if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool:
+        raise ValueError("forced: integer tokens, got %s" % forced.dtype)
+    if forced.dim() != 2 or forced.shape[0] != z.shape[0] or forced.shape[1] < steps:
+        raise ValueError("forced: (%d, >= %d) tokens, got %s" % (z.shape[0], steps, tuple(forced.shape)))
+    mask = _force_mask(force, steps)
+    mask[steps - 1] = False                          # nothing is fed after the last step
+    forced = forced[:, :steps]
+    if forced.numel():
+        lo, hi = int(forced.min()), int(forced.max())                  # a forced token indexes the embedding table
+        if lo < 0 or hi >= E_VOCAB:
+            raise ValueError("forced: tokens in [0, %d), got %d .. %d" % (E_VOCAB, lo, hi))
+    return forced.to(device=z.device, dtype=torch.int32).contiguous(), tuple(mask)
+
+
+def fed_tokens(tokens, forced, force):
+    """the stream that was fed back: forced[b][i] where force[i], else the decoder's own token; force as greedy_decode takes it (a bool
+    per step or an int P)"""
+    m = torch.tensor(_force_mask(force, tokens.shape[1]), dtype=torch.bool, device=tokens.device)
+    return torch.where(m.view(1, -1), forced[:, :tokens.shape[1]].to(device=tokens.device, dtype=tokens.dtype), tokens)
+
+
+MAX_MASKED_GRAPHS = 4      # cached decode graphs whose key carries a mask (the unmasked ones are bounded by the shapes in use)
+
+
 @torch.no_grad()
-def greedy_decode(model, z, steps, want_logp=True, use_graph=None):
+def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, force=None):
     """z (Bi, 2Z+24) -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32).
+
+    forced (Bi, >= steps) integer tokens + force (a bool per step, or an int P = the first P steps): after step i the decoder is fed
+    forced[:, i] instead of its own argmax wherever force[i] (gmm_model.py:139-144 with force[i] = `p < self.eps`; a prompt is a prefix).
+    The results keep their meaning: the model's OWN log-probs and first-index argmax of every step (fed_tokens() gives the fed stream).
 
     Bi <= Engine.single_launch_rows: ONE launch for the whole decode (fn_decode_greedy; above 32 rows a pipeline of 32- / 64-row blocks through
     its role workgroups).  Larger batches: steps x {layer-1 cell, W_ih2 projection,
@@ -24,33 +75,64 @@ def greedy_decode(model, z, steps, want_logp=True, use_graph=None):
     after every optimiser step / load_state_dict), so a graph stays valid when the weights change."""
     eng = model.engine()
     z = z.float().contiguous()
+    mask = None
+    if forced is not None or force is not None:
+        forced, mask = _forced_args(z, steps, forced, force)
     if _single_launch_ok(eng, z):
-        res = _decode_single_launch(eng, z, steps, want_logp)
+        res = _decode_single_launch(eng, z, steps, want_logp, forced, mask)
         if res is not None:
             return res
     if use_graph is None:
-        use_graph = z.is_cuda
+        # a graph per mask: by default only for the masks that come back (none, a prompt prefix); an arbitrary mask - every scheduled-sampling
+        # step draws a new one - goes launch by launch unless the caller asks for the graph
+        use_graph = z.is_cuda and (mask is None or not any(b and not a for a, b in zip(mask, mask[1:])))
     if not use_graph:
-        return _decode_body(eng, z, steps, want_logp, None, None)
+        return _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask)
     cache = eng.__dict__.setdefault("_decode_graphs", {})
+    # the captured launches depend on the path taken, on the cells' / GEMMs' arithmetic switches and - the per-token paths pick every step's
+    # token pointer on the host - on the mask
     key = (z.shape[0], steps, bool(want_logp), z.shape[0] >= eng.cell_decode_rows, bool(getattr(eng, "fused_argmax", True)),
-           bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)))     # the captured launches depend on the path taken (and on the cells' arithmetic)
+           bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)),
+           getattr(eng.ops, "cell_x6_rows", None), bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)), mask)
     ent = cache.get(key)
     if ent is None:
         zs = z.clone()
+        fs = None if mask is None else forced.clone()
         tokens = torch.zeros(z.shape[0], steps, dtype=torch.int32, device=z.device)
         logp = torch.empty(z.shape[0], steps, E_VOCAB, device=z.device) if want_logp else None
-        _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps)      # warm-up: allocates every buffer at its FINAL size (nothing is allocated inside the capture)
+        _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask)      # warm-up: allocates every buffer at its FINAL size (nothing is allocated inside the capture)
         g = torch.cuda.CUDAGraph()
         torch.cuda.synchronize()
         getattr(eng.ops, "begin_capture", lambda: None)()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            _decode_body(eng, zs, steps, want_logp, logp, tokens)
-        ent = cache[key] = (g, zs, logp, tokens)
-    g, zs, logp, tokens = ent
+            _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask)
+        ent = cache[key] = (g, zs, logp, tokens, fs)
+        masked = [k for k in cache if k[-1] is not None]
+        if len(masked) > MAX_MASKED_GRAPHS:           # each entry keeps its own static logp / tokens buffers: the oldest masked graph goes
+            del cache[masked[0]]
+    g, zs, logp, tokens, fs = ent
     zs.copy_(z)
+    if fs is not None:
+        fs.copy_(forced)
     g.replay()
     return (None if logp is None else logp.clone()), tokens.clone()
+
+
+def continue_from(model, z, prompt, steps, want_logp=True):
+    """Prompted continuation: prompt (Bi, P) tokens, 0 <= P <= steps -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32) where
+    tokens[:, :P] is the prompt and the rest is what the model wrote after it (the stream that was fed back); the log-probs are
+    the model's own at every step, i.e. logp[:, i] scores tokens[:, i] given the start token and tokens[:, :i]."""
+    prompt = prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))
+    if prompt.dim() != 2 or prompt.shape[0] != z.shape[0] or prompt.shape[1] > steps:
+        raise ValueError("prompt: (%d, <= %d) tokens, got %s" % (z.shape[0], steps, tuple(prompt.shape)))
+    P = prompt.shape[1]
+    if P == 0:
+        return greedy_decode(model, z, steps, want_logp)
+    forced = torch.zeros(z.shape[0], steps, dtype=prompt.dtype)
+    forced[:, :P] = prompt.cpu()
+    logp, tokens = greedy_decode(model, z, steps, want_logp, forced=forced, force=P)
+    tokens[:, :P] = forced[:, :P].to(device=tokens.device, dtype=tokens.dtype)
+    return logp, tokens
 
 
 def _single_launch_ok(eng, z):
@@ -60,7 +142,7 @@ def _single_launch_ok(eng, z):
             and eng.H <= 512 and eng.single_launch_decode)
 
 
-def _decode_single_launch(eng, z, steps, want_logp):
+def _decode_single_launch(eng, z, steps, want_logp, forced=None, mask=None):
     """None when the library reports the configuration as not eligible (e.g. fewer CUs than role workgroups) or the launch
     timed out waiting for a hand-over: the caller then takes the per-token path."""
     ops, P, H = eng.ops, eng.p, eng.H
@@ -71,9 +153,11 @@ def _decode_single_launch(eng, z, steps, want_logp):
     ops.gemm(z, P["grucell_g.weight_ih"][:, E_VOCAB:], rbg)
     tokens = torch.zeros(Bi, steps, dtype=torch.int32, device=z.device)
     logp = torch.empty(Bi, steps, E_VOCAB, device=z.device) if want_logp else None
+    # forced feedback (fn_decode_forced): the mask travels as device bytes, the kernel reads it step by step
+    fkw = {} if mask is None else dict(forced=forced, force=torch.tensor(mask, dtype=torch.uint8).to(z.device))
     ok = ops.decode_greedy(Bi, steps, H, E_VOCAB, E_VOCAB - 1, eng.whh_f["g"], P["grucell_g.bias_hh"], P["grucell_g.bias_ih"], eng.tab["g"], rbg, h0g,
                            eng.packs["ih2"], P["grucell_g_2.bias_ih"], eng.whh_f["g2"], P["grucell_g_2.bias_hh"], eng.packs["out"],
-                           P["linear_out_g.bias"], tokens, logp)
+                           P["linear_out_g.bias"], tokens, logp, **fkw)
     if not ok:
         return None
     if ops.gru_sync_error(clear=True):           # bounded spin gave up (another kernel held the CUs): results are garbage
@@ -83,7 +167,7 @@ def _decode_single_launch(eng, z, steps, want_logp):
     return logp, tokens
 
 
-def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None):
+def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, forced=None, mask=None):
     ops, P, H = eng.ops, eng.p, eng.H
     Bi = z.shape[0]
     dev = z.device
@@ -115,7 +199,10 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None):
             best.zero_()
         for i in range(steps):
             cur, prv = i & 1, (i & 1) ^ 1
-            tok_src = dict(idx_best=best[i - 1], best_v=E_VOCAB) if fused and i > 0 else dict(idx=tokens[:, i - 1] if i > 0 else None)
+            if mask is not None and i > 0 and mask[i - 1]:      # forced step: the previous token is a given one
+                tok_src = dict(idx=forced[:, i - 1])
+            else:
+                tok_src = dict(idx_best=best[i - 1], best_v=E_VOCAB) if fused and i > 0 else dict(idx=tokens[:, i - 1] if i > 0 else None)
             ops.gru_cell(h0g if i == 0 else hx0[prv][0], P["grucell_g.weight_hh"], P["grucell_g.bias_hh"], hx0[cur][0], b_ih=P["grucell_g.bias_ih"],
                          gx_table=eng.tab["g"], start_token=E_VOCAB - 1, gx_rowbias=rbg, **tok_src)
             ops.gru_cell(hx0[cur][0] if i == 0 else hx1[prv][0], P["grucell_g_2.weight_hh"], P["grucell_g_2.bias_hh"], hx1[cur][0],
@@ -132,7 +219,7 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None):
         cur, prv = i & 1, (i & 1) ^ 1
         ops.gru_seq_fwd([dict(B=Bi, T=1, H=H, w_hh_frag=eng.whh_f["g"], b_hh=P["grucell_g.bias_hh"], b_ih=P["grucell_g.bias_ih"],
                               h0=h0g if i == 0 else hx0[prv][0], h0_frag=None if i == 0 else hf0[prv], h_last_frag=hf0[cur],
-                              gx_table=eng.tab["g"], idx=tokens, idx_shift=i - 1,
+                              gx_table=eng.tab["g"], idx=forced if mask is not None and i > 0 and mask[i - 1] else tokens, idx_shift=i - 1,
                               start_token=E_VOCAB - 1, gx_rowbias=rbg, h_all=hx0[cur])], persistent=False)
         ops.gemm(hx0[cur][0], P["grucell_g_2.weight_ih"], gx2[0], bias=P["grucell_g_2.bias_ih"])
         ops.gru_seq_fwd([dict(B=Bi, T=1, H=H, w_hh_frag=eng.whh_f["g2"], b_hh=P["grucell_g_2.bias_hh"],
@@ -159,7 +246,7 @@ def clean_output(out):
 
 
 @torch.no_grad()
-def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set"):
+def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None):
     """Batched RhythmEvaluator.shift / NoteEvaluator.shift (test_class.py:233-254, :282-303) and the notebook's
     lambda*shift-vector transfer (cells 11 + 15): every (sample, fader value) pair is one row of ONE decode batch.
 
@@ -168,6 +255,7 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
       mode="shift": z_which += value * (mu_lookup[1] - mu_lookup[0]);  which="both" moves z_r and z_n together, as the notebook does
     eps: (eps_r, eps_n), each (n, Z) - one draw per sample, shared by its V values - or (n, V, Z) - one draw per (sample, value),
     which is what V separate reference calls consume; None = drawn here (r first, then n).
+    prompt: (P,) or (1, P) tokens every (sample, value) row starts with (continue_from), or None.
     Returns (tokens (n, V, steps) int32, z0 (n,) or (n, V): the value of z_which[:, 0] before the change; which="both": z_r's)."""
     if which not in ("r", "n", "both") or mode not in ("set", "shift") or (which == "both" and mode == "set"):
         raise ValueError("which in {r, n, both}, mode in {set, shift}; 'both' only with mode='shift'")
@@ -198,7 +286,11 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
                     tgt += vals.view(1, V, 1) * (lk.weight.data[1] - lk.weight.data[0]).view(1, 1, Z)
         c = chroma.float().to(dev).unsqueeze(1).expand(n, V, chroma.shape[-1])
         z = torch.cat([zr, zn, c], dim=2).reshape(n * V, -1)
-        _, tok = greedy_decode(model, z, steps, want_logp=False)
+        if prompt is None:
+            _, tok = greedy_decode(model, z, steps, want_logp=False)
+        else:
+            pr = (prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))).reshape(1, -1)
+            _, tok = continue_from(model, z, pr.expand(n * V, pr.shape[1]), steps, want_logp=False)
         return tok.view(n, V, steps), z0
     finally:
         model.train(was_training)

@@ -519,9 +519,11 @@ class Engine:
             self._sub_decoder_logits(sd, S["r"].shape[1], S["r"].shape[0])
         return sd
 
-    def forward(self, d, r, n, c, eps_r, eps_n, labels=None, save=True, head=True, sd_logits=True):
+    def forward(self, d, r, n, c, eps_r, eps_n, labels=None, save=True, head=True, sd_logits=True, dec_tokens=None):
         """Full training-mode forward up to logits; everything backward needs stays in named buffers (save=False: forward only,
-        the gate tensors are not written).  head=False: see global_decoder_tf; sd_logits=False: see decoders()."""
+        the gate tensors are not written).  head=False: see global_decoder_tf; sd_logits=False: see decoders().
+        dec_tokens: callable zc -> int32 [B][T], the token matrix the global decoder is FED instead of d (scheduled sampling: pass 1 decodes
+        it from zc); the encoders and the NLL targets keep d, the embedding gradient of decoder layer 1 gets a sort image of its own."""
         sort = None
         if save:
             # token sorts for the backward's segment sums (embed.hip): tiny kernels, side stream, beside the encoder scans
@@ -530,7 +532,12 @@ class Engine:
                 sort = {k: ops_sort(self, k, t, V) for k, t, V in (("d", d, E_VOCAB), ("r", r, R_DIMS), ("n", n, N_DIMS))}
         pre = self.encode(d, save)
         lat = self.latent(pre, {"r": eps_r, "n": eps_n}, labels)
-        dec = self.decoders(d, r, n, c, lat["r"]["z"], lat["n"]["z"], save, head, sd_logits)
+        d_dec = d
+        if dec_tokens is not None:
+            d_dec = dec_tokens(self.pack_zc(lat["r"]["z"], lat["n"]["z"], c))
+            if save:
+                sort["fed"] = ops_sort(self, "fed", d_dec, E_VOCAB)
+        dec = self.decoders(d_dec, r, n, c, lat["r"]["z"], lat["n"]["z"], save, head, sd_logits)
         self.main_wait_side()
         S = dict(d=d, r=r, n=n, c=c, eps={"r": eps_r, "n": eps_n}, labels=labels, pre=pre, lat=lat, dec=dec, sort=sort)
         self.saved = S if save else None
@@ -657,7 +664,8 @@ class Engine:
         self.colsum(rs2, G["grucell_g_2.bias_ih"])
         self._gru_weight_grads("g", "grucell_g.", "", T, B, dgx1, dghn1, dec["hx0"], dec["h0g"], G, sk_T, drb_g, rsn_g, lean=ln)
         dWg = G["grucell_g.weight_ih"]                          # [3H][E+ZG]: token columns = segment sums, written in place
-        ops.embed_grad_sorted(S["sort"]["d"], [dict(dgx=dgx1, out=dWg[:, :E_VOCAB], transposed=True, idx_shift=-1, start_token=E_VOCAB - 1)])
+        # (scheduled sampling: the decoder read the fed token matrix, whose sort image is its own; else the batch's)
+        ops.embed_grad_sorted(S["sort"].get("fed", S["sort"]["d"]), [dict(dgx=dgx1, out=dWg[:, :E_VOCAB], transposed=True, idx_shift=-1, start_token=E_VOCAB - 1)])
         ops.gemm(drb_g, dec["zc"], dWg[:, E_VOCAB:], a_k=False, b_k=False)
         self.colsum(drb_g, G["grucell_g.bias_ih"])
         ops.gemm(dh0_g, dec["zc"], G["linear_init_global.weight"], a_k=False, b_k=False)

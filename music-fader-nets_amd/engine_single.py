@@ -66,7 +66,8 @@ class SingleEncEngine(Engine):
         zc[:, Z:].copy_(cond)
         return zc
 
-    def forward(self, d, cond, eps, extra=None, save=True, head=True):
+    def forward(self, d, cond, eps, extra=None, save=True, head=True, dec_tokens=None):
+        """dec_tokens: see Engine.forward"""
         sort = None
         if save:
             self.side_wait_main()
@@ -74,7 +75,13 @@ class SingleEncEngine(Engine):
                 sort = {"d": ops_sort(self, "d", d, E_VOCAB)}
         enc = self.encode(d, extra, save)
         lat = self.latent1(enc["pre"], eps)
-        dec = self.global_decoder_tf(d, self.pack_zc(lat["z"], cond), save, head)
+        zc = self.pack_zc(lat["z"], cond)
+        d_dec = d
+        if dec_tokens is not None:
+            d_dec = dec_tokens(zc)
+            if save:
+                sort["fed"] = ops_sort(self, "fed", d_dec, E_VOCAB)
+        dec = self.global_decoder_tf(d_dec, zc, save, head)
         self.main_wait_side()
         S = dict(d=d, cond=cond, extra=extra, eps=eps, enc=enc, lat=lat, dec=dec, sort=sort)
         self.saved = S if save else None

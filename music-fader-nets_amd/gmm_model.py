@@ -27,7 +27,7 @@ class MusicAttrRegGMVAE(nn.Module):
         self.latent_dim = z_dims
         self.roll_dims = roll_dims
         self.hidden_dims = hidden_dims
-        self.eps = 100                   # teacher-forcing threshold: torch.rand(1) < 100 always (gmm_model.py:30,141)
+        self.eps = 100                   # teacher-forcing threshold: torch.rand(1) < 100 always (gmm_model.py:30,141); < 1: scheduled sampling
         self.sample = None
         # ---- parameter containers, in the construction order of gmm_model.py:33-71 -------------------
         self.gru_r = nn.GRU(roll_dims, hidden_dims, batch_first=True, bidirectional=True)
@@ -157,10 +157,43 @@ class MusicAttrRegGMVAE(nn.Module):
         (gmm_model.py:230,234-235) and, in train mode, T draws of torch.rand(1) in the decoder loop (:140)."""
         eps_r = torch.randn(B, self.latent_dim)
         eps_n = torch.randn(B, self.latent_dim)
-        if self.training:
-            for _ in range(T):
-                torch.rand(1)
+        self._rand_draws(T)
         return eps_r.to(device), eps_n.to(device)
+
+    # ------------------------------------------------------------------------------------------
+    # scheduled sampling (gmm_model.py:139-144: p = torch.rand(1); sample[:, i] if p < self.eps else _sampling(out)), self.eps < 1
+    # ------------------------------------------------------------------------------------------
+    _ss_draws = None                     # the decoder loop's rand(1) draws of the call being made (train mode)
+    _ss = None                           # its mask p_i < eps, or None: teacher forcing throughout (eps >= 1) / eval mode
+    fed = None                           # the token matrix the decoder was fed in the last scheduled-sampling call ...
+    sampled = None                       # ... and the model's own argmax tokens of that call's pass 1
+
+    def _rand_draws(self, T):
+        """the decoder loop's T draws of torch.rand(1) (:140), in the reference's order; kept, because they are the mask when eps < 1"""
+        self._ss_draws = [torch.rand(1) for _ in range(T)] if self.training else None
+
+    def _ss_mask(self, T):
+        """tuple of T bools `p_i < eps` from the draws made for this call (made here when the caller gave its own eps), or None"""
+        draws, self._ss_draws = self._ss_draws, None
+        if not self.training or self.eps >= 1:
+            return None
+        if draws is None or len(draws) != T:
+            draws = [torch.rand(1) for _ in range(T)]
+        return tuple(bool(p < self.eps) for p in draws)
+
+    def _dec_tokens(self, d, mask):
+        """pass 1 of a scheduled-sampling step: zc -> the token matrix the decoder is fed.  A forced decode with forced = d, tokens only, on
+        the current weights (fn_decode_forced / the per-token paths); fed[b][i] = d[b][i] where mask[i], else the model's own argmax of step i.
+        `_sampling` passes no gradient in the reference (:73-80), so pass 2 - the teacher-forced pipeline and its backward - runs over fed."""
+        if mask is None:
+            return None
+
+        def run(zc):
+            from .decode import fed_tokens, greedy_decode
+            _, tok = greedy_decode(self, zc, d.shape[1], want_logp=False, forced=d, force=mask)
+            self.sampled, self.fed = tok, fed_tokens(tok, d, mask).contiguous()
+            return self.fed
+        return run
 
     # ------------------------------------------------------------------------------------------
     # reference API
@@ -236,10 +269,13 @@ class MusicAttrRegGMVAE(nn.Module):
             d = self._indices(self.sample, self.roll_dims, ids_ndim=2)
             if d.shape[1] < steps or d.shape[0] != z.shape[0]:
                 raise IndexError("teacher forcing needs self.sample of shape (%d, >=%d, ...), got %s" % (z.shape[0], steps, tuple(self.sample.shape)))
-            for _ in range(steps):
-                torch.rand(1)
+            self._rand_draws(steps)
+            d = d[:, :steps].contiguous()
+            run = self._dec_tokens(d, self._ss_mask(steps))
+            if run is not None:
+                d = run(z.detach().float().contiguous())
             names, plist = self._named(_DecoderFunction.PREFIXES)
-            return _DecoderFunction.apply(self, names, d[:, :steps].contiguous(), z.float().contiguous(), *plist)
+            return _DecoderFunction.apply(self, names, d, z.float().contiguous(), *plist)
         return self._global_decoder_forward_only(z, steps)
 
     @torch.no_grad()
@@ -254,9 +290,11 @@ class MusicAttrRegGMVAE(nn.Module):
         d = self._indices(self.sample, self.roll_dims, ids_ndim=2)
         if d.shape[1] < steps or d.shape[0] != z.shape[0]:
             raise IndexError("teacher forcing needs self.sample of shape (%d, >=%d, ...), got %s" % (z.shape[0], steps, tuple(self.sample.shape)))
-        for _ in range(steps):
-            torch.rand(1)
+        self._rand_draws(steps)
         d = d[:, :steps].contiguous()
+        run = self._dec_tokens(d, self._ss_mask(steps))
+        if run is not None:
+            d = run(z.float().contiguous())
         dec = eng.global_decoder_tf(d, z.float().contiguous(), save=False)
         out = torch.empty(z.shape[0], steps, E_VOCAB, device=z.device)
         eng.ops.vocab_logsoftmax(dec["logits"], z.shape[0], steps, E_VOCAB, logp_bt=out)
@@ -305,6 +343,9 @@ class MusicAttrRegGMVAE(nn.Module):
         B, T = d.shape
         if eps is None:
             eps = self._draw_eps(B, T, d.device)
+        else:
+            self._ss_draws = None
+        self._ss = self._ss_mask(T)
         eps_r, eps_n = (e.float().contiguous() for e in eps)
         if not self.training or not torch.is_grad_enabled():
             res = self._forward_only(d, r, n, c, eps_r, eps_n)
@@ -334,7 +375,8 @@ class MusicAttrRegGMVAE(nn.Module):
         ops.time_logsoftmax(sd["n"]["logits"], logp_bt=n_out)
         zc = eng.pack_zc(z_r, z_n, c)
         if self.training:
-            dec = eng.global_decoder_tf(d, zc, save=False)
+            run = self._dec_tokens(d, self._ss)
+            dec = eng.global_decoder_tf(d if run is None else run(zc), zc, save=False)
             out = torch.empty(B, T, E_VOCAB, device=d.device)
             ops.vocab_logsoftmax(dec["logits"], B, T, E_VOCAB, logp_bt=out)
         else:
@@ -355,7 +397,7 @@ class _GMVAEFunction(torch.autograd.Function):
     def forward(ctx, model, names, d, r, n, c, eps_r, eps_n, *params):
         eng = model._engine
         ops = eng.ops
-        S = eng.forward(d, r, n, c, eps_r, eps_n)
+        S = eng.forward(d, r, n, c, eps_r, eps_n, dec_tokens=model._dec_tokens(d, model._ss))
         B, T = d.shape
         Tr = r.shape[1]
         dec, lat, pre = S["dec"], S["lat"], S["pre"]

@@ -452,8 +452,9 @@ class HipOps:
                                             _p(ws), wsb, self.stream()), "fn_gru_dwhh_f32")
 
     def decode_greedy(self, B, steps, H, V, start_token, w_hh1_frag, b_hh1, b_ih1, table1, rowbias1, h0, w_ih2_frag, b_ih2, w_hh2_frag, b_hh2,
-                      w_out_frag, b_out, tokens, logp=None):
-        """single-launch greedy decode of <= 2048 sequences (fn_decode_greedy); tokens int32 [B][>=steps], logp [B][steps][V] or None"""
+                      w_out_frag, b_out, tokens, logp=None, forced=None, force=None):
+        """single-launch greedy decode of <= 2048 sequences (fn_decode_greedy); tokens int32 [B][>=steps], logp [B][steps][V] or None.
+        forced int32 [B][>=steps] + force uint8 [steps] on the device: fn_decode_forced (forced[b][i] is fed after step i where force[i])"""
         d = _lib.FnDecode()
         for t, nm in ((w_hh1_frag, "w_hh1_frag"), (b_hh1, "b_hh1"), (b_ih1, "b_ih1"), (table1, "table1"), (rowbias1, "rowbias1"), (h0, "h0"),
                       (w_ih2_frag, "w_ih2_frag"), (b_ih2, "b_ih2"), (w_hh2_frag, "w_hh2_frag"), (b_hh2, "b_hh2"), (w_out_frag, "w_out_frag"),
@@ -470,10 +471,20 @@ class HipOps:
         if key not in syncs:
             syncs[key] = torch.zeros(int(self.lib.fn_decode_sync_ws_bytes()) // 4, dtype=torch.int32, device=self.device)
         d.sync_ws = _p(syncs[key])
-        rc = self.lib.fn_decode_greedy(C.byref(d), self.stream())
+        if forced is not None or force is not None:
+            if forced is None or force is None:
+                raise RuntimeError("decode_greedy: forced and force go together")
+            _dense(forced, torch.int32, "forced"), _dense(force, torch.uint8, "force")
+            if forced.shape[0] != B or forced.shape[1] < steps or force.numel() < steps:
+                raise RuntimeError("decode_greedy: forced [B][>=steps] and force [steps] expected")
+            f = _lib.FnDecodeForce()
+            f.forced, f.forced_ld, f.force = _p(forced), forced.shape[1], _p(force)
+            rc, what = self.lib.fn_decode_forced(C.byref(d), C.byref(f), self.stream()), "fn_decode_forced"
+        else:
+            rc, what = self.lib.fn_decode_greedy(C.byref(d), self.stream()), "fn_decode_greedy"
         if rc == _lib.FN_E_UNSUPPORTED:            # not eligible on this device (needs one CU per role workgroup)
             return False
-        _lib.check(rc, "fn_decode_greedy")
+        _lib.check(rc, what)
         return True
 
     def embed_grad(self, dgx_all, idx, idx_shift, start_token, reverse, V, out):

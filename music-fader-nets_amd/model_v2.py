@@ -60,9 +60,7 @@ class _SingleEncModel(MusicAttrRegGMVAE):
         """the reference's draws for one forward: eps, (subclass extras), T x rand(1) in train mode"""
         eps = torch.randn(B, self.latent_dim)
         extra = self._draw_extra(B)
-        if self.training:
-            for _ in range(T):
-                torch.rand(1)
+        self._rand_draws(T)
         return eps, extra
 
     def _draw_extra(self, B):
@@ -91,6 +89,7 @@ class _SingleEncModel(MusicAttrRegGMVAE):
         """encode -> z -> global decoder (teacher forced in train mode, greedy in eval mode) -> (out, dis, z_lat).  Train mode with autograd
         enabled: the outputs hang on ONE autograd node whose backward runs the HIP backward kernels (a reference-style
         ``loss.backward(); optimizer.step()`` loop works; call ``model.weights_changed()`` after the optimiser step)."""
+        self._ss = self._ss_mask(x.shape[1])          # scheduled sampling (self.eps < 1): gmm_model.MusicAttrRegGMVAE._dec_tokens
         if self.training and torch.is_grad_enabled():
             eng = self.engine()
             d = self._indices(x, self.roll_dims)
@@ -106,7 +105,7 @@ class _SingleEncModel(MusicAttrRegGMVAE):
         d = self._indices(x, self.roll_dims)
         B, T = d.shape
         Z = self.latent_dim
-        S = eng.forward(d, cond, eps, extra, save=False) if self.training else None
+        S = eng.forward(d, cond, eps, extra, save=False, dec_tokens=self._dec_tokens(d, self._ss)) if self.training else None
         if self.training:
             out = torch.empty(B, T, E_VOCAB, device=d.device)
             eng.ops.vocab_logsoftmax(S["dec"]["logits"], B, T, E_VOCAB, logp_bt=out)
@@ -149,6 +148,8 @@ class MusicAttrSingleVAE(_SingleEncModel):
         B, T = x.shape[0], x.shape[1]
         if eps is None:
             eps, _ = self._draw(B, T)
+        else:
+            self._ss_draws = None
         c = chroma.float().contiguous().to(dev)
         out, dis, z = self._forward_core(x, c, None, eps.float().contiguous().to(dev))
         return out, dis, torch.cat([z, c], dim=1)
@@ -190,6 +191,8 @@ class MusicAttrCVAE(_SingleEncModel):
         dev = self._device()
         if eps is None:
             eps, _ = self._draw(x.shape[0], x.shape[1])
+        else:
+            self._ss_draws = None
         dens = self._dens(r_density, n_density)
         out, dis, z = self._forward_core(x, dens, dens, eps.float().contiguous().to(dev))
         return out, dis, torch.cat([z, dens], dim=-1)
@@ -266,8 +269,10 @@ class MusicAttrFaderNets(_SingleEncModel):
         dev = self._device()
         if eps is None:
             eps, mask = self._draw(x.shape[0], x.shape[1])
-        elif mask is None:
-            mask = torch.ones(x.shape[0], 2)
+        else:
+            self._ss_draws = None
+            if mask is None:
+                mask = torch.ones(x.shape[0], 2)
         dens = self._dens(r_density, n_density)
         out, dis, z = self._forward_core(x, dens, None, eps.float().contiguous().to(dev))
         r_out, n_out = self.adversarial_heads(z, mask, dens)
@@ -286,7 +291,7 @@ class _SingleEncFunction(torch.autograd.Function):
         eng = model._engine
         B, T = d.shape
         Z = eng.Z
-        S = eng.forward(d, cond, eps, extra, save=True)
+        S = eng.forward(d, cond, eps, extra, save=True, dec_tokens=model._dec_tokens(d, model._ss))
         out = torch.empty(B, T, E_VOCAB, device=d.device)
         eng.ops.vocab_logsoftmax(S["dec"]["logits"], B, T, E_VOCAB, logp_bt=out)
         ctx.model, ctx.names, ctx.fw_id = model, names, id(S)

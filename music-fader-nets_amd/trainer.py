@@ -137,7 +137,15 @@ class GMVAETrainer:
         lo = self.dist.rank * B
         return tuple(e[lo:lo + B].contiguous() for e in self.model._draw_eps(B * self.dist.world, T, dev))
 
+    def _check_eps(self):
+        """the fused step captures ONE fixed schedule (teacher forcing at every decoder step); scheduled sampling is a per-step random choice"""
+        if self.model.eps < 1:
+            raise NotImplementedError("%s: scheduled sampling (model.eps = %g < 1, gmm_model.py:139-144) is not wired into the fused training "
+                                      "step; train through the drop-in path - out = model(...), a reference-style loss, loss.backward(), "
+                                      "optimizer.step(), model.weights_changed() - or set model.eps >= 1" % (type(self).__name__, self.model.eps))
+
     def _forward_losses(self, step, batch, eps, want_grads):
+        self._check_eps()
         m = self.model
         eng = m.engine()
         ops = eng.ops

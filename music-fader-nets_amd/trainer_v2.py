@@ -53,6 +53,7 @@ class _SingleEncTrainer(GMVAETrainer):
 
     # ---------------------------------------------------------------------------------------------
     def _forward_losses(self, step, batch, eps, want_grads):
+        self._check_eps()
         m = self.model
         eng = m.engine()
         ops = eng.ops
@@ -398,6 +399,7 @@ class GLSRTrainer(GMVAETrainer):
         return lat_up
 
     def _forward_losses(self, step, batch, eps, want_grads):
+        self._check_eps()
         self._cur_eps = eps
         # The regulariser runs four more decoder passes (weight-stationary, whole-chip launches that spin on each other's progress).  On the
         # side lane they would be in flight together with the main pass's decoder backward on the main stream: two such grids of 256

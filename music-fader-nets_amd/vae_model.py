@@ -88,6 +88,9 @@ class MusicAttrRegVAE(MusicAttrRegGMVAE):
         B, T = d.shape
         if eps is None:
             eps = self._draw_eps(B, T, d.device)     # Normal(0,1).sample(size) consumes the generator like randn (model_v2.py:152-154)
+        else:
+            self._ss_draws = None
+        self._ss = self._ss_mask(T)
         eps_r, eps_n = (e.float().contiguous() for e in eps)
         names = [k for k, _ in self.used_parameters()]
         plist = [p for _, p in self.used_parameters()]
