@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static check of the generated K-loop statements (kloop2_asm.h, kloop3_asm.h, kloop4_asm.h): the hand-counted `s_waitcnt vmcnt(n)` against the ISSUE order of
+"""Static check of the generated K-loop statements (kloop_asm.h, kloop2_asm.h, kloop3_asm.h, kloop4_asm.h): the hand-counted `s_waitcnt vmcnt(n)` against the ISSUE order of
 the statement's memory operations (vector memory operations retire in order on this counter).
 
   1. arrival: the wait in front of an `s_barrier` must leave at most as many operations outstanding as were issued BEHIND the last exchange-slab store
@@ -7,13 +7,17 @@ the statement's memory operations (vector memory operations retire in order on t
   2. operands: when an MFMA (or a ds_write / store that reads registers) is issued, no load that is still allowed to be outstanding may have one of its source
      registers as destination.  The loads in flight when a `*_main` / `*_first` statement starts are those of the family's `*_pro` statement (the
      ring request), in that order - for the bf16 x 6 backward followed by the `*_out` stores of the last epilogue; both paths behind the counter check are walked.
+     A `fn_kloop_*` statement (kloop_asm.h) requests its ring itself, in its prologue: it is walked from an empty queue.
+
+It reads header text only and shares nothing with the generators (kloop_common.py has THEIR model of the queue): a checker that imports the model it
+checks proves nothing.
 
 Round 5: check 1 found fn_rs_bwd_t1_main and fn_pp_bwd_k768_main one operation too lenient (the generator listed a unit's operations in the order it
 appended them, not in the order of their MFMA slots).  A real defect, fixed in the generator - but NOT the cause of the rare wrong 16 x 32 patch of eager
 training steps that was being hunted then (the rate was unchanged with the fix: profiles/r05_eager_nondeterminism.txt; that one is handled by
 gru_bwd_rs_kernel claiming the whole register file, gru_persist.hip).
 
-usage: check_kloops.py kloop2_asm.h [...]     exit status 1 on a finding
+usage: check_kloops.py kloop_asm.h kloop2_asm.h [...]     exit status 1 on a finding
 """
 import re
 import sys
@@ -134,6 +138,8 @@ def main(paths):
                 if name.endswith("_main") and fam + "_out" in st:        # kloop4: the dgx / dghn stores of the last epilogue leave behind the ring request
                     start += [None for l in st[fam + "_out"] if l.startswith("global_store")]
                 findings += walk(name, lines, start)
+            elif name.startswith("fn_kloop_"):
+                findings += walk(name, lines, [])
     for f in findings:
         print(f)
     print("%d statements of %d files checked, %d findings" % (sum(len(statements(p)) for p in paths), len(paths), len(findings)))

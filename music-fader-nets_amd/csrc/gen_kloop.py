@@ -28,7 +28,7 @@ Scalars: s[SB:SB+1] = operand base.
 """
 import sys
 
-SB = 84          # scalar temporaries s84..s85 (clobbered)
+from kloop_common import SB, Slots, VmQueue, advance, clobber, rng, statement
 
 
 class Gen:
@@ -79,39 +79,30 @@ class Gen:
                     a = self.ring(slot, m) + jj
                     b = (self.wf(bs, x) if self.fwd else self.wf(bs, 0)) + jj
                     c = self.acc(m, x)
-                    out.append("v_mfma_f32_16x16x4_f32 a[%d:%d], a%d, a%d, a[%d:%d]" % (c, c + 3, a, b, c, c + 3))
+                    out.append("v_mfma_f32_16x16x4_f32 %s, a%d, a%d, %s" % (rng(c), a, b, rng(c)))
         return out
 
-    # ---- stream state: s_rel = what s[SB:SB+1] points at relative to the first unit of the current group; vmops = issue order
+    # ---- stream state: s_rel = what s[SB:SB+1] points at relative to the first unit of the current group; self.q = issue order
     def advance_to(self, need_rel):
         out = []
         while need_rel - self.s_rel > 3072:
-            out += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1)]
+            out += advance()
             self.s_rel += 4096
         assert 0 <= need_rel - self.s_rel <= 3072, (need_rel, self.s_rel)
         return out
 
-    def gload(self, unit_abs, slot, m, need_rel):
+    def gload(self, slot, m, need_rel):
         imm = need_rel - self.s_rel
         assert 0 <= imm <= 4095
-        r = self.ring(slot, m)
-        self.vmops.append(("ring", unit_abs))
-        return "global_load_dwordx4 a[%d:%d], %%[vo%d], s[%d:%d] offset:%d sc1" % (r, r + 3, m, SB, SB + 1, imm)
-
-    def wait_unit(self, unit_abs):
-        last = max(i for i, o in enumerate(self.vmops) if o == ("ring", unit_abs))
-        n = len(self.vmops) - 1 - last
-        assert n < 64
-        return "s_waitcnt vmcnt(%d)" % n
+        return "global_load_dwordx4 %s, %%[vo%d], s[%d:%d] offset:%d sc1" % (rng(self.ring(slot, m)), m, SB, SB + 1, imm)
 
     def wread(self, bs, n, unit_in_group):
-        r = self.wf(bs, n)
         if self.fwd:      # wl[3][nk][2][64][4] floats, gate stride 32 KB at H = 512: gates 0, 1 off %[lp], gate 2 off %[lq] = lp + 64 KB
             ptr, off = ("%[lp]", n * 32768 + unit_in_group * 1024) if n < 2 else ("%[lq]", unit_in_group * 1024)
         else:
             ptr, off = "%[lp]", unit_in_group * 1024
         assert off < 65536
-        return "ds_read_b128 a[%d:%d], %s offset:%d" % (r, r + 3, ptr, off)
+        return "ds_read_b128 %s, %s offset:%d" % (rng(self.wf(bs, n)), ptr, off)
 
     def group(self, g, final):
         """text of group g (units g*RU .. g*RU+RU-1); final: nothing behind it"""
@@ -129,20 +120,16 @@ class Gen:
             if refill:
                 assert not self.advance_to((k + RU - 1) * 1024), "the scalar base must have been advanced in the previous unit"
             extra_here = self.extra_units.get(u, [])
-            out.append(self.wait_unit(u))
+            out.append(self.q.wait_for(("ring", u)))
             out.append("s_waitcnt lgkmcnt(0)")
-            companions = []                   # per MFMA: the instructions issued right behind it
+            slots = Slots(self.nmf)
             for t in range(self.nmf):
-                c = []
                 if refill and t in gslots:
-                    c.append(self.gload(u + RU - 1, (k - 1) % RU, gslots.index(t), (k + RU - 1) * 1024))
+                    slots.put(t, self.gload((k - 1) % RU, gslots.index(t), (k + RU - 1) * 1024), ("ring", u + RU - 1))
                 if wnext and t in wslots:
-                    c.append(self.wread((k + 1) & 1, wslots.index(t), k + 1))
+                    slots.put(t, self.wread((k + 1) & 1, wslots.index(t), k + 1))
                 if t in extra_here and self.pending_extras:
-                    c.append(self.pending_extras.pop(0))
-                    self.vmops.append(("extra", 0))
-                    if t == self.nmf - 2: c.append("s_nop 0")
-                companions.append(c)
+                    slots.put(t, [self.pending_extras.pop(0)] + (["s_nop 0"] if t == self.nmf - 2 else []), ("extra", 0))
             # bookkeeping for the next unit / group: one instruction (or one s_add / s_addc pair) per free MFMA gap from t_tail on
             tail = []
             if (not final) and k + 1 < RU:
@@ -153,14 +140,7 @@ class Gen:
                 tail.append("v_add_u32 %%[lp], 0x%x, %%[lp]" % (RU * 1024))
                 if self.fwd:
                     tail.append("v_add_u32 %%[lq], 0x%x, %%[lq]" % (RU * 1024))
-            for t, ins in enumerate(self.mfmas(k, k & 1)):
-                out.append(ins)
-                out += companions[t]
-                if t >= t_tail and tail and (not companions[t] or t == self.nmf - 1):
-                    out.append(tail.pop(0))
-                    if tail and tail[0].startswith("s_addc"):
-                        out.append(tail.pop(0))
-            out += tail
+            out += self.q.unit(self.mfmas(k, k & 1), slots, tail, t_tail)
         if not final:
             self.s_rel -= RU * 1024
         return out
@@ -168,7 +148,7 @@ class Gen:
     def stream(self, G):
         """(prologue, [group texts]) of a step with G groups"""
         RU = self.RU
-        self.vmops, self.s_rel = [], 0
+        self.q, self.s_rel = VmQueue(), 0        # the prologue is part of the statement: nothing is in flight when it begins
         self.pending_extras = list(self.extras)
         pro = ["s_mov_b64 s[%d:%d], %%[xin]" % (SB, SB + 1), "s_nop 4"]
         for n in range(self.NB):
@@ -177,10 +157,11 @@ class Gen:
             adv = self.advance_to(u * 1024)
             pro += adv + (["s_nop 4"] if adv else [])        # SALU write of the base -> VMEM read of it
             for m in range(2):
-                pro.append(self.gload(u, u, m, u * 1024))
+                pro.append(self.gload(u, m, u * 1024))
+                self.q.issue(("ring", u))
         start_rel = (RU - 1) * 1024 - 3072
         while self.s_rel < start_rel:
-            pro += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1)]
+            pro += advance()
             self.s_rel += 4096
         assert self.s_rel == start_rel
         for c in range(24 if self.fwd else 16):
@@ -200,21 +181,16 @@ class Gen:
         if self.fwd:
             for m in range(2):
                 for n in range(3):
-                    c = self.acc(m, n)
-                    L.append("ds_write_b128 %%[red], a[%d:%d] offset:%d" % (c, c + 3, (m * 3 + n) * 1088))
+                    L.append("ds_write_b128 %%[red], %s offset:%d" % (rng(self.acc(m, n)), (m * 3 + n) * 1088))
         else:
             # the two k-parity accumulators of a row tile go to two planes of 8 tiles (WK x EM = 8 in both tilings); the epilogue adds them
             for m in range(2):
                 for par in range(2):
-                    c = self.acc(m, par)
-                    L.append("ds_write_b128 %%[red], a[%d:%d] offset:%d" % (c, c + 3, m * 1088 + par * 8 * 1088))
+                    L.append("ds_write_b128 %%[red], %s offset:%d" % (rng(self.acc(m, par)), m * 1088 + par * 8 * 1088))
         L.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
         return L
 
     def emit(self):
-        L = self.build()
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
-        clob = ", ".join('"a%d"' % i for i in range(self.nagpr))
         if self.fwd:
             sig = ("const float* xin_, unsigned vo0, unsigned vo1, unsigned lp, unsigned lq, unsigned red,\n"
                    "                                 const float* xa0, const float* xa1, f32x4 (&ex)[2][3]")
@@ -233,24 +209,16 @@ class Gen:
             io = '[lp] "+v"(lp)'
             doc = ("ga / ha / xa = per-lane addresses of epilogue item 0 / 1: saved gates (r; z, n, hn follow 1 KB apart), previous state, external\n"
                    "// gradient; gt / hp / xt receive them")
-        return """
-// %s K loop of one time step: xin = this wave's first operand unit (uniform), vo0 / vo1 = byte offsets of its two row tiles (+ lane * 16),
+        comment = """// %s K loop of one time step: xin = this wave's first operand unit (uniform), vo0 / vo1 = byte offsets of its two row tiles (+ lane * 16),
 // lp%s = LDS byte address of its first weight-fragment unit (+ lane * 16), %d K units (groups of %d), red = LDS byte address of its
 // accumulator tiles; %s.
-// %d MFMAs per unit; %d AGPRs.  Everything requested here has landed when the statement ends.
-FN_DEVINL void %s(%s) {
-    // wave-uniform by construction (the K range depends on the wave id only); the compiler cannot see that
-    const unsigned long long xq = (unsigned long long)(uintptr_t)xin_;
-    const float* xin = reinterpret_cast<const float*>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(xq >> 32)) << 32) |
-                                                                  (unsigned)__builtin_amdgcn_readfirstlane((int)(xq & 0xffffffffull))));
-    asm volatile(
-%s
-        : %s, %s
-        : [xin] "s"(xin), [vo0] "v"(vo0), [vo1] "v"(vo1), [red] "v"(red), %s
-        : "memory", "scc", "s%d", "s%d", %s);
-}
-""" % ("forward" if self.fwd else "backward", " / lq" if self.fwd else "", self.G * self.RU, self.RU, doc, self.nmf, self.nagpr, self.name, sig,
-       body, io, outs, ins, SB, SB + 1, clob)
+// %d MFMAs per unit; %d AGPRs.  Everything requested here has landed when the statement ends.""" % (
+            "forward" if self.fwd else "backward", " / lq" if self.fwd else "", self.G * self.RU, self.RU, doc, self.nmf, self.nagpr)
+        pre = ["// wave-uniform by construction (the K range depends on the wave id only); the compiler cannot see that",
+               "const float* xin = fn_uniform_ptr(xin_);"]
+        return statement(comment, self.name, sig, pre, self.build(), io + ", " + outs,
+                         '[xin] "s"(xin), [vo0] "v"(vo0), [vo1] "v"(vo1), [red] "v"(red), ' + ins,
+                         ['"memory"', '"scc"'] + clobber("s", (SB, SB + 1)) + clobber("a", range(self.nagpr)))
 
 
 def main(path):

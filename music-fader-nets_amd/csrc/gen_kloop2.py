@@ -29,16 +29,10 @@ Pipeline unit = 16 K values of ONE row tile: 1 operand load (1 KB), NB weight-fr
 Register maps (a = AGPR):  acc a[0..nacc), ring[slot] a[nacc + 4 slot ..], wfrag[bs][n] a[w0 + 4 (NB bs + n) ..].  Scalars s84..s87,
 temporaries v200, v201 (backward).
 """
-import os
 import sys
 
-# Experiment switches (KLOOP2_* environment variables, used by scratch/ variant scripts only) change wait counts / hints of the generated statements: a
-# production build must not pick up a stray one.  They are honoured only when KLOOP_EXPERIMENT=1 is set with them; otherwise the generator refuses.
-_stray = sorted(k for k in os.environ if k.startswith("KLOOP2_"))
-if _stray and os.environ.get("KLOOP_EXPERIMENT") != "1":
-    sys.exit("gen_kloop2.py: experiment switches %s are set without KLOOP_EXPERIMENT=1 - refusing to generate a production header" % ", ".join(_stray))
+from kloop_common import SB, Slots, VmQueue, advance, clobber, lanes32, rng, statement
 
-SB = 84          # s84:85 = running operand base, s86:87 = saved exec / scratch
 TV = 200         # v200, v201: address temporaries of the backward slab stores
 
 
@@ -47,6 +41,7 @@ class Gen:
         self.name, self.fwd, self.units, self.RU, self.stores, self.masked = name, fwd, units, RU, stores, masked
         assert units % RU == 0 and RU % 2 == 0
         self.G = units // RU
+        self.TH = 1                                # row tiles per unit = operand loads per unit
         self.NB = 3 if fwd else 1
         self.nmf = 12 if fwd else 4
         self.nacc = 12 if fwd else 8
@@ -76,109 +71,81 @@ class Gen:
                        ("out", ["global_store_dwordx4 %[sg], %[d0], off offset:-2048"]), ("out", ["global_store_dwordx4 %[sg], %[d1], off"]),
                        ("out", ["global_store_dwordx4 %[sg], %[d2], off offset:2048"]), ("out", ["global_store_dwordx4 %[sn], %[d3], off"])]
 
-    def ring(self, slot):
-        return self.ring0 + 4 * slot
+    def ring(self, slot, m=0):
+        return self.ring0 + 4 * (self.TH * slot + m)
+
+    def vreg(self, m, y=False):
+        """offset register of row tile m of this phase / (y) of the next one"""
+        return ("%[voy]" if y else "%[vo]") if m == 0 else "v%d" % (TV + 3 if y else TV + 2)
 
     def refill_ins(self, slot, imm):
         """(MFMA gap, instruction) pairs that re-fill ring slot `slot` from byte offset imm off the running base"""
-        r = self.ring(slot)
-        return [(0, "global_load_dwordx4 a[%d:%d], %%[vo], s[%d:%d] offset:%d sc1" % (r, r + 3, SB, SB + 1, imm))]
+        return [(4 * m, "global_load_dwordx4 %s, %s, s[%d:%d] offset:%d sc1" % (rng(self.ring(slot, m)), self.vreg(m), SB, SB + 1, imm)) for m in range(self.TH)]
 
     def next_ring_ins(self, slot, off):
-        r = self.ring(slot)
-        return ["global_load_dwordx4 a[%d:%d], %%[voy], s[%d:%d] offset:%d sc1" % (r, r + 3, SB, SB + 1, off)]
+        return ["global_load_dwordx4 %s, %s, s[%d:%d] offset:%d sc1" % (rng(self.ring(slot, m)), self.vreg(m, True), SB, SB + 1, off) for m in range(self.TH)]
 
     def wf(self, bs, n):
         return self.w0 + 4 * (self.NB * bs + n)
 
-    def mfmas_u(self, slot, bs, u):
-        return self.mfmas(slot, bs)
-
-    def mfmas(self, slot, bs):
+    def mfmas(self, slot, bs, u):
+        """u = the unit inside this wave's K range (the LDS-fed loops do not need it)"""
         out = []
         for jj in range(4):
             for x in (range(3) if self.fwd else [jj & 1]):
                 a = self.ring(slot) + jj
                 b = (self.wf(bs, x) if self.fwd else self.wf(bs, 0)) + jj
-                c = 4 * x
-                out.append("v_mfma_f32_16x16x4_f32 a[%d:%d], a%d, a%d, a[%d:%d]" % (c, c + 3, a, b, c, c + 3))
+                out.append("v_mfma_f32_16x16x4_f32 %s, a%d, a%d, %s" % (rng(4 * x), a, b, rng(4 * x)))
         return out
 
     # ---- ring request of a phase: units 0 .. RU-2 into slots 0 .. RU-2 off the scalar base in s[SB:SB+1] (clobbered), + weight fragments of unit 0
-    def request(self, xin, vo):
-        L = ["s_mov_b64 s[%d:%d], %s" % (SB, SB + 1, xin), "s_nop 4"]
+    def request(self):
+        L = ["s_mov_b64 s[%d:%d], %%[xin]" % (SB, SB + 1), "s_nop 4"]
         rel = 0
         for u in range(self.RU - 1):
             while u * 1024 - rel > 4095:
-                L += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1), "s_nop 4"]
+                L += advance(nop=True)
                 rel += 4096
-            r = self.ring(u)
-            L.append("global_load_dwordx4 a[%d:%d], %s, s[%d:%d] offset:%d sc1" % (r, r + 3, vo, SB, SB + 1, u * 1024 - rel))
+            for m in range(self.TH):
+                L.append("global_load_dwordx4 %s, %s, s[%d:%d] offset:%d sc1" % (rng(self.ring(u, m)), self.vreg(m), SB, SB + 1, u * 1024 - rel))
         for n in range(self.NB):
             L.append(self.wread_at(0, n, 0))
         return L
 
     def wread_at(self, bs, n, unit):
         """weight fragments of K unit `unit` (absolute inside this wave's K range); no pointer is ever advanced"""
-        r = self.wf(bs, n)
         if self.fwd:      # wl[3][nk][2][64][4] floats, gate stride 32 KB at H = 512: gates 0, 1 off lp, gate 2 off lq = lp + 64 KB
             ptr, off = ("%[lp]", n * 32768 + unit * 1024) if n < 2 else ("%[lq]", unit * 1024)
         else:             # wl[nk3][2][64][4]: units 0-47 off lp, 48-95 off lq = lp + 48 KB
             ptr, off = ("%[lp]", unit * 1024) if unit < 48 else ("%[lq]", (unit - 48) * 1024)
         assert 0 <= off < 65536
-        return "ds_read_b128 a[%d:%d], %s offset:%d" % (r, r + 3, ptr, off)
+        return "ds_read_b128 %s, %s offset:%d" % (rng(self.wf(bs, n)), ptr, off)
 
     def advance_to(self, need_rel):
         out = []
         while need_rel - self.s_rel > 3072:
-            out += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1)]
+            out += advance()
             self.s_rel += 4096
         assert 0 <= need_rel - self.s_rel <= 3072, (need_rel, self.s_rel)
         return out
 
-    def wait_unit(self, unit_abs):
-        last = max(i for i, o in enumerate(self.vmops) if o == ("ring", unit_abs))
-        n = len(self.vmops) - 1 - last
-        assert n < 60, n
-        if os.environ.get("KLOOP2_RING0") == "1":        # experiment (round 5): every ring wait drains the counter
-            n = 0
-        if os.environ.get("KLOOP2_RING0_RANGE"):         # experiment: only the waits of units lo..hi (inside this wave's K range) drain it
-            lo, hi = (int(x) for x in os.environ["KLOOP2_RING0_RANGE"].split("-"))
-            if lo <= unit_abs <= hi:
-                n = 0
-        if os.environ.get("KLOOP2_NOSTORE") == "1":      # experiment (round 5): younger STORES are not assumed to stay behind the ring load (loads only)
-            n = sum(1 for o in self.vmops[last + 1:] if o[0] != "store")
-        if os.environ.get("KLOOP2_NOEXTRA") == "1":      # experiment (round 5): neither are the plain (non-sc1) loads of the epilogue operands
-            n = sum(1 for o in self.vmops[last + 1:] if o[0] != "extra")
-        return "s_waitcnt vmcnt(%d)" % n
-
     def arrive_block(self):
         """the slab stores of the previous epilogue (or, without stores, everything older than this statement) have completed in every
         wave -> one arrival (arr: 0 = none due, 1 = due, 2 = due and this wave issues it)"""
-        slab = [i for i, o in enumerate(self.vmops) if o == ("store", "slab")]
-        n = (len(self.vmops) - 1 - max(slab)) if slab else (len(self.vmops) - self.n0)
-        if os.environ.get("KLOOP2_ARR0") == "1":         # experiment (round 5): the arrival waits for everything in flight
-            n = 0
-        return ["s_cmp_eq_u32 %[arr], 0", "s_cbranch_scc1 .Lnoarr_%=", "s_waitcnt vmcnt(%d)" % n, "s_barrier",
+        return ["s_cmp_eq_u32 %[arr], 0", "s_cbranch_scc1 .Lnoarr_%=", self.q.wait_slab_store(), "s_barrier",
                 "s_cmp_lt_u32 %[arr], 2", "s_cbranch_scc1 .Lnoarr_%=",
                 "s_mov_b64 s[%d:%d], exec" % (SB + 2, SB + 3), "s_mov_b64 exec, 1", "v_mov_b32 %[pv], 1",
                 "global_atomic_add %[acnt], %[pv], off", "s_mov_b64 exec, s[%d:%d]" % (SB + 2, SB + 3), ".Lnoarr_%=:"]
 
-    def store_ins(self, ins):
-        if not self.masked:
-            return ins
-        return ["s_mov_b64 s[%d:%d], exec" % (SB + 2, SB + 3), "s_mov_b64 exec, 0xffffffff"] + ins + ["s_mov_b64 exec, s[%d:%d]" % (SB + 2, SB + 3)]
-
     def body(self):
         RU, G = self.RU, self.G
         assert G >= 2
-        self.vmops = [("ring", u) for u in range(RU - 1) for _ in range(getattr(self, "TH", 1))]      # in flight when the statement starts: the ring request and nothing else
-        self.n0 = len(self.vmops)
+        self.q = VmQueue(("ring", u) for u in range(RU - 1) for _ in range(self.TH))      # in flight when the statement starts: the ring request and nothing else
         self.s_rel = 0
         L = ["s_mov_b64 s[%d:%d], %%[xin]" % (SB, SB + 1)]
         start_rel = (RU - 1) * 1024 - 3072
         while self.s_rel < start_rel:
-            L += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1)]
+            L += advance()
             self.s_rel += 4096
         assert self.s_rel == start_rel
         for c in range(self.nacc):
@@ -204,25 +171,17 @@ class Gen:
             refill = (not final) or k == 0
             wnext = (not final) or k < RU - 1
             if path is None:
-                out.append(self.wait_unit(u))
-                if os.environ.get("KLOOP2_NOP"):             # experiment (round 5): wait states between the counted wait and the first MFMA that reads the ring slot
-                    out.append("s_nop %d" % (int(os.environ["KLOOP2_NOP"]) - 1))
+                out.append(self.q.wait_for(("ring", u)))
             out.append("s_waitcnt lgkmcnt(0)")
-            comp = [[] for _ in range(self.nmf)]
-            issued = []            # (MFMA slot, order inside the slot, what) of this unit's memory operations: self.vmops must list them in ISSUE order -
-            # an epilogue-operand load sits in an earlier slot than the store of the same unit, and the arrival's wait counts the operations BEHIND
-            # the last slab store (round 5: listed in append order, that wait of fn_rs_bwd_t1_main / fn_pp_bwd_k768_main was one too lenient - the
-            # last slab store could still be in flight when the arrival was posted)
+            gaps = Slots(self.nmf)      # an epilogue-operand load sits in an earlier slot than the store of the same unit: the queue lists them in slot order
             if refill:
                 imm = (k + RU - 1) * 1024 - self.s_rel
                 assert 0 <= imm <= 4095
                 for t_, ins_ in self.refill_ins((k - 1) % RU, imm):
-                    comp[t_].append(ins_)
-                    issued.append((t_, len(issued), ("ring", u + RU - 1)))
+                    gaps.put(t_, ins_, ("ring", u + RU - 1))
             if final and k == 0:
                 # the last refill is out: the counter of the NEXT phase's half, looked at KC units later
-                comp[1].append("global_load_dword %[pv], %[pcnt], off sc1")
-                issued.append((1, len(issued), ("poll", 0)))
+                gaps.put(1, "global_load_dword %[pv], %[pcnt], off sc1", ("poll", 0))
             if path == "R":
                 # ring of the next phase: slot s is free once unit u0 + s has been multiplied.  Unit KC + 1 requests slots 0 .. KC, every later one its predecessor's
                 slots = list(range(0, KC + 1)) if k == KC + 1 else [k - 1]
@@ -233,34 +192,23 @@ class Gen:
                         continue
                     assert -4096 <= sl * 1024 - self.y_rel <= 4095
                     for ins_ in self.next_ring_ins(sl, sl * 1024 - self.y_rel):
-                        comp[ts[n_ % len(ts)]].append(ins_)
+                        gaps.put(ts[n_ % len(ts)], ins_)
                         n_ += 1
             if stores and path is None and not final:                 # one store of the previous epilogue per unit, the exchange slab first
                 kind, ins = stores.pop(0)
-                comp[t_store] += self.store_ins(ins)
-                issued.append((t_store, len(issued), ("store", kind)))
+                gaps.put(t_store, lanes32(ins, self.masked), ("store", kind))
             if wnext:
                 for n, t in enumerate(wslots):
-                    comp[t].append(self.wread_at((k + 1) & 1, n, u + 1))
+                    gaps.put(t, self.wread_at((k + 1) & 1, n, u + 1))
             if u in extra_units:
-                comp[t_extra].append(pending.pop(0))
-                issued.append((t_extra, len(issued), ("extra", 0)))
+                gaps.put(t_extra, pending.pop(0), ("extra", 0))
             tail = []
             if (not final) and k + 1 < RU:
                 tail += self.advance_to((k + 1 + RU - 1) * 1024)
             if k == RU - 1 and not final:
                 tail += self.advance_to(RU * 1024 + start_rel + 3072)
                 assert self.s_rel == RU * 1024 + start_rel
-            t_tail = self.t_tail
-            for t, ins in enumerate(self.mfmas_u(k, k & 1, u)):
-                out.append(ins)
-                out += comp[t]
-                if t >= t_tail and tail and (not comp[t] or t == self.nmf - 1):
-                    out.append(tail.pop(0))
-                    if tail and tail[0].startswith("s_addc"):
-                        out.append(tail.pop(0))
-            out += tail
-            self.vmops += [e for _, _, e in sorted(issued)]
+            out += self.q.unit(self.mfmas(k, k & 1, u), gaps, tail, self.t_tail)
             if u == u_arr:
                 out += self.arrive_block()
             return out
@@ -282,7 +230,7 @@ class Gen:
             # scalar base of the next phase's operands: advance in 4 KB steps so that slot offsets stay below 4096
             need = (k - 1) * 1024
             if need - self.y_rel > 3072:
-                L += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1), "s_nop 4"]
+                L += advance(nop=True)
                 self.y_rel += 4096
                 # slots requested by unit KC + 1 below the new base were issued before the advance (they are at offsets < 4096 of the old base)
             L += unit(G - 1, k, "R")
@@ -292,25 +240,43 @@ class Gen:
         L += [".Ldone_%=:"]
         for n in range(self.NB):          # weight fragments of the next phase's unit 0 (the same slice for both halves)
             L.append(self.wread_at(0, n, 0))
-        L += ["s_nop 15"] * int(os.environ.get("KLOOP2_ENDNOP", "1"))      # (experiment switch, round 5: more wait states in front of the accumulator hand-over)
         # accumulators -> LDS (padded MFMA C layout); an MFMA result needs 12 wait states before anything but an accumulating MFMA reads it
-        L += self.acc_writes()
+        L += ["s_nop 15"] + self.acc_writes()
         L.append("s_waitcnt lgkmcnt(0)")
         return L
 
     def acc_writes(self):
         if self.fwd:
-            return ["ds_write_b128 %%[red], a[%d:%d] offset:%d" % (4 * n, 4 * n + 3, n * 1088) for n in range(3)]
-        return ["ds_write_b128 %%[red], a[%d:%d] offset:%d" % (4 * par, 4 * par + 3, par * 8 * 1088) for par in range(2)]
+            return ["ds_write_b128 %%[red], %s offset:%d" % (rng(4 * n), n * 1088) for n in range(3)]
+        return ["ds_write_b128 %%[red], %s offset:%d" % (rng(4 * par), par * 8 * 1088) for par in range(2)]
+
+    def bwd_operands(self):
+        """(rest of the signature, C++ lines in front of the statement, outputs, inputs) of a backward phase"""
+        sig = "        const float* ga, const float* ha, const float* xa"
+        ins = '[ga] "v"(ga), [ha] "v"(ha), [xa] "v"(xa)'
+        pre = []
+        if self.stores:
+            sig += ",\n        float* sbase_, unsigned so0, float* sg, float* sn, const f32x4& d0, const f32x4& d1, const f32x4& d2, const f32x4& d3"
+            pre = ["float* sbase = const_cast<float*>(fn_uniform_ptr(sbase_));"]
+            ins += ', [sbase] "s"(sbase), [so0] "v"(so0), [sg] "v"(sg), [sn] "v"(sn), [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3)'
+        sig += ",\n        f32x4 (&gt)[4], f32x4& hp, f32x4& xt, unsigned& pv"
+        outs = ", ".join(['[gt%d] "=&v"(gt[%d])' % (q, q) for q in range(4)] + ['[hp] "=&v"(hp)', '[xt] "=&v"(xt)', '[pv] "=&v"(pv)'])
+        return sig, pre, outs, ins
+
+    def phase_statement(self, comment, sig, why, pre, lds, outs, ins, clob):
+        """what the statements of all phases share: the operands of the protocol (why = comment lines in front of the two made uniform here), scalar clobbers"""
+        pre = ["const float* xin = fn_uniform_ptr(xin_);", "const float* xiny = fn_uniform_ptr(xiny_);"] + why + [
+            "arr = __builtin_amdgcn_readfirstlane(arr);", "ptgt = (unsigned)__builtin_amdgcn_readfirstlane((int)ptgt);"] + pre
+        ins = ('[xin] "s"(xin), [xiny] "s"(xiny), [vo] "v"(vo), [voy] "v"(voy), [red] "v"(red), %s, [arr] "s"(arr),\n'
+               '          [acnt] "v"(acnt), [pcnt] "v"(pcnt), [ptgt] "s"(ptgt), %s') % (lds, ins)
+        return statement(comment, self.name, sig, pre, self.body(), outs, ins, ['"memory"', '"scc"', '"vcc"'] + clobber("s", range(SB, SB + 4)) + clob)
 
     def emit_main(self):
-        L = self.body()
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
-        clob = ", ".join(['"a%d"' % i for i in range(self.nagpr)] + ([] if self.fwd or not self.stores else ['"v%d"' % TV, '"v%d"' % (TV + 1)]))
+        clob = clobber("a", range(self.nagpr)) + ([] if self.fwd or not self.stores else clobber("v", (TV, TV + 1)))
         sig = ("const float* xin_, unsigned vo, unsigned lp, unsigned lq, unsigned red,\n"
                "        int arr, u32* acnt, const u32* pcnt, unsigned ptgt, const float* xiny_, unsigned voy,\n")
-        pre = ""
         if self.fwd:
+            pre = []
             sig += "        const float* xa, const int* ta"
             if self.stores:
                 sig += ",\n        float* sa0, float* sa1, float* sa2, const f32x4& d0, const f32x4& d1, const f32x4& d2, const f32x4& d3, const f32x4& d4"
@@ -319,60 +285,28 @@ class Gen:
             ins = '[xa] "v"(xa), [ta] "v"(ta)'
             if self.stores:
                 ins += ', [sa0] "v"(sa0), [sa1] "v"(sa1), [sa2] "v"(sa2), [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3), [d4] "v"(d4)'
-        else:
-            sig += "        const float* ga, const float* ha, const float* xa"
-            if self.stores:
-                sig += ",\n        float* sbase_, unsigned so0, float* sg, float* sn, const f32x4& d0, const f32x4& d1, const f32x4& d2, const f32x4& d3"
-                pre = "    float* sbase = const_cast<float*>(fn_uniform_ptr(sbase_));\n"
-            sig += ",\n        f32x4 (&gt)[4], f32x4& hp, f32x4& xt, unsigned& pv"
-            outs = ", ".join(['[gt%d] "=&v"(gt[%d])' % (q, q) for q in range(4)] + ['[hp] "=&v"(hp)', '[xt] "=&v"(xt)', '[pv] "=&v"(pv)'])
-            ins = '[ga] "v"(ga), [ha] "v"(ha), [xa] "v"(xa)'
-            if self.stores:
-                ins += ', [sbase] "s"(sbase), [so0] "v"(so0), [sg] "v"(sg), [sn] "v"(sn), [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3)'
-        if self.fwd:
             what = "sa0 / sa1 / sa2 + d0..d4: exchange-slab, h_all and saved-gates addresses and new state, r, z, n, W_hn h + b_hn" if self.stores else ""
         else:
+            sig2, pre, outs, ins = self.bwd_operands()
+            sig += sig2
             what = ("sbase + so0: exchange slab of the previous epilogue and this lane's byte offset in it, sg / sn: dgx (middle gate) and dghn addresses, "
                     "d0..d3 = dr', dz', dn', dn' r") if self.stores else ""
-        return """
-// %s: K loop of one phase (%d units of 16 K values, ring of %d, %d MFMAs per unit, %d AGPRs; %s%s).
+        comment = """// %s: K loop of one phase (%d units of 16 K values, ring of %d, %d MFMAs per unit, %d AGPRs; %s%s).
 // xin = this wave's first operand unit of THIS phase (uniform), vo = byte offset of its row tile (+ lane * 16); the first %d units are already
 // in flight.  arr / acnt: arrival for the previous phase's epilogue (0 none, 1 due, 2 due and this wave issues it / its counter).
 // pcnt / ptgt: counter and target of the next phase's half; xiny / voy: its operand base and tile offset - its ring is requested when
-// pv >= ptgt at the end of this loop (pv is returned: otherwise the caller polls and requests it with the *_pro statement).%s
-FN_DEVINL void %s(%s) {
-    const float* xin = fn_uniform_ptr(xin_);
-    const float* xiny = fn_uniform_ptr(xiny_);
-    // wave-uniform by construction; an "s" operand the compiler believes divergent would be handed over in a VGPR
-    arr = __builtin_amdgcn_readfirstlane(arr);
-    ptgt = (unsigned)__builtin_amdgcn_readfirstlane((int)ptgt);
-%s    asm volatile(
-%s
-        : %s
-        : [xin] "s"(xin), [xiny] "s"(xiny), [vo] "v"(vo), [voy] "v"(voy), [red] "v"(red), [lp] "v"(lp), [lq] "v"(lq), [arr] "s"(arr),
-          [acnt] "v"(acnt), [pcnt] "v"(pcnt), [ptgt] "s"(ptgt), %s
-        : "memory", "scc", "vcc", "s%d", "s%d", "s%d", "s%d", %s);
-}
-""" % (self.name, self.units, self.RU, self.nmf, self.nagpr, "issues the previous epilogue's stores" if self.stores else "no stores to issue",
-       ", lanes 0-31 store" if self.masked and self.stores else "", self.RU - 1, ("\n// " + what) if what else "", self.name, sig, pre, body, outs, ins,
-       SB, SB + 1, SB + 2, SB + 3, clob)
+// pv >= ptgt at the end of this loop (pv is returned: otherwise the caller polls and requests it with the *_pro statement).%s""" % (
+            self.name, self.units, self.RU, self.nmf, self.nagpr, "issues the previous epilogue's stores" if self.stores else "no stores to issue",
+            ", lanes 0-31 store" if self.masked and self.stores else "", self.RU - 1, ("\n// " + what) if what else "")
+        why = ['// wave-uniform by construction; an "s" operand the compiler believes divergent would be handed over in a VGPR']
+        return self.phase_statement(comment, sig, why, pre, '[lp] "v"(lp), [lq] "v"(lq)', outs, ins, clob)
 
     def emit_pro(self, name):
-        L = self.request("%[xin]", "%[vo]")
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
-        clob = ", ".join('"a%d"' % i for i in list(range(self.ring0, self.ring0 + (self.RU - 1) * 4)) + list(range(self.w0, self.w0 + self.NB * 4)))
-        return """
-// ring request of a phase (units 0 .. %d) + the weight fragments of unit 0: what the previous phase's statement does at its end when the
-// counter was already there
-FN_DEVINL void %s(const float* xin_, unsigned vo, unsigned lp, unsigned lq) {
-    const float* xin = fn_uniform_ptr(xin_);
-    asm volatile(
-%s
-        :
-        : [xin] "s"(xin), [vo] "v"(vo), [lp] "v"(lp), [lq] "v"(lq)
-        : "memory", "scc", "s%d", "s%d", %s);
-}
-""" % (self.RU - 2, name, body, SB, SB + 1, clob)
+        comment = """// ring request of a phase (units 0 .. %d) + the weight fragments of unit 0: what the previous phase's statement does at its end when the
+// counter was already there""" % (self.RU - 2)
+        regs = list(range(self.ring0, self.ring0 + (self.RU - 1) * 4)) + list(range(self.w0, self.w0 + self.NB * 4))
+        return statement(comment, name, "const float* xin_, unsigned vo, unsigned lp, unsigned lq", ["const float* xin = fn_uniform_ptr(xin_);"], self.request(), "",
+                         '[xin] "s"(xin), [vo] "v"(vo), [lp] "v"(lp), [lq] "v"(lq)', ['"memory"', '"scc"'] + clobber("s", (SB, SB + 1)) + clobber("a", regs))
 
 
 class GenRS(Gen):
@@ -407,108 +341,40 @@ class GenRS(Gen):
         self.next_ts = [0, 2, 4, 6, 8, 10, 12, 14] if TH == 2 else [0, 1, 2, 3, 4, 5, 6, 7]
         self.extra_lead = 12 if TH == 2 else 14
 
-    def ring(self, slot, m=0):
-        return self.ring0 + 4 * (self.TH * slot + m)
-
-    def vreg(self, m, y=False):
-        return ("%[voy]" if y else "%[vo]") if m == 0 else "v%d" % (TV + 3 if y else TV + 2)
-
-    def refill_ins(self, slot, imm):
-        out = []
-        for m in range(self.TH):
-            r = self.ring(slot, m)
-            out.append((4 * m, "global_load_dwordx4 a[%d:%d], %s, s[%d:%d] offset:%d sc1" % (r, r + 3, self.vreg(m), SB, SB + 1, imm)))
-        return out
-
-    def next_ring_ins(self, slot, off):
-        return ["global_load_dwordx4 a[%d:%d], %s, s[%d:%d] offset:%d sc1" % (self.ring(slot, m), self.ring(slot, m) + 3, self.vreg(m, True), SB, SB + 1, off)
-                for m in range(self.TH)]
-
-    def request(self, xin, vo):
-        y = vo == "%[voy]"
-        L = ["s_mov_b64 s[%d:%d], %s" % (SB, SB + 1, xin), "s_nop 4"]
-        rel = 0
-        for u in range(self.RU - 1):
-            while u * 1024 - rel > 4095:
-                L += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1), "s_nop 4"]
-                rel += 4096
-            for m in range(self.TH):
-                r = self.ring(u, m)
-                L.append("global_load_dwordx4 a[%d:%d], %s, s[%d:%d] offset:%d sc1" % (r, r + 3, self.vreg(m, y), SB, SB + 1, u * 1024 - rel))
-        L.append(self.wread_at(0, 0, 0))
-        return L
-
-    def mfmas_u(self, slot, bs, u):
+    def mfmas(self, slot, bs, u):
         out = []
         for jj in range(4):
             for m in range(self.TH):
                 a = self.ring(slot, m) + jj
                 for ct, b in ((0, self.wr0 + 4 * u + jj), (1, self.wf(bs, 0) + jj)):
                     c = 4 * (2 * m + ct)
-                    out.append("v_mfma_f32_16x16x4_f32 a[%d:%d], a%d, a%d, a[%d:%d]" % (c, c + 3, a, b, c, c + 3))
+                    out.append("v_mfma_f32_16x16x4_f32 %s, a%d, a%d, %s" % (rng(c), a, b, rng(c)))
         return out
 
     def acc_writes(self):
-        return ["ds_write_b128 %%[red], a[%d:%d] offset:%d" % (4 * t, 4 * t + 3, t * 1088) for t in range(2 * self.TH)]
+        return ["ds_write_b128 %%[red], %s offset:%d" % (rng(4 * t), t * 1088) for t in range(2 * self.TH)]
 
     def body(self):
         # the second row tile's offsets (one row tile = nk3 * 2 KB further on) live in v202 / v203 for the whole statement
         pre = ["v_add_u32 v%d, 0x18000, %%[vo]" % (TV + 2), "v_add_u32 v%d, 0x18000, %%[voy]" % (TV + 3)] if self.TH == 2 else []
-        # the ring holds TH loads per unit: the base class counts one vmop per ring load, which refill_ins / the initial state provide
-        L = Gen.body(self)
-        return pre + L
+        return pre + Gen.body(self)
 
     def emit_main(self):
-        # initial ring state: TH loads per unit (Gen.body starts from one per unit: patch the bookkeeping through a subclass hook)
-        L = self.body()
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
-        clob = ", ".join(['"a%d"' % i for i in range(self.wr0)] + ['"v%d"' % (TV + i) for i in range(4)])
+        sig2, pre, outs, ins = self.bwd_operands()
         sig = ("const float* xin_, unsigned vo, unsigned lp, unsigned red,\n"
-               "        int arr, u32* acnt, const u32* pcnt, unsigned ptgt, const float* xiny_, unsigned voy,\n"
-               "        const float* ga, const float* ha, const float* xa")
-        ins = '[ga] "v"(ga), [ha] "v"(ha), [xa] "v"(xa)'
-        pre = ""
-        if self.stores:
-            sig += ",\n        float* sbase_, unsigned so0, float* sg, float* sn, const f32x4& d0, const f32x4& d1, const f32x4& d2, const f32x4& d3"
-            pre = "    float* sbase = const_cast<float*>(fn_uniform_ptr(sbase_));\n"
-            ins += ', [sbase] "s"(sbase), [so0] "v"(so0), [sg] "v"(sg), [sn] "v"(sn), [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [d3] "v"(d3)'
-        sig += ",\n        f32x4 (&gt)[4], f32x4& hp, f32x4& xt, unsigned& pv"
-        outs = ", ".join(['[gt%d] "=&v"(gt[%d])' % (q, q) for q in range(4)] + ['[hp] "=&v"(hp)', '[xt] "=&v"(xt)', '[pv] "=&v"(pv)'])
-        return """
-// %s: register-stationary backward K loop of one phase (%d row tile(s) x 2 column tiles, 24 units of 16 K values = this wave's K quarter, ring of %d,
+               "        int arr, u32* acnt, const u32* pcnt, unsigned ptgt, const float* xiny_, unsigned voy,\n" + sig2)
+        comment = """// %s: register-stationary backward K loop of one phase (%d row tile(s) x 2 column tiles, 24 units of 16 K values = this wave's K quarter, ring of %d,
 // %d MFMAs per unit; %s).  Operands as in the fn_pp_bwd_* statements; vo / voy = byte offset of the FIRST row tile of the half (the second one
-// follows nk3 * 2 KB further on); lp = LDS byte address of this wave's first weight-fragment unit of the LDS half of the slice.
-FN_DEVINL void %s(%s) {
-    const float* xin = fn_uniform_ptr(xin_);
-    const float* xiny = fn_uniform_ptr(xiny_);
-    arr = __builtin_amdgcn_readfirstlane(arr);
-    ptgt = (unsigned)__builtin_amdgcn_readfirstlane((int)ptgt);
-%s    asm volatile(
-%s
-        : %s
-        : [xin] "s"(xin), [xiny] "s"(xiny), [vo] "v"(vo), [voy] "v"(voy), [red] "v"(red), [lp] "v"(lp), [arr] "s"(arr),
-          [acnt] "v"(acnt), [pcnt] "v"(pcnt), [ptgt] "s"(ptgt), %s
-        : "memory", "scc", "vcc", "s%d", "s%d", "s%d", "s%d", %s);
-}
-""" % (self.name, self.TH, self.RU, self.nmf, "issues the previous epilogue's stores" if self.stores else "no stores to issue", self.name, sig, pre, body, outs, ins,
-       SB, SB + 1, SB + 2, SB + 3, clob)
+// follows nk3 * 2 KB further on); lp = LDS byte address of this wave's first weight-fragment unit of the LDS half of the slice.""" % (
+            self.name, self.TH, self.RU, self.nmf, "issues the previous epilogue's stores" if self.stores else "no stores to issue")
+        return self.phase_statement(comment, sig, [], pre, '[lp] "v"(lp)', outs, ins, clobber("a", range(self.wr0)) + clobber("v", range(TV, TV + 4)))
 
     def emit_pro(self, name):
-        L = (["v_add_u32 v%d, 0x18000, %%[vo]" % (TV + 2)] if self.TH == 2 else []) + self.request("%[xin]", "%[vo]")
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
+        L = (["v_add_u32 v%d, 0x18000, %%[vo]" % (TV + 2)] if self.TH == 2 else []) + self.request()
         regs = list(range(self.ring0, self.ring0 + (self.RU - 1) * self.TH * 4)) + list(range(self.w0, self.w0 + 4))
-        clob = ", ".join(['"a%d"' % i for i in regs] + ['"v%d"' % (TV + 2)])
-        return """
-// ring request of a phase (units 0 .. %d, %d row tile(s)) + the LDS-half weight fragments of unit 0
-FN_DEVINL void %s(const float* xin_, unsigned vo, unsigned lp) {
-    const float* xin = fn_uniform_ptr(xin_);
-    asm volatile(
-%s
-        :
-        : [xin] "s"(xin), [vo] "v"(vo), [lp] "v"(lp)
-        : "memory", "scc", "s%d", "s%d", %s);
-}
-""" % (self.RU - 2, self.TH, name, body, SB, SB + 1, clob)
+        comment = "// ring request of a phase (units 0 .. %d, %d row tile(s)) + the LDS-half weight fragments of unit 0" % (self.RU - 2, self.TH)
+        return statement(comment, name, "const float* xin_, unsigned vo, unsigned lp", ["const float* xin = fn_uniform_ptr(xin_);"], L, "",
+                         '[xin] "s"(xin), [vo] "v"(vo), [lp] "v"(lp)', ['"memory"', '"scc"'] + clobber("s", (SB, SB + 1)) + clobber("a", regs) + clobber("v", [TV + 2]))
 
     def emit_wload(self, name):
         """the register-stationary half of the slice: this wave's 24 units of column tile 0 -> a[wr0 .. wr0 + 96)"""
@@ -516,37 +382,20 @@ FN_DEVINL void %s(const float* xin_, unsigned vo, unsigned lp) {
         rel = 0
         for u in range(24):
             while u * 1024 - rel > 4095:
-                L += ["s_add_u32 s%d, s%d, 0x1000" % (SB, SB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1), "s_nop 4"]
+                L += advance(nop=True)
                 rel += 4096
-            L.append("global_load_dwordx4 a[%d:%d], %%[vo], s[%d:%d] offset:%d" % (self.wr0 + 4 * u, self.wr0 + 4 * u + 3, SB, SB + 1, u * 1024 - rel))
+            L.append("global_load_dwordx4 %s, %%[vo], s[%d:%d] offset:%d" % (rng(self.wr0 + 4 * u), SB, SB + 1, u * 1024 - rel))
         L.append("s_waitcnt vmcnt(0)")
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
-        clob = ", ".join('"a%d"' % i for i in range(self.wr0, self.wr0 + 96))
-        return """
-// one-time: the register-stationary half of the W_hh^T slice.  src = this wave's first unit of column tile 0 in the fragment image (uniform),
-// vo = lane * 16.  a[%d:%d] are read by every %s statement and never written again.
-FN_DEVINL void %s(const float* src_, unsigned vo) {
-    const float* src = fn_uniform_ptr(src_);
-    asm volatile(
-%s
-        :
-        : [src] "s"(src), [vo] "v"(vo)
-        : "memory", "scc", "s%d", "s%d", %s);
-}
-""" % (self.wr0, self.wr0 + 95, self.name, name, body, SB, SB + 1, clob)
+        comment = """// one-time: the register-stationary half of the W_hh^T slice.  src = this wave's first unit of column tile 0 in the fragment image (uniform),
+// vo = lane * 16.  a[%d:%d] are read by every %s statement and never written again.""" % (self.wr0, self.wr0 + 95, self.name)
+        return statement(comment, name, "const float* src_, unsigned vo", ["const float* src = fn_uniform_ptr(src_);"], L, "", '[src] "s"(src), [vo] "v"(vo)',
+                         ['"memory"', '"scc"'] + clobber("s", (SB, SB + 1)) + clobber("a", range(self.wr0, self.wr0 + 96)))
 
 
 HEAD = """// GENERATED by gen_kloop2.py - do not edit.  K loops of the ping-pong weight-stationary GRU scans (H = 512, one row tile per wave and phase).
 #pragma once
 #include "mma_core.h"
 typedef unsigned int u32;
-
-// wave-uniform by construction (depends on the wave id only); the compiler cannot see that
-FN_DEVINL const float* fn_uniform_ptr(const float* p) {
-    const unsigned long long q = (unsigned long long)(uintptr_t)p;
-    return reinterpret_cast<const float*>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(q >> 32)) << 32) |
-                                                      (unsigned)__builtin_amdgcn_readfirstlane((int)(q & 0xffffffffull))));
-}
 """
 
 

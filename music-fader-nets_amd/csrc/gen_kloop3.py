@@ -26,10 +26,9 @@ Scalars s84..s87.
 """
 import sys
 
-SB = 84
-UB = 3072            # bytes of one unit on the exchange slab / in the LDS weight image (3 pieces x 1 KB)
+from kloop_common import PROD, SB, UB, Slots, VmQueue, advance, clobber, lanes32, rng, statement
+
 GS = 49152           # gate stride of the LDS weight image: 16 K blocks x 3 KB
-PROD = [(2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)]      # (piece of A = state, piece of B = weights), smallest product first; 0 = hi, 1 = mid, 2 = lo
 
 
 class GenX6:
@@ -49,50 +48,34 @@ class GenX6:
         return self.w0 + 36 * bs + 12 * q + 4 * pc
 
     def wread(self, bs, q, pc, unit):
-        r = self.wf(bs, q, pc)
         off = unit * UB + pc * 1024
         assert 0 <= off < 65536
-        return "ds_read_b128 a[%d:%d], %%[lp%d] offset:%d" % (r, r + 3, q, off)
+        return "ds_read_b128 %s, %%[lp%d] offset:%d" % (rng(self.wf(bs, q, pc)), q, off)
 
     def mfmas(self, slot, bs):
         out = []
         for pa, pb in PROD:
             for q in range(3):
                 a, b, c = self.ring(slot, pa), self.wf(bs, q, pb), 4 * q
-                out.append("v_mfma_f32_16x16x32_bf16 a[%d:%d], a[%d:%d], a[%d:%d], a[%d:%d]" % (c, c + 3, a, a + 3, b, b + 3, c, c + 3))
+                out.append("v_mfma_f32_16x16x32_bf16 %s, %s, %s, %s" % (rng(c), rng(a), rng(b), rng(c)))
         return out
-
-    def wait_unit(self, u):
-        last = max(i for i, o in enumerate(self.vmops) if o == ("ring", u))
-        n = len(self.vmops) - 1 - last
-        assert n < 60, n
-        return "s_waitcnt vmcnt(%d)" % n
-
-    def masked_ins(self, ins):
-        if not self.masked:
-            return ins
-        return ["s_mov_b64 s[%d:%d], exec" % (SB + 2, SB + 3), "s_mov_b64 exec, 0xffffffff"] + ins + ["s_mov_b64 exec, s[%d:%d]" % (SB + 2, SB + 3)]
 
     def arrive_block(self):
         """the slab stores of the previous epilogue have completed in every wave (barrier: also the fence between the previous epilogue's
         reads of the accumulator tiles and this phase's writes) -> one arrival (arr: 0 = none due, 1 = due, 2 = due and this wave issues it)"""
-        slab = [i for i, o in enumerate(self.vmops) if o == ("store", "slab")]
         # no stores in this statement: the previous epilogue's were issued in front of it (flush_stores) - everything older than the statement
-        n = (len(self.vmops) - 1 - max(slab)) if slab else (len(self.vmops) - self.n0)
         # (the atomic is NOT entered into the bookkeeping: only one wave issues it, and an operation the count does not know makes a later
         # wait more patient, one it wrongly knows would end a wait too early)
-        return ["s_waitcnt vmcnt(%d)" % n, "s_barrier", "s_cmp_lt_u32 %[arr], 2", "s_cbranch_scc1 .Lnoarr_%=",
+        return [self.q.wait_slab_store(), "s_barrier", "s_cmp_lt_u32 %[arr], 2", "s_cbranch_scc1 .Lnoarr_%=",
                 "s_mov_b64 s[%d:%d], exec" % (SB + 2, SB + 3), "s_mov_b64 exec, 1", "v_mov_b32 %[pv], 1",
                 "global_atomic_add %[acnt], %[pv], off", "s_mov_b64 exec, s[%d:%d]" % (SB + 2, SB + 3), ".Lnoarr_%=:"]
 
     def body(self):
         RU, units = self.RU, self.units
-        self.vmops = [("ring", u) for u in range(RU - 1) for _ in range(3)]      # in flight when the statement starts: the ring request and nothing else
-        self.n0 = len(self.vmops)
+        self.q = VmQueue(("ring", u) for u in range(RU - 1) for _ in range(3))      # in flight when the statement starts: the ring request and nothing else
         L = ["s_mov_b64 s[%d:%d], %%[xin]" % (SB, SB + 1)]
         # running base = first refill of unit 0's turn = unit RU - 1
-        adv0 = (RU - 1) * UB
-        L += ["s_add_u32 s%d, s%d, 0x%x" % (SB, SB, adv0), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1)]
+        L += advance((RU - 1) * UB)
         for c in range(12):
             L.append("v_accvgpr_write_b32 a%d, 0" % c)
         if self.stores:
@@ -106,56 +89,43 @@ class GenX6:
         done_arr = False
         for u in range(units):
             bs = u & 1
-            comp = [[] for _ in range(18)]
-            vm = [[] for _ in range(18)]                   # bookkeeping entries in issue order
+            slots = Slots(18)
             refill = u + RU - 1 < units
             if refill:
                 for pc in range(3):
-                    r = self.ring(u + RU - 1, pc)
-                    comp[pc].append("global_load_dwordx4 a[%d:%d], %%[vo], s[%d:%d] offset:%d sc1" % (r, r + 3, SB, SB + 1, pc * 1024))
-                    vm[pc].append(("ring", u + RU - 1))
-                comp[3] += ["s_add_u32 s%d, s%d, 0x%x" % (SB, SB, UB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1)]
+                    slots.put(pc, "global_load_dwordx4 %s, %%[vo], s[%d:%d] offset:%d sc1" % (rng(self.ring(u + RU - 1, pc)), SB, SB + 1, pc * 1024), ("ring", u + RU - 1))
+                slots.put(3, advance(UB))
             if u + 1 < units:
                 n = 0
                 for q in range(3):
                     for pc in range(3):
-                        comp[2 + n].append(self.wread(bs ^ 1, q, pc, u + 1))
+                        slots.put(2 + n, self.wread(bs ^ 1, q, pc, u + 1))
                         n += 1
             if u == 0 and slab:
                 for i, (kind, ins) in enumerate(slab):
-                    comp[11 + 2 * i] += self.masked_ins([ins])
-                    vm[11 + 2 * i].append(("store", kind))
+                    slots.put(11 + 2 * i, lanes32([ins], self.masked), ("store", kind))
             elif outs and u >= 1 and not (u == self.extra_unit):
                 kind, ins = outs.pop(0)
-                comp[12] += self.masked_ins([ins])
-                vm[12].append(("store", kind))
+                slots.put(12, lanes32([ins], self.masked), ("store", kind))
             if u == self.extra_unit:
                 for i, ins in enumerate(extras):
-                    comp[11 + i].append(ins)
-                    vm[11 + i].append(("extra", 0))
+                    slots.put(11 + i, ins, ("extra", 0))
             if u == self.poll_unit:
-                comp[16].append("global_load_dword %[pv], %[pcnt], off sc1")
-                vm[16].append(("poll", 0))
-            L.append(self.wait_unit(u))
+                slots.put(16, "global_load_dword %[pv], %[pcnt], off sc1", ("poll", 0))
+            L.append(self.q.wait_for(("ring", u)))
             L.append("s_waitcnt lgkmcnt(0)")
-            for t, ins in enumerate(self.mfmas(u, bs)):
-                L.append(ins)
-                L += comp[t]
-                self.vmops += vm[t]
+            L += self.q.unit(self.mfmas(u, bs), slots)
             if u == self.u_arr:
                 L += self.arrive_block()
                 done_arr = True
         assert done_arr and not outs, (done_arr, outs)
         # everything requested by this statement has landed (epilogue operands, the counter value; the stores have completed)
         L += ["s_waitcnt vmcnt(0)", "s_nop 7"]
-        L += ["ds_write_b128 %%[red], a[%d:%d] offset:%d" % (4 * q, 4 * q + 3, q * 1088) for q in range(3)]
+        L += ["ds_write_b128 %%[red], %s offset:%d" % (rng(4 * q), q * 1088) for q in range(3)]
         L.append("s_waitcnt lgkmcnt(0)")
         return L
 
     def emit_main(self):
-        L = self.body()
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
-        clob = ", ".join('"a%d"' % i for i in range(self.nagpr))
         sig = ("const void* xin_, unsigned vo, unsigned lp0, unsigned lp1, unsigned lp2, unsigned red,\n"
                "        int arr, u32* acnt, const u32* pcnt, const float* xa, const int* ta")
         ins = '[xa] "v"(xa), [ta] "v"(ta)'
@@ -168,51 +138,34 @@ class GenX6:
         outs = ", ".join(['[ex%d] "=&v"(ex[%d])' % (q, q) for q in range(3)] + ['[tokn] "=&v"(tokn)', '[pv] "=&v"(pv)'])
         what = ("\n// sa0 + t0..t2: this lane's 8 bytes per piece on the exchange slab and the new state as bf16 triples; sa1 / sa2 + d0..d4: h_all and "
                 "saved-gates addresses, new state, r, z, n, W_hn h + b_hn") if self.stores else ""
-        return """
-// %s: K loop of one phase on the bf16 MFMA (%d units of 32 K values x 3 pieces, ring of %d, 18 MFMAs per unit, %d AGPRs; %s%s).
+        comment = """// %s: K loop of one phase on the bf16 MFMA (%d units of 32 K values x 3 pieces, ring of %d, 18 MFMAs per unit, %d AGPRs; %s%s).
 // xin = this wave's first operand unit of THIS phase (uniform), vo = byte offset of its row tile (+ lane * 16); the first %d units are already in
 // flight (`*_pro`).  lp0..2 = LDS byte addresses of this wave's first weight unit of gates r, z, n.  arr / acnt: arrival for the previous phase's
 // epilogue (0 none, 1 due, 2 due and this wave issues it / its counter).  pcnt: counter of the next phase's half, returned in pv (loaded %d unit(s)
-// before the end).  xa / ta: this phase's epilogue operands (middle gate row of the input pre-activations; token of the next step).%s
-FN_DEVINL void %s(%s) {
-    const void* xin = fn_uniform_ptr(reinterpret_cast<const float*>(xin_));
-    arr = __builtin_amdgcn_readfirstlane(arr);       // wave-uniform by construction; an "s" operand the compiler believes divergent would be handed over in a VGPR
-    asm volatile(
-%s
-        : %s
-        : [xin] "s"(xin), [vo] "v"(vo), [red] "v"(red), [lp0] "v"(lp0), [lp1] "v"(lp1), [lp2] "v"(lp2), [arr] "s"(arr),
-          [acnt] "v"(acnt), [pcnt] "v"(pcnt), %s
-        : "memory", "scc", "vcc", "s%d", "s%d", "s%d", "s%d", %s);
-}
-""" % (self.name, self.units, self.RU, self.nagpr, "issues the previous epilogue's stores" if self.stores else "no stores to issue",
-       ", lanes 0-31 store" if self.masked and self.stores else "", self.RU - 1, self.units - self.poll_unit, what, self.name, sig, body, outs, ins,
-       SB, SB + 1, SB + 2, SB + 3, clob)
+// before the end).  xa / ta: this phase's epilogue operands (middle gate row of the input pre-activations; token of the next step).%s""" % (
+            self.name, self.units, self.RU, self.nagpr, "issues the previous epilogue's stores" if self.stores else "no stores to issue",
+            ", lanes 0-31 store" if self.masked and self.stores else "", self.RU - 1, self.units - self.poll_unit, what)
+        pre = ["const void* xin = fn_uniform_ptr(reinterpret_cast<const float*>(xin_));",
+               'arr = __builtin_amdgcn_readfirstlane(arr);       // wave-uniform by construction; an "s" operand the compiler believes divergent would be handed over in a VGPR']
+        ins = ('[xin] "s"(xin), [vo] "v"(vo), [red] "v"(red), [lp0] "v"(lp0), [lp1] "v"(lp1), [lp2] "v"(lp2), [arr] "s"(arr),\n'
+               '          [acnt] "v"(acnt), [pcnt] "v"(pcnt), ' + ins)
+        return statement(comment, self.name, sig, pre, self.body(), outs, ins, ['"memory"', '"scc"', '"vcc"'] + clobber("s", range(SB, SB + 4)) + clobber("a", range(self.nagpr)))
 
     def emit_pro(self, name):
         L = ["s_mov_b64 s[%d:%d], %%[xin]" % (SB, SB + 1), "s_nop 4"]
         for u in range(self.RU - 1):
             for pc in range(3):
-                r = self.ring(u, pc)
-                L.append("global_load_dwordx4 a[%d:%d], %%[vo], s[%d:%d] offset:%d sc1" % (r, r + 3, SB, SB + 1, pc * 1024))
+                L.append("global_load_dwordx4 %s, %%[vo], s[%d:%d] offset:%d sc1" % (rng(self.ring(u, pc)), SB, SB + 1, pc * 1024))
             if u + 1 < self.RU - 1:
-                L += ["s_add_u32 s%d, s%d, 0x%x" % (SB, SB, UB), "s_addc_u32 s%d, s%d, 0" % (SB + 1, SB + 1), "s_nop 4"]
+                L += advance(UB, nop=True)
         for q in range(3):
             for pc in range(3):
                 L.append(self.wread(0, q, pc, 0))
-        body = "\n".join('        "%s\\n\\t"' % l for l in L)
         regs = list(range(self.ring0, self.ring0 + (self.RU - 1) * 12)) + list(range(self.w0, self.w0 + 36))
-        clob = ", ".join('"a%d"' % i for i in regs)
-        return """
-// ring request of a phase (units 0 .. %d, three pieces each) + the weight fragments of unit 0
-FN_DEVINL void %s(const void* xin_, unsigned vo, unsigned lp0, unsigned lp1, unsigned lp2) {
-    const void* xin = fn_uniform_ptr(reinterpret_cast<const float*>(xin_));
-    asm volatile(
-%s
-        :
-        : [xin] "s"(xin), [vo] "v"(vo), [lp0] "v"(lp0), [lp1] "v"(lp1), [lp2] "v"(lp2)
-        : "memory", "scc", "s%d", "s%d", %s);
-}
-""" % (self.RU - 2, name, body, SB, SB + 1, clob)
+        comment = "// ring request of a phase (units 0 .. %d, three pieces each) + the weight fragments of unit 0" % (self.RU - 2)
+        return statement(comment, name, "const void* xin_, unsigned vo, unsigned lp0, unsigned lp1, unsigned lp2",
+                         ["const void* xin = fn_uniform_ptr(reinterpret_cast<const float*>(xin_));"], L, "",
+                         '[xin] "s"(xin), [vo] "v"(vo), [lp0] "v"(lp0), [lp1] "v"(lp1), [lp2] "v"(lp2)', ['"memory"', '"scc"'] + clobber("s", (SB, SB + 1)) + clobber("a", regs))
 
 
 HEAD = """// GENERATED by gen_kloop3.py - do not edit.  K loops of the ping-pong forward scans on the bf16 MFMA with exact bf16 triple splits (H = 512).

@@ -39,6 +39,13 @@ FN_DEVINL void fn_wait_vm() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// wave-uniform by construction (depends on the wave id only); the compiler cannot see that
+FN_DEVINL const float* fn_uniform_ptr(const float* p) {
+    const unsigned long long q = (unsigned long long)(uintptr_t)p;
+    return reinterpret_cast<const float*>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(q >> 32)) << 32) |
+                                                      (unsigned)__builtin_amdgcn_readfirstlane((int)(q & 0xffffffffull))));
+}
+
 // bf16 x 6 arithmetic: x rounded to its nearest bf16 value (8 significant bits; ties away from zero: the bit pattern plus half a bf16 ulp,
 // truncated).  Whatever the rounding, x - fn_rn16(x) is exact in fp32, and two levels leave a remainder of <= 8 significant bits: hi + mid + lo == x
 // with all three pieces exact bf16 values.  ROUNDED pieces (instead of truncated ones, whose remainders all carry the sign of x) make the three

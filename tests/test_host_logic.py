@@ -340,17 +340,34 @@ def test_generated_k_loops_wait_counts():
     """the hand-counted `s_waitcnt vmcnt(n)` of the generated K-loop statements against the issue order of their memory operations (csrc/check_kloops.py):
     no arrival may be posted while an exchange-slab store of the statement can still be in flight, no MFMA may read a register a load is still allowed
     to be writing.  Round 5: the arrival wait of fn_rs_bwd_t1_main was one operation too lenient - a real defect, unrelated to the rare eager-step
-    nondeterminism of profiles/r05_eager_nondeterminism.txt (its rate did not change with the fix).  Also: the committed headers equal a clean regeneration."""
+    nondeterminism of profiles/r05_eager_nondeterminism.txt (its rate did not change with the fix).  All four headers (42 statements): the four
+    fn_kloop_* statements of kloop_asm.h request their ring themselves and are walked from an empty queue - and raising any single one of their 192 ring
+    waits by one is a finding.  Also: the committed headers equal a regeneration, whatever KLOOP* variables the environment holds (the generators read none)."""
     import importlib.util
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "music-fader-nets_amd", "csrc")
     spec = importlib.util.spec_from_file_location("check_kloops", os.path.join(csrc, "check_kloops.py"))
     ck = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ck)
-    heads = [os.path.join(csrc, h) for h in ("kloop2_asm.h", "kloop3_asm.h", "kloop4_asm.h")]
+    heads = [os.path.join(csrc, h) for h in ("kloop2_asm.h", "kloop3_asm.h", "kloop4_asm.h", "kloop_asm.h")]
     for h in heads:
         assert os.path.exists(h), "%s missing: run __graft_entry__.build()" % h
     assert ck.main(heads) == 0
-    # the headers the library was built from are what the generators produce in a clean environment (no stray experiment switch: ADVICE r5)
+    # the walk of kloop_asm.h is not vacuous: every single ring wait, one too lenient, is found
+    import re
+    st = ck.statements(heads[3])
+    nwaits = {}
+    for name in ("fn_kloop_fwd_h512_k512", "fn_kloop_fwd_h512_k256", "fn_kloop_bwd_h512_k1536", "fn_kloop_bwd_h512_k768"):
+        lines = st[name]
+        assert ck.walk(name, lines, []) == []
+        # (the closing `s_waitcnt vmcnt(0) lgkmcnt(0)` is not a ring wait: what it covers is read by the caller, behind the statement)
+        ring_waits = [i for i, l in enumerate(lines) if re.fullmatch(r"s_waitcnt vmcnt\(\d+\)", l)]
+        for i in ring_waits:
+            mutated = list(lines)
+            mutated[i] = "s_waitcnt vmcnt(%d)" % (int(lines[i][len("s_waitcnt vmcnt("):-1]) + 1)
+            assert ck.walk(name, mutated, []), "%s: wait %d (%s) raised by one is not found" % (name, i, lines[i])
+        nwaits[name] = len(ring_waits)
+    assert list(nwaits.values()) == [32, 16, 96, 48], nwaits
+    # the headers the library was built from are what the generators produce in a clean environment
     import subprocess
     import sys
     import tempfile
@@ -360,10 +377,12 @@ def test_generated_k_loops_wait_counts():
             out = os.path.join(td, head)
             subprocess.run([sys.executable, os.path.join(csrc, gen), out], check=True, env=env, cwd=csrc)
             assert open(out).read() == open(os.path.join(csrc, head)).read(), "%s differs from a clean regeneration by %s" % (head, gen)
-        # and a stray switch is refused
-        r = subprocess.run([sys.executable, os.path.join(csrc, "gen_kloop2.py"), os.path.join(td, "x.h")], env=dict(env, KLOOP2_ARR0="1"), cwd=csrc,
-                           capture_output=True)
-        assert r.returncode != 0 and not os.path.exists(os.path.join(td, "x.h"))
+        # and a stray variable of the former experiment switches (or any other) cannot reach a production header
+        stray = dict(env, KLOOP2_ARR0="1", KLOOP2_RING0="1", KLOOP4_NT="1")
+        for gen, head in (("gen_kloop2.py", "kloop2_asm.h"), ("gen_kloop4.py", "kloop4_asm.h")):
+            out = os.path.join(td, "stray_" + head)
+            subprocess.run([sys.executable, os.path.join(csrc, gen), out], check=True, env=stray, cwd=csrc)
+            assert open(out, "rb").read() == open(os.path.join(csrc, head), "rb").read(), "%s changes with KLOOP* variables in the environment" % head
 
 
 def test_isa_wait_checker_finds_an_uncovered_asm_load(tmp_path):
