@@ -444,6 +444,42 @@ int fn_vocab_logsoftmax_bwd(const float* logp_bt, const float* gout_bt, int B, i
 int fn_vocab_argmax(const float* logits, int B, int E, int ld, float* logp_out, int64_t logp_ld, int32_t* tok_out,
                     int tok_ld, void* stream);
 
+/* Seeded temperature / top-k / top-p draw from the same head (decode.sample_decode).  There is NO reference counterpart: the reference's
+ * _sampling (gmm_model.py:73-80) is the argmax above; the definition below is the specification.  Per row b of logits [B][ld], V valid columns,
+ * 1 <= V <= FN_SAMPLE_MAX_V:
+ *   1. lp[e] = x[e] - lse and the first-index argmax, computed as the greedy head computes them: logp_out [B][V] (row stride logp_ld) and
+ *      own_out[b*own_ld], both optional, are bit-identical to the greedy head's outputs on the same logits;
+ *   2. descending order by lp, ties to the lower index: rank[e] = #{e' : lp[e'] > lp[e] or (lp[e'] == lp[e] and e' < e)};
+ *   3. sorted weights w[rank[e]] = expf((lp[e] - max lp) * inv_temperature), sorted indices idx[rank[e]] = e;
+ *   4. inclusive fp32 prefix sums c[j] of w: with per = ceil(V / 64), block l = entries per*l .. per*l + per - 1 is summed in order from 0.0f,
+ *      the 64 block totals are scanned inclusively (for o = 1, 2, .. 32: t[l] += t[l - o] for every l >= o, all l at once),
+ *      c[j] = (scanned total of block l - 1, 0.0f for l = 0) + (running sum inside block l);
+ *   5. the kept set is a prefix of the order: n = top_k ? min(top_k, V) : V;  m = top_p < 1 ? min(n, 1 + #{j < n : c[j] < top_p * c[n-1]}) : n
+ *      (fp32 product).  Where c is non-decreasing that is the smallest m with c[m-1] >= top_p * c[n-1]; across a block border of step 4 the
+ *      fp32 sums can step down by an ulp, so the COUNT is the definition, here and in step 6;
+ *   6. u = (Philox4x32-10(counter = (b, step, offset_lo, offset_hi), key = (seed_lo, seed_hi))[0] >> 8) * 2^-24, in [0, 1);
+ *      tok_out[b*tok_ld] = idx[j], j = min(m - 1, #{j < m : not c[j] > u * c[m-1]}) (fp32 product; the first index with c[j] > u c[m-1] where
+ *      c is non-decreasing);  u_out[b] = u when given.
+ * The draw depends on the row of the batch and on `step` (a launch argument), not on the launch geometry.  The parameters are read from
+ * DEVICE memory, so a captured graph serves any seed or setting; as they come from memory they are clamped: top_k to [0, V], top_p to
+ * [FN_SAMPLE_MIN_P, 1] (NaN: 1), inv_temperature to [FN_SAMPLE_MIN_INV_T, FN_SAMPLE_MAX_INV_T] (NaN: 1).  Rows that hold NaNs give an
+ * unspecified token in [0, V).  logits, params or tok_out NULL: FN_E_NULL; B < 1, V outside [1, FN_SAMPLE_MAX_V], ld < V, step < 0:
+ * FN_E_SHAPE; both before any launch. */
+#define FN_SAMPLE_MAX_V 1024
+#define FN_SAMPLE_MIN_P 1e-30f
+#define FN_SAMPLE_MIN_INV_T 1e-30f
+#define FN_SAMPLE_MAX_INV_T 1e30f
+typedef struct FnSampleParams {      /* 32 bytes */
+    uint32_t seed_lo, seed_hi;       /* the Philox key: a 64-bit seed                                                  */
+    uint32_t offset_lo, offset_hi;   /* counter words 2, 3: a 64-bit offset (another stream of draws under one seed)   */
+    float inv_temperature;           /* 1 / temperature                                                                */
+    float top_p;                     /* 1: off                                                                         */
+    int32_t top_k;                   /* 0: off                                                                         */
+    int32_t reserved;                /* 0                                                                              */
+} FnSampleParams;
+int fn_vocab_sample(const float* logits, int B, int V, int ld, const FnSampleParams* params_dev, int step, float* logp_out,
+                    int64_t logp_ld, int32_t* own_out, int own_ld, int32_t* tok_out, int tok_ld, float* u_out, void* stream);
+
 /* TIME-axis log_softmax of the sub-decoders (gmm_model.py:110,115; the reference's dim=1 quirk).
  * logits [Tr][B][Cc] time-major.  logp_bt [B][Tr][Cc].  target [B][Tr] or NULL.
  * nll_bc [B][Cc] (sum over t with target==c of -logp) ; dlogits [Tr][B][Cc] = grad_scale * dNLLsum/dlogits. */

@@ -62,6 +62,8 @@ size_t fn_decode_ws_bytes_host(int B, int H, int V);                            
 size_t fn_decode_sync_ws_bytes_host(void);                                                               /* fn_decode_sync_ws_bytes */
 int fn_decode_greedy_host(const FnDecode* d, void* stream);                                              /* fn_decode_greedy */
 int fn_decode_forced_host(const FnDecode* d, const FnDecodeForce* f, void* stream);                      /* fn_decode_forced */
+int fn_vocab_sample_host(const float* logits, int B, int V, int ld, const FnSampleParams* params, int step, float* logp_out,
+                         int64_t logp_ld, int32_t* own_out, int own_ld, int32_t* tok_out, int tok_ld, float* u_out, void* stream);   /* fn_vocab_sample */
 size_t fn_frag_floats_host(int rows, int K);                                                             /* fn_frag_floats */
 size_t fn_gru_gates_floats_host(int B, int H);                                                           /* fn_gru_gates_floats */
 

@@ -32,6 +32,7 @@ FN_E_UNSUPPORTED = -6
 FN_E_COMM = -7
 FN_COMM_ID_BYTES = 128
 FN_COLSUM_MAX_JOBS = 64
+FN_SAMPLE_MAX_V = 1024
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
 vp = C.c_void_p
@@ -91,6 +92,11 @@ class FnDecodeForce(C.Structure):
     _fields_ = [("forced", vp), ("forced_ld", C.c_int32), ("force", vp)]
 
 
+class FnSampleParams(C.Structure):
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("offset_lo", C.c_uint32), ("offset_hi", C.c_uint32),
+                ("inv_temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fadernets.h
 SIGNATURES = {
     "fn_version": (C.c_int, []),
@@ -137,6 +143,7 @@ SIGNATURES = {
     "fn_vocab_logsoftmax_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_out_head_f32": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_float, vp, vp, C.c_int, vp]),
     "fn_vocab_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, vp]),
+    "fn_vocab_sample": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),
     "fn_time_logsoftmax_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_latent_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

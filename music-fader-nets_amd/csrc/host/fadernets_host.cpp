@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../../include/fadernets_host.h"
+#include "sample_host.h"
 
 namespace {
 
@@ -556,6 +557,11 @@ int fn_best_tokens_host(const uint64_t* best, int steps, int B, int V, int32_t* 
     for (int t = 0; t < steps; ++t)
         for (int b = 0; b < B; ++b) tokens[(long)b * tok_ld + t] = V - 1 - (int)(uint32_t)(best[(long)t * B + b] & 0xffffffffull);
     return FN_OK;
+}
+
+int fn_vocab_sample_host(const float* logits, int B, int V, int ld, const FnSampleParams* params, int step, float* logp_out, int64_t logp_ld,
+                         int32_t* own_out, int own_ld, int32_t* tok_out, int tok_ld, float* u_out, void*) {
+    return fn_sample_host::vocab_sample(logits, B, V, ld, params, step, logp_out, logp_ld, own_out, own_ld, tok_out, tok_ld, u_out);
 }
 
 size_t fn_decode_ws_bytes_host(int B, int H, int) { return (size_t)4 * B * H * sizeof(float) + 16; }

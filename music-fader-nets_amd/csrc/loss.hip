@@ -82,6 +82,155 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float* __restri
     if (lane == 0) tok_out[(long)b * tok_ld] = am;
 }
 
+// seeded temperature / top-k / top-p draw (fn_vocab_sample, include/fadernets.h has the definition; no reference counterpart: the reference's
+// _sampling is the argmax above).  Geometry of vocab_argmax_kernel: one wavefront per row, 4 rows per workgroup, lane l holds e = l, l+64, ...
+// LDS per wavefront: V floats + V indices.  The wavefronts of a workgroup are independent but walk the same barriers, so a wavefront past
+// the last row works on row B-1 again and stores nothing.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__device__ __forceinline__ int fn_wave_sum_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int NE>      // entries per lane: V <= 64 NE
+__global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restrict__ logits, int B, int E, int ld,
+                                                           const FnSampleParams* __restrict__ params, int step, float* __restrict__ logp_out,
+                                                           long logp_ld, int* __restrict__ own_out, int own_ld, int* __restrict__ tok_out,
+                                                           int tok_ld, float* __restrict__ u_out) {
+    extern __shared__ __attribute__((aligned(16))) char fn_sample_lds[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wv;
+    const bool live = b < B;
+    const int br = live ? b : B - 1;
+    float* sf = reinterpret_cast<float*>(fn_sample_lds) + (size_t)wv * E;             // lp, then the sorted weights, then their prefix sums
+    int* si = reinterpret_cast<int*>(fn_sample_lds) + (size_t)4 * E + (size_t)wv * E;  // the sorted indices
+    // 1. max, first-index argmax, lse, lp: the instruction sequence of vocab_argmax_kernel
+    const float* x = logits + (long)br * ld;
+    float mx = -INFINITY;
+    int am = 0x7fffffff;
+    for (int e = lane; e < E; e += 64) {
+        const float v = x[e];
+        if (v > mx) { mx = v; am = e; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(mx, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        if (ov > mx || (ov == mx && oa < am)) { mx = ov; am = oa; }
+    }
+    float s = 0.f;
+    for (int e = lane; e < E; e += 64) s += expf(x[e] - mx);
+    s = fn_wave_sum(s);
+    const float lse = mx + logf(s);
+    if (logp_out && live)
+        for (int e = lane; e < E; e += 64) logp_out[(long)b * logp_ld + e] = x[e] - lse;
+    if (own_out && live && lane == 0) own_out[(long)b * own_ld] = am;
+    float lp[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        const int e = lane + 64 * k;
+        lp[k] = e < E ? x[e] - lse : -INFINITY;
+        if (e < E) sf[e] = lp[k];
+    }
+    const float lp_max = mx - lse;
+    // the parameters come from memory: clamped, as the host twin clamps them
+    const FnSampleParams pr = *params;
+    const int top_k = min(max(pr.top_k, 0), E);
+    float top_p = pr.top_p;
+    if (!(top_p <= 1.0f)) top_p = 1.0f;
+    if (top_p < FN_SAMPLE_MIN_P) top_p = FN_SAMPLE_MIN_P;
+    float inv_t = pr.inv_temperature;
+    if (inv_t != inv_t) inv_t = 1.0f;
+    inv_t = fminf(fmaxf(inv_t, FN_SAMPLE_MIN_INV_T), FN_SAMPLE_MAX_INV_T);
+    __syncthreads();
+    // 2. rank[e] = #{e' : lp[e'] > lp[e] or (lp[e'] == lp[e] and e' < e)}: a counting pass, every lane reads the same address
+    int rank[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k) rank[k] = 0;
+    for (int j = 0; j < E; ++j) {
+        const float v = sf[j];
+#pragma unroll
+        for (int k = 0; k < NE; ++k) rank[k] += (v > lp[k] || (v == lp[k] && j < lane + 64 * k)) ? 1 : 0;
+    }
+    __syncthreads();
+    // 3. scatter weight and index to the rank.  A rank is a count of OTHER entries, so it is below E whatever the logits hold
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        const int e = lane + 64 * k;
+        if (e < E) {
+            sf[rank[k]] = expf((lp[k] - lp_max) * inv_t);
+            si[rank[k]] = e;
+        }
+    }
+    __syncthreads();
+    // 4. inclusive prefix sums of the sorted weights: lane l owns entries per*l .. per*l + per - 1, sums them in order, then a scan over the lanes
+    const int per = (E + 63) >> 6;
+    float c[NE];
+    float run = 0.f;
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        const int j = per * lane + k;
+        if (k < per) run += j < E ? sf[j] : 0.f;
+        c[k] = run;
+    }
+    float tot = run;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(tot, o, 64);
+        if (lane >= o) tot += up;
+    }
+    float before = __shfl_up(tot, 1, 64);
+    if (lane == 0) before = 0.f;
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        c[k] = before + c[k];
+        const int j = per * lane + k;
+        if (k < per && j < E) sf[j] = c[k];
+    }
+    __syncthreads();
+    // 5. the kept set is a prefix of the sorted order: top-k, then the prefix holding top_p of its mass.  Both searches are COUNTS over all entries, as the
+    // definition has them: c is non-decreasing inside a lane's block, but across a block border the fp32 sums can step down by an ulp
+    const int n = top_k ? top_k : E;
+    int m = n;
+    if (top_p < 1.0f) {
+        const float thr = top_p * sf[n - 1];
+        int below = 0;
+#pragma unroll
+        for (int k = 0; k < NE; ++k) {
+            const int j = per * lane + k;
+            below += (k < per && j < n && c[k] < thr) ? 1 : 0;
+        }
+        m = min(fn_wave_sum_i32(below) + 1, n);
+    }
+    // 6. the draw: u in [0, 1) from Philox4x32-10 on (row, step, offset), keyed by the seed; j = #{j < m : not c[j] > u c[m-1]}
+    uint32_t r4[4];
+    philox4x32_10((uint32_t)b, (uint32_t)step, pr.offset_lo, pr.offset_hi, pr.seed_lo, pr.seed_hi, r4);
+    const float u = (float)(r4[0] >> 8) * 0x1p-24f;
+    const float t = u * sf[m - 1];
+    int notabove = 0;
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        const int j = per * lane + k;
+        notabove += (k < per && j < m && !(c[k] > t)) ? 1 : 0;
+    }
+    const int j = min(fn_wave_sum_i32(notabove), m - 1);
+    if (live && lane == 0) {
+        tok_out[(long)b * tok_ld] = min(max(si[j], 0), E - 1);      // in range even for rows of NaNs (their ranks collide)
+        if (u_out) u_out[b] = u;
+    }
+}
+
 // ------------------------------------------------------------------ masked probability sums (GLSR, trainer_glsr.py:121-139) -----
 // per row of logits: P_a = sum over tokens [lo_a, hi_a) of softmax(logits) for two token ranges (played notes 2..89, time separators
 // 180..277 in the reference).  sums [rows][2].  Gradient form: dlogits[u] = p_u (a_u - (w0 P_0 + w1 P_1)),  a_u = w0 [u in range 0] +
@@ -544,6 +693,21 @@ int fn_vocab_argmax(const float* logits, int B, int E, int ld, float* logp_out, 
     if (B <= 0 || E <= 0 || ld < E) return FN_E_SHAPE;
     hipLaunchKernelGGL(vocab_argmax_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, B, E, ld, logp_out,
                        (long)logp_ld, tok_out, tok_ld);
+    FN_CHECK_LAUNCH();
+    return FN_OK;
+}
+
+int fn_vocab_sample(const float* logits, int B, int V, int ld, const FnSampleParams* params_dev, int step, float* logp_out, int64_t logp_ld,
+                    int32_t* own_out, int own_ld, int32_t* tok_out, int tok_ld, float* u_out, void* stream) {
+    if (!logits || !params_dev || !tok_out) return FN_E_NULL;
+    if (B <= 0 || V < 1 || V > FN_SAMPLE_MAX_V || ld < V || step < 0) return FN_E_SHAPE;
+    const size_t lds = (size_t)4 * V * (sizeof(float) + sizeof(int32_t));
+    if (V <= 384)
+        hipLaunchKernelGGL(vocab_sample_kernel<6>, dim3((B + 3) / 4), dim3(256), lds, (hipStream_t)stream, logits, B, V, ld, params_dev, step,
+                           logp_out, (long)logp_ld, own_out, own_ld, tok_out, tok_ld, u_out);
+    else
+        hipLaunchKernelGGL(vocab_sample_kernel<16>, dim3((B + 3) / 4), dim3(256), lds, (hipStream_t)stream, logits, B, V, ld, params_dev, step,
+                           logp_out, (long)logp_ld, own_out, own_ld, tok_out, tok_ld, u_out);
     FN_CHECK_LAUNCH();
     return FN_OK;
 }

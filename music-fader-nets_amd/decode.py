@@ -135,6 +135,94 @@ def continue_from(model, z, prompt, steps, want_logp=True):
     return logp, tokens
 
 
+def _sample_args(z, steps, temperature, top_k, top_p, seed, offset, prompt):
+    """validated (the 32 bytes of FnSampleParams as a CPU uint8 tensor, prompt int32 (Bi, steps) on z's device or None, its prefix mask or None, P);
+    ValueError before anything is launched"""
+    if not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError("steps: a positive int, got %r" % (steps,))
+    for name, v in (("temperature", temperature), ("top_p", top_p)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError("%s: a finite number, got %r" % (name, v))
+    if not temperature > 0:
+        raise ValueError("temperature > 0, got %r" % (temperature,))
+    if not 0 < top_p <= 1:
+        raise ValueError("0 < top_p <= 1, got %r" % (top_p,))
+    for name, v, hi in (("top_k", top_k, 1 << 31), ("seed", seed, 1 << 64), ("offset", offset, 1 << 64)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < hi:
+            raise ValueError("%s: an int in [0, 2^%d), got %r" % (name, hi.bit_length() - 1, v))
+    P, forced, mask = 0, None, None
+    if prompt is not None:
+        prompt = prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))
+        if prompt.dim() != 2 or prompt.shape[0] != z.shape[0] or prompt.shape[1] > steps:
+            raise ValueError("prompt: (%d, <= %d) tokens, got %s" % (z.shape[0], steps, tuple(prompt.shape)))
+        P = prompt.shape[1]
+        if P:
+            full = torch.zeros(z.shape[0], steps, dtype=prompt.dtype)
+            full[:, :P] = prompt.cpu()
+            forced, mask = _forced_args(z, steps, full, P)
+    with np.errstate(over="ignore"):
+        inv_t = np.float32(1.0) / np.float32(temperature)          # the kernel clamps what fp32 cannot hold
+    raw = np.zeros(1, dtype=[("seed", "<u8"), ("offset", "<u8"), ("inv_t", "<f4"), ("top_p", "<f4"), ("top_k", "<i4"), ("reserved", "<i4")])
+    raw["seed"], raw["offset"], raw["inv_t"], raw["top_p"], raw["top_k"] = int(seed), int(offset), inv_t, np.float32(top_p), int(top_k)
+    return torch.from_numpy(raw.view(np.uint8).copy()), forced, mask, P
+
+
+@torch.no_grad()
+def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, want_logp=True, prompt=None, use_graph=None):
+    """Seeded temperature / top-k / top-p sampling: z (Bi, 2Z+24) -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32).
+
+    tokens is the stream that was fed back: the draws, with tokens[:, :P] = prompt (Bi, P <= steps) when one is given; the log-probs are the
+    model's own, untempered, of every step: logp.gather(-1, tokens) scores the sample.  Step i of row b draws with the uniform
+    Philox4x32-10(key = seed, counter = (b, i, offset)) from the distribution include/fadernets.h defines at fn_vocab_sample: softmax(logits /
+    temperature) restricted to the top_k most likely tokens (0: all), then to the shortest prefix of them that holds top_p of their mass.
+    The same (seed, offset) gives the same uniforms on every path and batch size, and the same tokens on the same path (the paths' logits differ
+    in their low bits); top_k = 1 is greedy_decode.
+
+    The reference has no counterpart (its _sampling is the argmax, gmm_model.py:73-80).  Every batch size takes the per-token launches -
+    scan steps below Engine.cell_decode_rows rows, cells from there on - with the output GEMM and fn_vocab_sample as the head; the
+    one-launch decode kernel is not involved.  On the GPU the launches are captured once per (Bi, steps, want_logp, P, arithmetic) into
+    Engine._sample_graphs (at most MAX_MASKED_GRAPHS of them with a prompt: the oldest goes); z, the prompt and the 32 parameter bytes are copied
+    into the graph's buffers, so any seed or setting replays it."""
+    params, forced, mask, P = _sample_args(z, steps, temperature, top_k, top_p, seed, offset, prompt)
+    eng = model.engine()
+    z = z.float().contiguous()
+    if use_graph is None:
+        use_graph = z.is_cuda
+    if not use_graph:
+        logp, tokens = _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask, sample=params.to(z.device))
+    else:
+        cache = eng.__dict__.setdefault("_sample_graphs", {})
+        key = (z.shape[0], steps, bool(want_logp), P, z.shape[0] >= eng.cell_decode_rows,
+               bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)), getattr(eng.ops, "cell_x6_rows", None),
+               bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)))
+        ent = cache.get(key)
+        if ent is None:
+            zs, ps = z.clone(), params.to(z.device)
+            fs = None if forced is None else forced.clone()
+            tokens = torch.zeros(z.shape[0], steps, dtype=torch.int32, device=z.device)
+            logp = torch.empty(z.shape[0], steps, E_VOCAB, device=z.device) if want_logp else None
+            _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask, sample=ps)   # warm-up, as greedy_decode
+            g = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            getattr(eng.ops, "begin_capture", lambda: None)()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask, sample=ps)
+            ent = cache[key] = (g, zs, ps, fs, logp, tokens)
+            prompted = [k for k in cache if k[3]]
+            if len(prompted) > MAX_MASKED_GRAPHS:         # as greedy_decode bounds its masked graphs: every prompt length owns static logp / tokens buffers
+                del cache[prompted[0]]
+        g, zs, ps, fs, logp, tokens = ent
+        zs.copy_(z)
+        ps.copy_(params)
+        if fs is not None:
+            fs.copy_(forced)
+        g.replay()
+        logp, tokens = (None if logp is None else logp.clone()), tokens.clone()
+    if P:
+        tokens[:, :P] = forced[:, :P]
+    return logp, tokens
+
+
 def _single_launch_ok(eng, z):
     """small batches decode as ONE launch (fn_decode_greedy: weight slices resident in LDS, activations handed over through L2)"""
     lo, hi = getattr(eng, "single_launch_skip", (0, -1))
@@ -167,7 +255,9 @@ def _decode_single_launch(eng, z, steps, want_logp, forced=None, mask=None):
     return logp, tokens
 
 
-def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, forced=None, mask=None):
+def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, forced=None, mask=None, sample=None):
+    """sample: None, or the 32 device bytes of FnSampleParams - then `tokens` receives the DRAWN tokens (fn_vocab_sample in place of the argmax
+    launch, never the fused output layer), which are what the next step is fed; forced / mask keep their meaning (a prompt)"""
     ops, P, H = eng.ops, eng.p, eng.H
     Bi = z.shape[0]
     dev = z.device
@@ -187,13 +277,20 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
     nf = ops.frag_floats(Bi, H)
     hf0 = [eng.buf("dec_hf0_a", (nf,)), eng.buf("dec_hf0_b", (nf,))]
     hf1 = [eng.buf("dec_hf1_a", (nf,)), eng.buf("dec_hf1_b", (nf,))]
+
+    def head(i):
+        if sample is None:
+            ops.vocab_argmax(logits, E_VOCAB, logp[:, i, :] if want_logp else None, tokens[:, i])
+        else:
+            ops.vocab_sample(logits, E_VOCAB, sample, i, logp[:, i, :] if want_logp else None, tokens[:, i])
+
     if Bi >= eng.cell_decode_rows:
         # thousands of rows: every cell is ONE MFMA launch with the gates in its epilogue (fn_gru_cell_f32: LDS-free loop above 512 rows); layer 2 takes its input
         # projection in the same K loop - 3 launches + argmax per token instead of 4 + argmax, and no [B][3H] round trip
         # tokens only (the evaluators' sweeps): the output layer takes the argmax into its epilogue (fn_out_argmax_f32: packed (logit, column)
         # words by 64-bit atomic max, no logits, no argmax launch) and the next layer-1 cell reads its token from the packed word -
         # 3 launches per token; the int32 tokens are unpacked once at the end
-        fused = not want_logp and getattr(eng, "fused_argmax", True) and hasattr(ops, "out_argmax")
+        fused = not want_logp and sample is None and getattr(eng, "fused_argmax", True) and hasattr(ops, "out_argmax")
         best = eng.buf("dec_best", (max(steps, alloc_steps or 0), Bi), dtype=torch.int64)[:steps] if fused else None
         if fused:
             best.zero_()
@@ -211,7 +308,7 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
                 ops.out_argmax(hx1[cur][0], P["linear_out_g.weight"], P["linear_out_g.bias"], best[i])
             else:
                 ops.gemm(hx1[cur][0], P["linear_out_g.weight"], logits[:, :E_VOCAB], bias=P["linear_out_g.bias"])
-                ops.vocab_argmax(logits, E_VOCAB, logp[:, i, :] if want_logp else None, tokens[:, i])
+                head(i)
         if fused:
             ops.best_tokens(best, E_VOCAB, tokens)
         return logp, tokens
@@ -226,7 +323,7 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
                               h0=hx0[cur][0] if i == 0 else hx1[prv][0], h0_frag=hf0[cur] if i == 0 else hf1[prv], h_last_frag=hf1[cur],
                               gx_dense=gx2, h_all=hx1[cur])], persistent=False)
         ops.gemm(hx1[cur][0], P["linear_out_g.weight"], logits[:, :E_VOCAB], bias=P["linear_out_g.bias"])
-        ops.vocab_argmax(logits, E_VOCAB, logp[:, i, :] if want_logp else None, tokens[:, i])
+        head(i)
     return logp, tokens
 
 
@@ -246,7 +343,7 @@ def clean_output(out):
 
 
 @torch.no_grad()
-def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None):
+def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None, sample=None):
     """Batched RhythmEvaluator.shift / NoteEvaluator.shift (test_class.py:233-254, :282-303) and the notebook's
     lambda*shift-vector transfer (cells 11 + 15): every (sample, fader value) pair is one row of ONE decode batch.
 
@@ -256,6 +353,7 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
     eps: (eps_r, eps_n), each (n, Z) - one draw per sample, shared by its V values - or (n, V, Z) - one draw per (sample, value),
     which is what V separate reference calls consume; None = drawn here (r first, then n).
     prompt: (P,) or (1, P) tokens every (sample, value) row starts with (continue_from), or None.
+    sample: None = the greedy decode; a dict of sample_decode's keywords (temperature, top_k, top_p, seed, offset) = drawn continuations.
     Returns (tokens (n, V, steps) int32, z0 (n,) or (n, V): the value of z_which[:, 0] before the change; which="both": z_r's)."""
     if which not in ("r", "n", "both") or mode not in ("set", "shift") or (which == "both" and mode == "set"):
         raise ValueError("which in {r, n, both}, mode in {set, shift}; 'both' only with mode='shift'")
@@ -286,10 +384,15 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
                     tgt += vals.view(1, V, 1) * (lk.weight.data[1] - lk.weight.data[0]).view(1, 1, Z)
         c = chroma.float().to(dev).unsqueeze(1).expand(n, V, chroma.shape[-1])
         z = torch.cat([zr, zn, c], dim=2).reshape(n * V, -1)
-        if prompt is None:
+        pr = None if prompt is None else (prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))).reshape(1, -1)
+        if sample is not None:
+            unknown = set(sample) - {"temperature", "top_k", "top_p", "seed", "offset"}
+            if unknown:
+                raise ValueError("sample: keys among temperature, top_k, top_p, seed, offset; got %s" % sorted(unknown, key=str))
+            _, tok = sample_decode(model, z, steps, want_logp=False, prompt=None if pr is None else pr.expand(n * V, pr.shape[1]), **sample)
+        elif prompt is None:
             _, tok = greedy_decode(model, z, steps, want_logp=False)
         else:
-            pr = (prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))).reshape(1, -1)
             _, tok = continue_from(model, z, pr.expand(n * V, pr.shape[1]), steps, want_logp=False)
         return tok.view(n, V, steps), z0
     finally:

@@ -582,6 +582,22 @@ class HipOps:
         _lib.check(self.lib.fn_vocab_argmax(pl, B, E, ld, _p(logp_out), lp_ld, _p(tok_out), tok_out.stride(0) if tok_out.dim() else 1,
                                             self.stream()), "fn_vocab_argmax")
 
+    def vocab_sample(self, logits, E, params, step, logp_out, tok_out, own_out=None, u_out=None):
+        """fn_vocab_sample: logits [B][ld]; params: the 32 bytes of FnSampleParams on the device; logp_out: 2-D view [B][E] (any row stride) or None;
+        tok_out (the drawn tokens) / own_out (the first-index argmax, or None): int32 1-D views (any stride); u_out: [B] floats or None."""
+        pl, B, _, ld = _mat(logits, "logits")
+        _chk(tok_out, torch.int32, "tok_out"), _chk(own_out, torch.int32, "own_out")
+        _dense(params, torch.uint8, "params"), _dense(u_out, name="u_out")
+        if params.numel() != C.sizeof(_lib.FnSampleParams) or (u_out is not None and u_out.numel() < B):
+            raise RuntimeError("vocab_sample: params holds %d bytes, FnSampleParams %d; u_out one float per row" % (params.numel(), C.sizeof(_lib.FnSampleParams)))
+        lp_ld = 0
+        if logp_out is not None:
+            _chk(logp_out, name="logp_out")
+            lp_ld = logp_out.stride(0)
+        _lib.check(self.lib.fn_vocab_sample(pl, B, E, ld, _p(params), step, _p(logp_out), lp_ld, _p(own_out),
+                                            0 if own_out is None else (own_out.stride(0) if own_out.dim() else 1), _p(tok_out),
+                                            tok_out.stride(0) if tok_out.dim() else 1, _p(u_out), self.stream()), "fn_vocab_sample")
+
     def time_logsoftmax(self, logits, logp_bt=None, target=None, nll_bc=None, grad_scale=0.0, dlogits=None):
         _dense(logits, name="logits"), _dense(logp_bt, name="logp_bt"), _dense(target, torch.int32, "target")
         _dense(nll_bc, name="nll_bc"), _dense(dlogits, name="dlogits")
