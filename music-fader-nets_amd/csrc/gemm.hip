@@ -444,172 +444,91 @@ __global__ __launch_bounds__(NT) void gemm_tn_x6_kernel(int M, int N, int K, flo
 // hi*mid, hi*hi per 32 k; B pieces rounded, A pieces truncated): bit-identical results on K ranges of whole 32-k blocks; rows beyond the last row
 // of the matrix count as zeros (the kernel above runs them on the fp32 MFMA).
 // ---------------------------------------------------------------------------------------------------------
-// Producer wavefront of gemm_tn_x6w_kernel: operand columns [pcol, pcol + 4) of rows kbeg + 32 blk + 8 lg + j (j = 0..7) of P, block after block,
-// 8 loads per block into register set blk % NS.  In trip t the loads of block t + NS + 1 are requested, then block t + 2 (requested NS - 1 trips
-// ago) is cut into LDS stage (t + 2) % 3, barrier; the consumers multiply block t meanwhile and read block t + 1 ahead.
-// PLAIN loads, the compiler counts vmcnt: the steady-state trips are straight-line code (whole blocks only, no clamping, no branch between a request
-// and its use), for which hipcc emits exactly `s_waitcnt vmcnt(8 (NS - 1))` in front of the cut (checked in the ISA; Makefile target isa.checked
-// re-checks every build: csrc/check_isa_waits.py).  A first version with asm-statement loads and hand-counted waits passed every test, but its ISA
-// showed whole register sets copied (`v_mov_b64`) at the control-flow merges of the partial-block / tail paths while asm loads into them could be in
-// flight - the compiler cannot know: the hazard class of profiles/r05_x6_suite_soak.txt.  The last 2 NS + 1 blocks (the only ones that can be
-// partial) run through guarded code with clamped row addresses and zero-filled rows.
-template <bool RN>
-FN_DEVINL void x6w_produce(u32x4* __restrict__ lds, const float* __restrict__ P, long pld, long pcol, int ps, int lane, int kbeg, int kend, int nblk) {
-    constexpr int NS = X6W_NS;
-    const int lg = lane >> 4;
-    f32x4 fa[NS][8];
-    auto gload = [&](auto SET, int blk) __attribute__((always_inline)) {              // a whole block inside the matrix
-#ifndef X6W_EXP_NOLOAD
-        constexpr int set = decltype(SET)::value;
-        const float* p0 = P + ((long)kbeg + 32 * blk + 8 * lg) * pld + pcol;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fa[set][j] = x6w_ld(p0 + j * pld);
-#endif
-    };
-    auto gload_safe = [&](auto SET, int blk) __attribute__((always_inline)) {         // any block: rows beyond the matrix are read from its last row
-#ifndef X6W_EXP_NOLOAD
-        constexpr int set = decltype(SET)::value;
-        const long k0 = (long)kbeg + 32 * blk + 8 * lg;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fa[set][j] = x6w_ld(P + min(k0 + j, (long)kend - 1) * pld + pcol);
-#endif
-    };
-    auto cut = [&](auto SET, int blk, int stage, bool zero_tail) __attribute__((always_inline)) {      // block blk: register set blk % NS -> LDS stage blk % 3
-        constexpr int set = decltype(SET)::value;
-        if (zero_tail) {                                 // rows beyond the matrix count as zeros (selects, no branch)
-            const long k0 = (long)kbeg + 32 * blk + 8 * lg;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const bool in = k0 + j < kend;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) fa[set][j][e] = in ? fa[set][j][e] : 0.f;
-            }
-        }
-        u32x4* dst = lds + stage * X6W_STAGE + ps * X6W_SET + lane;
-#ifdef X6W_EXP_NOCUT
-        if (blk > 1) return;
-#endif
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            bf16x8 h, m, l;
-            fn_split8<RN>(fa[set], a, h, m, l);
-            dst[(a * 3 + 0) * 64] = __builtin_bit_cast(u32x4, h);
-            dst[(a * 3 + 1) * 64] = __builtin_bit_cast(u32x4, m);
-            dst[(a * 3 + 2) * 64] = __builtin_bit_cast(u32x4, l);
-        }
-    };
-    // prologue: blocks 0 and 1 cut, blocks 2 .. NS requested
-    x6w_for<NS>([&](auto I) __attribute__((always_inline)) {
-        if (decltype(I)::value < nblk) gload_safe(I, decltype(I)::value);
-    });
-    cut(x6w_ic<0>{}, 0, 0, true);
-    if (nblk > 1) cut(x6w_ic<1>{}, 1, 1, true);
-    if (nblk > NS) gload_safe(x6w_ic<0>{}, NS);
-    x6w_barrier_p();
-    int stage = 2, t = 0;
-    // steady state, NS trips per pass (static register sets): trip t (t % NS == r) requests block t + NS + 1 -> set (r + 1) % NS and cuts block
-    // t + 2 (set (r + 2) % NS, stage (t + 2) % 3).  Only whole blocks: t + NS + 1 <= nblk - 2 for every trip of the pass.
-    // Request and cut are INTERLEAVED: two loads of the new block in front of every quarter of the cut.  Issued as one burst the 8 loads keep the
-    // wave at the vector-memory queue until most of them have been taken (a CU's address path takes ~30 clocks per 1 KB wave load: measured, the
-    // loads of a block cost the CU ~1000 clocks), and the address path then idles while the wave splits: loads + cut ran as long as their sum.
-    auto fused = [&](auto LS, int lblk, auto CS, int stage_) __attribute__((always_inline)) {
-        constexpr int ls = decltype(LS)::value, cs = decltype(CS)::value;
-        const float* p0 = P + ((long)kbeg + 32 * lblk + 8 * lg) * pld + pcol;
-        u32x4* dst = lds + stage_ * X6W_STAGE + ps * X6W_SET + lane;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-#ifndef X6W_EXP_NOLOAD
-            fa[ls][2 * a] = x6w_ld(p0 + (2 * a) * pld);
-            fa[ls][2 * a + 1] = x6w_ld(p0 + (2 * a + 1) * pld);
-#endif
-            bf16x8 h, m, l;
-            fn_split8<RN>(fa[cs], a, h, m, l);
-            dst[(a * 3 + 0) * 64] = __builtin_bit_cast(u32x4, h);
-            dst[(a * 3 + 1) * 64] = __builtin_bit_cast(u32x4, m);
-            dst[(a * 3 + 2) * 64] = __builtin_bit_cast(u32x4, l);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-#pragma unroll 1
-    for (; t + 2 * NS + 1 < nblk; t += NS) {
-        x6w_for<NS>([&](auto R) __attribute__((always_inline)) {
-            constexpr int r = decltype(R)::value;
-            if (X6W_INTERLEAVE) {
-                fused(x6w_ic<(r + 1) % NS>{}, t + r + NS + 1, x6w_ic<(r + 2) % NS>{}, stage);
-            } else {
-                gload(x6w_ic<(r + 1) % NS>{}, t + r + NS + 1);
-                cut(x6w_ic<(r + 2) % NS>{}, t + r + 2, stage, false);
-            }
-            stage = stage == 2 ? 0 : stage + 1;
-            x6w_barrier_p();
-        });
+// What the two TN producer / consumer kernels (128 x 128 tiles here, 128 x 256 tiles below) share: their arguments, the producers' column clamp and
+// row loads, the walk over (tile, K range) items and the epilogue.
+struct X6Tn {
+    int M, N, K;
+    float alpha;
+    const float* A;
+    long lda;
+    const float* B;
+    long ldb;
+    float beta;
+    float* C;
+    long ldc;
+    const float* bias;
+    int ksplit_len;
+    float* slabs;
+    const float* A2;
+    long lda2;
+    int msplit;
+};
+// 64 operand columns from pc0 on, of A (two sources: rows of A^T from msplit on come from A2) or of B: the operand, its leading dimension and the
+// column offset of this lane's 16-byte loads, kept inside the columns the operand REALLY has (see gemm_tn_body)
+FN_DEVINL long x6_tn_pcol(const X6Tn& g, bool pa, int pc0, int li, const float*& P, long& pld) {
+    P = pa ? g.A : g.B;
+    pld = pa ? g.lda : g.ldb;
+    long ncols = pa ? (long)g.M : (long)g.N, rel = pc0;
+    if (pa && g.A2 != nullptr) {
+        if (pc0 >= g.msplit) { P = g.A2; pld = g.lda2; ncols = (long)g.M - g.msplit; rel = pc0 - g.msplit; }
+        else ncols = g.msplit;
     }
-    // the last <= 2 NS + 1 trips (t is a multiple of NS here: the register sets stay static)
-    x6w_for<2 * NS + 1>([&](auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value, r = i % NS;
-        if (t + i < nblk) {
-            if (t + i + NS + 1 < nblk) gload_safe(x6w_ic<(r + 1) % NS>{}, t + i + NS + 1);
-            if (t + i + 2 < nblk) cut(x6w_ic<(r + 2) % NS>{}, t + i + 2, stage, true);
-            stage = stage == 2 ? 0 : stage + 1;
-            x6w_barrier_p();
-        }
-    });
+    long pcol = min(rel + 4 * li, ((ncols - 1) >> 2) << 2);
+    if (rel >= ncols) pcol = ((ncols - 1) >> 2) << 2;                    // a set entirely beyond the matrix: any legal column (never stored)
+    return pcol;
 }
-
-// one (output tile, K range) of gemm_tn_x6w_kernel: both roles run 1 + nblk barriers, and behind the last one no stage is read any more (the reads in flight fetch
-// values nobody uses): the next item of a workgroup that walks several of them may be cut into the stages at once
-FN_DEVINL void gemm_tn_x6w_kernel_item(int M, int N, int K, float alpha, const float* __restrict__ A, long lda,
-                                                              const float* __restrict__ B, long ldb, float beta, float* __restrict__ C, long ldc,
-                                                              const float* __restrict__ bias, int ksplit_len, float* __restrict__ slabs,
-                                                              const float* __restrict__ A2, long lda2, int msplit, u32x4* __restrict__ x6w_lds, int ntn, int tile, int zk) {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int mb = (tile / ntn) * 128, nb = (tile % ntn) * 128;          // the workgroup's output tile
-    const int li = lane & 15, lg = lane >> 4;
-    const int kbeg = zk * ksplit_len, kend = min(K, kbeg + ksplit_len);
-    const int nblk = (kend - kbeg + 31) >> 5;
-    if (nblk <= 0) return;                               // (the host never launches an empty K range)
-
-    if (X6W_SWAP ? wave < 4 : wave >= 4) {
-        if (X6W_PRIO_P) __builtin_amdgcn_s_setprio(X6W_PRIO_P);
-        // ---- producer: set ps = 64 operand columns (sets 0, 1: A columns mb + 64 ps; sets 2, 3: B columns nb + 64 (ps - 2)) ----
-        const int ps = wave & 3;
-        const bool pa = ps < 2;
-        const float* P = pa ? A : B;
-        long pld = pa ? lda : ldb;
-        // column offset of this lane's 16-byte loads, kept inside the columns the operand REALLY has (see gemm_tn_body)
-        const int pc0 = pa ? mb + 64 * ps : nb + 64 * (ps - 2);
-        long ncols = pa ? (long)M : (long)N, rel = pc0;
-        if (pa && A2 != nullptr) {
-            if (pc0 >= msplit) { P = A2; pld = lda2; ncols = (long)M - msplit; rel = pc0 - msplit; }
-            else ncols = msplit;
-        }
-        long pcol = min(rel + 4 * li, ((ncols - 1) >> 2) << 2);
-        if (rel >= ncols) pcol = ((ncols - 1) >> 2) << 2;                // a set entirely beyond the matrix: any legal column (never stored)
-        if (pa) x6w_produce<false>(x6w_lds, P, pld, pcol, ps, lane, kbeg, kend, nblk);
-        else x6w_produce<true>(x6w_lds, P, pld, pcol, ps, lane, kbeg, kend, nblk);
-        return;
+// rows k0 .. k0 + N - 1 of a producer lane's column quad: rows beyond the matrix are read from its last row ... and count as zeros (selects, no branch)
+template <int N>
+FN_DEVINL void x6_tn_load(f32x4 (&v)[N], const float* __restrict__ P, long pld, long pcol, long k0, int kend) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = x6w_ld(P + min(k0 + j, (long)kend - 1) * pld + pcol);
+}
+template <int N>
+FN_DEVINL void x6_tn_zero_tail(f32x4 (&v)[N], long k0, int kend) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const bool in = k0 + j < kend;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[j][e] = in ? v[j][e] : 0.f;
     }
-
-    // ---- consumer ----
-    if (X6W_PRIO_C) __builtin_amdgcn_s_setprio(X6W_PRIO_C);
-    const int wm = (wave >> 1) & 1, wn = wave & 1;
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    x6w_consume(x6w_lds, wm, wn, lane, nblk, acc);
-    const int m0 = mb + 64 * wm, n0 = nb + 64 * wn;
-    const int colb = n0 + 4 * li;
-    if (slabs != nullptr && (N & 3) == 0) {              // split-K slabs: 16-byte stores
+}
+// The (tile, K range) items of a workgroup.  Both roles run 1 + nblk barriers per item, and behind the last one no stage is read any more (the reads in
+// flight fetch values nobody uses): the next item of a workgroup that walks several of them may be cut into the stages at once.
+// item(mb, nb, zk): output tile at (mb, nb), K range zk
+template <int BN, class F>
+FN_DEVINL void x6_tn_walk(const X6Tn& g, F&& item) {
+    const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + 127) / 128;
+    if (gridDim.z == 1 && g.slabs != nullptr) {          // K ranges dealt to the XCDs (see gemm_tn_body); a workgroup walks items blockIdx.x, + gridDim.x, ...
+        const int S = (g.K + g.ksplit_len - 1) / g.ksplit_len, items = S * ntn * ntm;      // (gridDim.x < items only when it is a multiple of 8: the items of a workgroup stay on its XCD)
+#pragma unroll 1
+        for (int v = blockIdx.x; v < items; v += gridDim.x) {
+            const int c = v & 7, q = v >> 3, tile = q % (ntn * ntm);
+            item((tile / ntn) * 128, (tile % ntn) * BN, c * (S >> 3) + q / (ntn * ntm));
+        }
+    } else {
+        const int tile = fn_xcd_remap(blockIdx.x, ntn * ntm);
+        item((tile / ntn) * 128, (tile % ntn) * BN, (int)blockIdx.z);
+    }
+}
+// epilogue of a consumer wave: 4 x NB accumulator tiles (row 4 (4 lg + r) + a of m0; column tile b = columns 64 (b >> 2) + 4 li + (b & 3) of n0 - a
+// lane's four column tiles of a set are four consecutive columns) to the split-K slab of K range zk (16-byte stores when the rows allow it) or,
+// unsplit, alpha / bias / beta to C
+template <int NB>
+FN_DEVINL void x6_tn_store(const X6Tn& g, const f32x4 (&acc)[4][NB], int m0, int n0, int li, int lg, int zk) {
+    if (g.slabs != nullptr && (g.N & 3) == 0) {          // split-K slabs: 16-byte stores
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = m0 + 4 * (lg * 4 + r) + a;
-                if (row >= M || colb >= N) continue;
-                const f32x4 v = {acc[a][0][r], acc[a][1][r], acc[a][2][r], acc[a][3][r]};
-                *reinterpret_cast<f32x4*>(slabs + ((long)zk * M + row) * N + colb) = v;
+                if (row >= g.M) continue;
+#pragma unroll
+                for (int bs = 0; bs < NB / 4; ++bs) {
+                    const int col = n0 + 64 * bs + 4 * li;
+                    if (col >= g.N) continue;
+                    const f32x4 v = {acc[a][4 * bs][r], acc[a][4 * bs + 1][r], acc[a][4 * bs + 2][r], acc[a][4 * bs + 3][r]};
+                    *reinterpret_cast<f32x4*>(g.slabs + ((long)zk * g.M + row) * g.N + col) = v;
+                }
             }
         return;
     }
@@ -618,22 +537,86 @@ FN_DEVINL void gemm_tn_x6w_kernel_item(int M, int N, int K, float alpha, const f
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = m0 + 4 * (lg * 4 + r) + a;
-            if (row >= M) continue;
+            if (row >= g.M) continue;
 #pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int col = colb + b;
-                if (col >= N) continue;
+            for (int b = 0; b < NB; ++b) {
+                const int col = n0 + 64 * (b >> 2) + 4 * li + (b & 3);
+                if (col >= g.N) continue;
                 const float v = acc[a][b][r];
-                if (slabs) {
-                    slabs[((long)zk * M + row) * N + col] = v;
+                if (g.slabs) {
+                    g.slabs[((long)zk * g.M + row) * g.N + col] = v;
                 } else {
-                    float o = alpha * v;
-                    if (bias) o += bias[col];
-                    if (beta != 0.f) o += beta * C[(long)row * ldc + col];
-                    C[(long)row * ldc + col] = o;
+                    float o = g.alpha * v;
+                    if (g.bias) o += g.bias[col];
+                    if (g.beta != 0.f) o += g.beta * g.C[(long)row * g.ldc + col];
+                    g.C[(long)row * g.ldc + col] = o;
                 }
             }
         }
+}
+
+// Producer wavefront of gemm_tn_x6w_kernel (trip schedule: x6w_trips, x6w_core.h): operand columns [pcol, pcol + 4) of rows kbeg + 32 blk + 8 lg + j
+// (j = 0..7) of P, 8 loads per block (`s_waitcnt vmcnt(8 (NS - 1))` in front of a steady-state cut), cut into set ps of stage blk % 3.  Fused trip:
+// two loads of the new block in front of every quarter of the cut.
+template <bool RN>
+FN_DEVINL void x6w_produce(u32x4* __restrict__ lds, const float* __restrict__ P, long pld, long pcol, int ps, int lane, int kbeg, int kend, int nblk) {
+    constexpr int NS = X6W_NS;
+    const int lg = lane >> 4;
+    f32x4 fa[NS][8];
+    auto request = [&](auto SET, int blk) __attribute__((always_inline)) {
+        x6_tn_load(fa[decltype(SET)::value], P, pld, pcol, (long)kbeg + 32 * blk + 8 * lg, kend);
+    };
+    auto cut = [&](auto SET, int blk, int stage) __attribute__((always_inline)) {
+        constexpr int set = decltype(SET)::value;
+        x6_tn_zero_tail(fa[set], (long)kbeg + 32 * blk + 8 * lg, kend);
+        u32x4* dst = lds + stage * X6W_STAGE + ps * X6W_SET + lane;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) x6w_cut<RN>(dst, a, fa[set]);
+    };
+    auto fused = [&](auto LS, int lblk, auto CS, int, int stage) __attribute__((always_inline)) {
+        constexpr int ls = decltype(LS)::value, cs = decltype(CS)::value;
+        const float* p0 = P + ((long)kbeg + 32 * lblk + 8 * lg) * pld + pcol;
+        u32x4* dst = lds + stage * X6W_STAGE + ps * X6W_SET + lane;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            fa[ls][2 * a] = x6w_ld(p0 + (2 * a) * pld);
+            fa[ls][2 * a + 1] = x6w_ld(p0 + (2 * a + 1) * pld);
+            x6w_cut<RN>(dst, a, fa[cs]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    x6w_trips<NS, 2, true>(nblk, request, cut, fused);
+}
+
+// one (output tile, K range) of gemm_tn_x6w_kernel
+FN_DEVINL void gemm_tn_x6w_kernel_item(const X6Tn& g, u32x4* __restrict__ x6w_lds, int mb, int nb, int zk) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int li = lane & 15, lg = lane >> 4;
+    const int kbeg = zk * g.ksplit_len, kend = min(g.K, kbeg + g.ksplit_len);
+    const int nblk = (kend - kbeg + 31) >> 5;
+    if (nblk <= 0) return;                               // (the host never launches an empty K range)
+
+    if (wave >= 4) {
+        // ---- producer: set ps = 64 operand columns (sets 0, 1: A columns mb + 64 ps; sets 2, 3: B columns nb + 64 (ps - 2)) ----
+        const int ps = wave & 3;
+        const bool pa = ps < 2;
+        const float* P;
+        long pld;
+        const long pcol = x6_tn_pcol(g, pa, pa ? mb + 64 * ps : nb + 64 * (ps - 2), li, P, pld);
+        if (pa) x6w_produce<false>(x6w_lds, P, pld, pcol, ps, lane, kbeg, kend, nblk);
+        else x6w_produce<true>(x6w_lds, P, pld, pcol, ps, lane, kbeg, kend, nblk);
+        return;
+    }
+
+    // ---- consumer ----
+    const int wm = (wave >> 1) & 1, wn = wave & 1;
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    x6w_consume(x6w_lds, wm, wn, lane, nblk, acc);
+    x6_tn_store(g, acc, mb + 64 * wm, nb + 64 * wn, li, lg, zk);
 }
 
 __global__ __launch_bounds__(X6W_NT) void gemm_tn_x6w_kernel(int M, int N, int K, float alpha, const float* __restrict__ A, long lda,
@@ -641,17 +624,8 @@ __global__ __launch_bounds__(X6W_NT) void gemm_tn_x6w_kernel(int M, int N, int K
                                                               const float* __restrict__ bias, int ksplit_len, float* __restrict__ slabs,
                                                               const float* __restrict__ A2, long lda2, int msplit) {
     extern __shared__ __attribute__((aligned(16))) u32x4 x6w_lds[];      // [3 stages][4 sets][4 tiles][3 pieces][64 lanes]
-    const int ntn = (N + 127) / 128, ntm = (M + 127) / 128;
-    if (gridDim.z == 1 && slabs != nullptr) {            // K ranges dealt to the XCDs (see gemm_tn_body); a workgroup walks items blockIdx.x, + gridDim.x, ...
-        const int S = (K + ksplit_len - 1) / ksplit_len, items = S * ntn * ntm;      // (gridDim.x < items only when it is a multiple of 8: the items of a workgroup stay on its XCD)
-#pragma unroll 1
-        for (int v = blockIdx.x; v < items; v += gridDim.x) {
-            const int c = v & 7, q = v >> 3;
-            gemm_tn_x6w_kernel_item(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, ksplit_len, slabs, A2, lda2, msplit, x6w_lds, ntn, q % (ntn * ntm), c * (S >> 3) + q / (ntn * ntm));
-        }
-    } else {
-        gemm_tn_x6w_kernel_item(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, ksplit_len, slabs, A2, lda2, msplit, x6w_lds, ntn, fn_xcd_remap(blockIdx.x, ntn * ntm), blockIdx.z);
-    }
+    const X6Tn g = {M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, ksplit_len, slabs, A2, lda2, msplit};
+    x6_tn_walk<128>(g, [&](int mb, int nb, int zk) __attribute__((always_inline)) { gemm_tn_x6w_kernel_item(g, x6w_lds, mb, nb, zk); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -663,107 +637,38 @@ __global__ __launch_bounds__(X6W_NT) void gemm_tn_x6w_kernel(int M, int N, int K
 // B: rounded ones, six products smallest first, as everywhere.  Runs where the decoder pipeline turns layer-1 states into layer-2 gate inputs
 // (gx2 = hx0 W_ih2^T per 32-step chunk) and gate gradients into state gradients (dhx0 = dgx2 W_ih2): 116 / 102 us per launch on the fp32 MFMA.
 // ---------------------------------------------------------------------------------------------------------
+// (trip schedule: x6w_trips; whole blocks only here: K % 32 == 0.  Fused trip: the two loads of row 4 r + e of the new block in front of the cut of tile e)
 template <bool RN>
 FN_DEVINL void x6w_produce_nt(u32x4* __restrict__ lds, const float* __restrict__ P, long pld, int ps, int lane, int nblk) {
     constexpr int NS = X6W_NS;
     const int r = lane >> 2, q = lane & 3;
     f32x4 fa[NS][8];                                     // [set][2 e + j]: row 4 r + e, k = 8 q + 4 j ..
     const float* base = P + (long)(4 * r) * pld + 8 * q;
-    auto gload = [&](auto SET, int blk) __attribute__((always_inline)) {
+    auto ld_row = [&](auto SET, const float* p0, int e) __attribute__((always_inline)) {
         constexpr int set = decltype(SET)::value;
-        const float* p0 = base + 32 * blk;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            fa[set][2 * e] = x6w_ld(p0 + e * pld);
-            fa[set][2 * e + 1] = x6w_ld(p0 + e * pld + 4);
-        }
+        fa[set][2 * e] = x6w_ld(p0 + e * pld);
+        fa[set][2 * e + 1] = x6w_ld(p0 + e * pld + 4);
     };
-    auto cut = [&](auto SET, int stage) __attribute__((always_inline)) {
-        constexpr int set = decltype(SET)::value;
+    auto request = [&](auto SET, int blk) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ld_row(SET, base + 32 * blk, e);
+    };
+    auto cut = [&](auto SET, int, int stage) __attribute__((always_inline)) {
+        u32x4* dst = lds + stage * X6W_STAGE + ps * X6W_SET + r + 16 * q;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x6w_cut_row<RN>(dst, e, fa[decltype(SET)::value]);
+    };
+    auto fused = [&](auto LS, int lblk, auto CS, int, int stage) __attribute__((always_inline)) {
+        const float* p0 = base + 32 * lblk;
         u32x4* dst = lds + stage * X6W_STAGE + ps * X6W_SET + r + 16 * q;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float x[8], hi[8], r1[8], mi[8], r2[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = fa[set][2 * e + (j >> 2)][j & 3];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { hi[j] = RN ? fn_rn16(x[j]) : fn_top16(x[j]); r1[j] = x[j] - hi[j]; }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { mi[j] = RN ? fn_rn16(r1[j]) : fn_top16(r1[j]); r2[j] = r1[j] - mi[j]; }
-            u32x4 Hh, Mm, Ll;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Hh[j] = fn_pack_top16(hi[2 * j], hi[2 * j + 1]);
-                Mm[j] = fn_pack_top16(mi[2 * j], mi[2 * j + 1]);
-                Ll[j] = fn_pack_top16(r2[2 * j], r2[2 * j + 1]);
-            }
-            dst[(e * 3 + 0) * 64] = Hh;
-            dst[(e * 3 + 1) * 64] = Mm;
-            dst[(e * 3 + 2) * 64] = Ll;
-        }
-    };
-    // same trip structure as x6w_produce (whole blocks only here: K % 32 == 0): blocks 0, 1 cut and 2 .. NS requested, then per trip
-    // request t + NS + 1 | cut t + 2 | barrier
-    x6w_for<NS>([&](auto I) __attribute__((always_inline)) {
-        if (decltype(I)::value < nblk) gload(I, decltype(I)::value);
-    });
-    cut(x6w_ic<0>{}, 0);
-    if (nblk > 1) cut(x6w_ic<1>{}, 1);
-    if (nblk > NS) gload(x6w_ic<0>{}, NS);
-    x6w_barrier_p();
-    int stage = 2, t = 0;
-    // request and cut interleaved (see x6w_produce): the two loads of row 4 r + e of the new block in front of the cut of tile e
-    auto fused = [&](auto LS, int lblk, auto CS, int stage_) __attribute__((always_inline)) {
-        constexpr int ls = decltype(LS)::value, cs = decltype(CS)::value;
-        const float* p0 = base + 32 * lblk;
-        u32x4* dst = lds + stage_ * X6W_STAGE + ps * X6W_SET + r + 16 * q;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            fa[ls][2 * e] = x6w_ld(p0 + e * pld);
-            fa[ls][2 * e + 1] = x6w_ld(p0 + e * pld + 4);
-            float x[8], hi[8], r1[8], mi[8], r2[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = fa[cs][2 * e + (j >> 2)][j & 3];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { hi[j] = RN ? fn_rn16(x[j]) : fn_top16(x[j]); r1[j] = x[j] - hi[j]; }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { mi[j] = RN ? fn_rn16(r1[j]) : fn_top16(r1[j]); r2[j] = r1[j] - mi[j]; }
-            u32x4 Hh, Mm, Ll;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Hh[j] = fn_pack_top16(hi[2 * j], hi[2 * j + 1]);
-                Mm[j] = fn_pack_top16(mi[2 * j], mi[2 * j + 1]);
-                Ll[j] = fn_pack_top16(r2[2 * j], r2[2 * j + 1]);
-            }
-            dst[(e * 3 + 0) * 64] = Hh;
-            dst[(e * 3 + 1) * 64] = Mm;
-            dst[(e * 3 + 2) * 64] = Ll;
+            ld_row(LS, p0, e);
+            x6w_cut_row<RN>(dst, e, fa[decltype(CS)::value]);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-#pragma unroll 1
-    for (; t + 2 * NS < nblk; t += NS) {
-        x6w_for<NS>([&](auto R) __attribute__((always_inline)) {
-            constexpr int rr = decltype(R)::value;
-            if (X6W_INTERLEAVE) {
-                fused(x6w_ic<(rr + 1) % NS>{}, t + rr + NS + 1, x6w_ic<(rr + 2) % NS>{}, stage);
-            } else {
-                gload(x6w_ic<(rr + 1) % NS>{}, t + rr + NS + 1);
-                cut(x6w_ic<(rr + 2) % NS>{}, stage);
-            }
-            stage = stage == 2 ? 0 : stage + 1;
-            x6w_barrier_p();
-        });
-    }
-    x6w_for<2 * NS>([&](auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value, rr = i % NS;
-        if (t + i < nblk) {
-            if (t + i + NS + 1 < nblk) gload(x6w_ic<(rr + 1) % NS>{}, t + i + NS + 1);
-            if (t + i + 2 < nblk) cut(x6w_ic<(rr + 2) % NS>{}, stage);
-            stage = stage == 2 ? 0 : stage + 1;
-            x6w_barrier_p();
-        }
-    });
+    x6w_trips<NS, 2, false>(nblk, request, cut, fused);
 }
 
 __global__ __launch_bounds__(X6W_NT) void gemm_nt_x6w_kernel(int M, int N, int K, float alpha, const float* __restrict__ A, long lda,
@@ -840,30 +745,10 @@ __global__ __launch_bounds__(X6W_NT) void gemm_nt_x6w_kernel(int M, int N, int K
 // Same products in the same order per accumulator as gemm_tn_x6_kernel: bit-identical on K ranges of whole 32-k blocks.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int X6V_STAGE = 6 * X6W_SET;           // u32x4 vectors per stage (72 KB)
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-// element e of four float4 vectors (4 consecutive k of one column) -> the three pieces as 4 bf16 each
-template <bool RN>
-FN_DEVINL void fn_split4(const f32x4 (&v)[4], int e, u32x2& h, u32x2& m, u32x2& l) {
-    float x[4], hi[4], r1[4], mi[4], r2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = v[j][e];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { hi[j] = RN ? fn_rn16(x[j]) : fn_top16(x[j]); r1[j] = x[j] - hi[j]; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { mi[j] = RN ? fn_rn16(r1[j]) : fn_top16(r1[j]); r2[j] = r1[j] - mi[j]; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        h[j] = fn_pack_top16(hi[2 * j], hi[2 * j + 1]);
-        m[j] = fn_pack_top16(mi[2 * j], mi[2 * j + 1]);
-        l[j] = fn_pack_top16(r2[2 * j], r2[2 * j + 1]);
-    }
-}
-
-#ifndef X6V_NS
-#define X6V_NS 2
-#endif
-// producer wave: full set `fs` from (Pf, ldf, colf) [RNF = rounded pieces], k half `kh` of set `hs` from (Ph, ldh, colh) [always B: rounded].
-// Plain loads counted by the compiler, steady-state trips straight-line (see x6w_produce): 12 loads per block, `s_waitcnt vmcnt(12 (NS - 1))`.
+constexpr int X6V_NS = 2;                        // register sets of a producer wavefront
+// producer wave (trip schedule: x6w_trips with TWO stages - one block cut ahead): full set `fs` from (Pf, ldf, colf) [RNF = rounded pieces], k half
+// `kh` of set `hs` from (Ph, ldh, colh) [always B: rounded]; 12 loads per block (`s_waitcnt vmcnt(12 (NS - 1))` in front of a steady-state cut).
+// Fused trip: two loads in front of every quarter of the full set's cut, one in front of every quarter of the half set's.
 template <bool RNF>
 FN_DEVINL void x6v_produce(u32x4* __restrict__ lds, const float* __restrict__ Pf, long ldf, long colf, int fs, const float* __restrict__ Ph, long ldh,
                            long colh, int hs, int kh, int lane, int kbeg, int kend, int nblk) {
@@ -871,175 +756,56 @@ FN_DEVINL void x6v_produce(u32x4* __restrict__ lds, const float* __restrict__ Pf
     const int lg = lane >> 4, li = lane & 15;
     f32x4 fa[NS][8], fh[NS][4];
     const int hrow = 8 * (2 * kh + (lg >> 1)) + 4 * (lg & 1);      // first row (inside a block) of this lane's four half-set rows
-    auto gload = [&](auto SET, int blk) __attribute__((always_inline)) {              // a whole block inside the matrix
-#ifndef X6W_EXP_NOLOAD
-        constexpr int set = decltype(SET)::value;
-        const long kb = (long)kbeg + 32 * blk;
-        const float* p0 = Pf + (kb + 8 * lg) * ldf + colf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fa[set][j] = x6w_ld(p0 + j * ldf);
-        const float* p1 = Ph + (kb + hrow) * ldh + colh;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fh[set][j] = x6w_ld(p1 + j * ldh);
-#endif
+    auto dstf = [&](int stage) __attribute__((always_inline)) { return lds + stage * X6V_STAGE + fs * X6W_SET + lane; };
+    // half set: operand slot of MFMA lane (i = li, g = 2 kh + (lg >> 1)), its low or high 8 bytes (k 8 g + 4 (lg & 1) ..)
+    auto dsth = [&](int stage) __attribute__((always_inline)) {
+        return reinterpret_cast<u32x2*>(lds + stage * X6V_STAGE + hs * X6W_SET + li + 16 * (2 * kh + (lg >> 1))) + (lg & 1);
     };
-    auto gload_safe = [&](auto SET, int blk) __attribute__((always_inline)) {         // any block: rows beyond the matrix are read from its last row
-#ifndef X6W_EXP_NOLOAD
+    auto request = [&](auto SET, int blk) __attribute__((always_inline)) {
         constexpr int set = decltype(SET)::value;
-        const long k0 = (long)kbeg + 32 * blk + 8 * lg, k1 = (long)kbeg + 32 * blk + hrow;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fa[set][j] = x6w_ld(Pf + min(k0 + j, (long)kend - 1) * ldf + colf);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fh[set][j] = x6w_ld(Ph + min(k1 + j, (long)kend - 1) * ldh + colh);
-#endif
+        x6_tn_load(fa[set], Pf, ldf, colf, (long)kbeg + 32 * blk + 8 * lg, kend);
+        x6_tn_load(fh[set], Ph, ldh, colh, (long)kbeg + 32 * blk + hrow, kend);
     };
-    auto cut = [&](auto SET, int blk, int stage, bool zero_tail) __attribute__((always_inline)) {
+    auto cut = [&](auto SET, int blk, int stage) __attribute__((always_inline)) {
         constexpr int set = decltype(SET)::value;
-        if (zero_tail) {                                 // rows beyond the matrix count as zeros (selects, no branch)
-            const long k0 = (long)kbeg + 32 * blk + 8 * lg, k1 = (long)kbeg + 32 * blk + hrow;
+        x6_tn_zero_tail(fa[set], (long)kbeg + 32 * blk + 8 * lg, kend);
+        x6_tn_zero_tail(fh[set], (long)kbeg + 32 * blk + hrow, kend);
+        u32x4* dst = dstf(stage);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const bool in = k0 + j < kend;
+        for (int a = 0; a < 4; ++a) x6w_cut<RNF>(dst, a, fa[set]);
+        u32x2* dh = dsth(stage);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) fa[set][j][e] = in ? fa[set][j][e] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool in = k1 + j < kend;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) fh[set][j][e] = in ? fh[set][j][e] : 0.f;
-            }
-        }
-#ifdef X6W_EXP_NOCUT
-        if (blk > 0) {                                   // experiment: the loads stay (their registers are "used"), no split, no LDS write
-#pragma unroll
-            for (int j = 0; j < 8; ++j) fn_keep(fa[set][j]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fn_keep(fh[set][j]);
-            return;
-        }
-#endif
-        u32x4* dst = lds + stage * X6V_STAGE + fs * X6W_SET + lane;
-#ifdef X6W_EXP_NOVALU
-        if (blk > 0) {                                   // experiment: the same LDS writes without the split arithmetic
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                dst[(a * 3 + 0) * 64] = __builtin_bit_cast(u32x4, fa[set][2 * a]);
-                dst[(a * 3 + 1) * 64] = __builtin_bit_cast(u32x4, fa[set][2 * a + 1]);
-                dst[(a * 3 + 2) * 64] = __builtin_bit_cast(u32x4, fa[set][(2 * a + 2) & 7]);
-            }
-            u32x2* dh0 = reinterpret_cast<u32x2*>(lds + stage * X6V_STAGE + hs * X6W_SET + li + 16 * (2 * kh + (lg >> 1))) + (lg & 1);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const u32x4 w = __builtin_bit_cast(u32x4, fh[set][a]);
-                dh0[((a * 3 + 0) * 64) * 2] = (u32x2){w[0], w[1]};
-                dh0[((a * 3 + 1) * 64) * 2] = (u32x2){w[2], w[3]};
-                dh0[((a * 3 + 2) * 64) * 2] = (u32x2){w[1], w[2]};
-            }
-            return;
-        }
-#endif
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            bf16x8 h, m, l;
-            fn_split8<RNF>(fa[set], a, h, m, l);
-#ifdef X6W_EXP_NODSW
-            if (blk > 0) { asm volatile("" ::"v"(h), "v"(m), "v"(l)); continue; }
-#endif
-            dst[(a * 3 + 0) * 64] = __builtin_bit_cast(u32x4, h);
-            dst[(a * 3 + 1) * 64] = __builtin_bit_cast(u32x4, m);
-            dst[(a * 3 + 2) * 64] = __builtin_bit_cast(u32x4, l);
-        }
-        // half set: operand slot of MFMA lane (i = li, g = 2 kh + (lg >> 1)), its low or high 8 bytes (k 8 g + 4 (lg & 1) ..)
-        u32x2* dh = reinterpret_cast<u32x2*>(lds + stage * X6V_STAGE + hs * X6W_SET + li + 16 * (2 * kh + (lg >> 1))) + (lg & 1);
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            u32x2 h, m, l;
-            fn_split4<true>(fh[set], a, h, m, l);
-#ifdef X6W_EXP_NODSW
-            if (blk > 0) { asm volatile("" ::"v"(h), "v"(m), "v"(l)); continue; }
-#endif
-            dh[((a * 3 + 0) * 64) * 2] = h;
-            dh[((a * 3 + 1) * 64) * 2] = m;
-            dh[((a * 3 + 2) * 64) * 2] = l;
-        }
+        for (int a = 0; a < 4; ++a) x6w_cut<true>(dh, a, fh[set]);
     };
-    // prologue: block 0 cut into stage 0, blocks 1 .. NS - 1 requested
-    x6w_for<NS>([&](auto I) __attribute__((always_inline)) {
-        if (decltype(I)::value < nblk) gload_safe(I, decltype(I)::value);
-    });
-    cut(x6w_ic<0>{}, 0, 0, true);
-    x6w_barrier_p();
-    int t = 0;
-    // steady state: trip t (t % NS == r) requests block t + NS -> set r and cuts block t + 1 (set (r + 1) % NS, stage (t + 1) & 1); whole blocks only
-    // request and cut interleaved (see x6w_produce): two loads in front of every quarter of the full set's cut, one in front of every quarter of the half set's
-    auto fused = [&](auto LS, int lblk, auto CS, int stage) __attribute__((always_inline)) {
+    auto fused = [&](auto LS, int lblk, auto CS, int, int stage) __attribute__((always_inline)) {
         constexpr int ls = decltype(LS)::value, cs = decltype(CS)::value;
         const long kb = (long)kbeg + 32 * lblk;
         const float* p0 = Pf + (kb + 8 * lg) * ldf + colf;
         const float* p1 = Ph + (kb + hrow) * ldh + colh;
-        u32x4* dst = lds + stage * X6V_STAGE + fs * X6W_SET + lane;
-        u32x2* dh = reinterpret_cast<u32x2*>(lds + stage * X6V_STAGE + hs * X6W_SET + li + 16 * (2 * kh + (lg >> 1))) + (lg & 1);
+        u32x4* dst = dstf(stage);
+        u32x2* dh = dsth(stage);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-#ifndef X6W_EXP_NOLOAD
             fa[ls][2 * a] = x6w_ld(p0 + (2 * a) * ldf);
             fa[ls][2 * a + 1] = x6w_ld(p0 + (2 * a + 1) * ldf);
-#endif
-            bf16x8 h, m, l;
-            fn_split8<RNF>(fa[cs], a, h, m, l);
-            dst[(a * 3 + 0) * 64] = __builtin_bit_cast(u32x4, h);
-            dst[(a * 3 + 1) * 64] = __builtin_bit_cast(u32x4, m);
-            dst[(a * 3 + 2) * 64] = __builtin_bit_cast(u32x4, l);
+            x6w_cut<RNF>(dst, a, fa[cs]);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-#ifndef X6W_EXP_NOLOAD
             fh[ls][a] = x6w_ld(p1 + a * ldh);
-#endif
-            u32x2 h, m, l;
-            fn_split4<true>(fh[cs], a, h, m, l);
-            dh[((a * 3 + 0) * 64) * 2] = h;
-            dh[((a * 3 + 1) * 64) * 2] = m;
-            dh[((a * 3 + 2) * 64) * 2] = l;
+            x6w_cut<true>(dh, a, fh[cs]);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-#pragma unroll 1
-    for (; t + 2 * NS < nblk; t += NS) {
-        x6w_for<NS>([&](auto R) __attribute__((always_inline)) {
-            constexpr int r = decltype(R)::value;
-            if (X6W_INTERLEAVE) {
-                fused(R, t + r + NS, x6w_ic<(r + 1) % NS>{}, (t + r + 1) & 1);
-            } else {
-                gload(R, t + r + NS);
-                cut(x6w_ic<(r + 1) % NS>{}, t + r + 1, (t + r + 1) & 1, false);
-            }
-            x6w_barrier_p();
-        });
-    }
-    // the last <= 2 NS trips (t is a multiple of NS here)
-    x6w_for<2 * NS>([&](auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value, r = i % NS;
-        if (t + i < nblk) {
-            if (t + i + NS < nblk) gload_safe(x6w_ic<r>{}, t + i + NS);
-            if (t + i + 1 < nblk) cut(x6w_ic<(r + 1) % NS>{}, t + i + 1, (t + i + 1) & 1, true);
-            x6w_barrier_p();
-        }
-    });
+    x6w_trips<NS, 1, true>(nblk, request, cut, fused);
 }
 
-// one (output tile, K range) of gemm_tn_x6v_kernel: both roles run 1 + nblk barriers, and behind the last one no stage is read any more (the reads in flight fetch
-// values nobody uses): the next item of a workgroup that walks several of them may be cut into the stages at once
-FN_DEVINL void gemm_tn_x6v_kernel_item(int M, int N, int K, float alpha, const float* __restrict__ A, long lda,
-                                                              const float* __restrict__ B, long ldb, float beta, float* __restrict__ C, long ldc,
-                                                              const float* __restrict__ bias, int ksplit_len, float* __restrict__ slabs,
-                                                              const float* __restrict__ A2, long lda2, int msplit, u32x4* __restrict__ x6v_lds, int ntn, int tile, int zk) {
+// one (output tile, K range) of gemm_tn_x6v_kernel
+FN_DEVINL void gemm_tn_x6v_kernel_item(const X6Tn& g, u32x4* __restrict__ x6v_lds, int mb, int nb, int zk) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int mb = (tile / ntn) * 128, nb = (tile % ntn) * 256;          // the workgroup's output tile
     const int li = lane & 15, lg = lane >> 4;
-    const int kbeg = zk * ksplit_len, kend = min(K, kbeg + ksplit_len);
+    const int kbeg = zk * g.ksplit_len, kend = min(g.K, kbeg + g.ksplit_len);
     const int nblk = (kend - kbeg + 31) >> 5;
     if (nblk <= 0) return;                               // (the host never launches an empty K range)
 
@@ -1047,22 +813,12 @@ FN_DEVINL void gemm_tn_x6v_kernel_item(int M, int N, int K, float alpha, const f
         // ---- producer p: set p (p < 2: A columns mb + 64 p; else B columns nb + 64 (p - 2)) and k half p & 1 of set 4 + (p >> 1) (B columns nb + 128 + 64 (p >> 1)) ----
         const int p = wave & 3;
         const bool pa = p < 2;
-        const float* P = pa ? A : B;
-        long pld = pa ? lda : ldb;
-        // column offsets of this lane's 16-byte loads, kept inside the columns the operand REALLY has (see gemm_tn_body)
-        const int pc0 = pa ? mb + 64 * p : nb + 64 * (p - 2);
-        long ncols = pa ? (long)M : (long)N, rel = pc0;
-        if (pa && A2 != nullptr) {
-            if (pc0 >= msplit) { P = A2; pld = lda2; ncols = (long)M - msplit; rel = pc0 - msplit; }
-            else ncols = msplit;
-        }
-        long pcol = min(rel + 4 * li, ((ncols - 1) >> 2) << 2);
-        if (rel >= ncols) pcol = ((ncols - 1) >> 2) << 2;                // a set entirely beyond the matrix: any legal column (never stored)
-        const long hrel = (long)nb + 128 + 64 * (p >> 1);
-        long hcol = min(hrel + 4 * li, (((long)N - 1) >> 2) << 2);
-        if (hrel >= N) hcol = (((long)N - 1) >> 2) << 2;
-        if (pa) x6v_produce<false>(x6v_lds, P, pld, pcol, p, B, ldb, hcol, 4 + (p >> 1), p & 1, lane, kbeg, kend, nblk);
-        else x6v_produce<true>(x6v_lds, P, pld, pcol, p, B, ldb, hcol, 4 + (p >> 1), p & 1, lane, kbeg, kend, nblk);
+        const float *P, *Ph;
+        long pld, ldh;
+        const long pcol = x6_tn_pcol(g, pa, pa ? mb + 64 * p : nb + 64 * (p - 2), li, P, pld);
+        const long hcol = x6_tn_pcol(g, false, nb + 128 + 64 * (p >> 1), li, Ph, ldh);
+        if (pa) x6v_produce<false>(x6v_lds, P, pld, pcol, p, Ph, ldh, hcol, 4 + (p >> 1), p & 1, lane, kbeg, kend, nblk);
+        else x6v_produce<true>(x6v_lds, P, pld, pcol, p, Ph, ldh, hcol, 4 + (p >> 1), p & 1, lane, kbeg, kend, nblk);
         return;
     }
 
@@ -1099,13 +855,11 @@ FN_DEVINL void gemm_tn_x6v_kernel_item(int M, int N, int K, float alpha, const f
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
             rdB(st, b + 2);
-#ifndef X6W_EXP_NOMMA
 #pragma unroll
             for (int c = 0; c < 6; ++c)
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Af[a][PA[c]], Bf[b & 3][PB[c]], acc[a][b], 0, 0, 0);
-#endif
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
@@ -1120,13 +874,11 @@ FN_DEVINL void gemm_tn_x6v_kernel_item(int M, int N, int K, float alpha, const f
         // (behind the last block: reads of a stage nobody uses)
         auto joint = [&](auto AA) __attribute__((always_inline)) {
             constexpr int a = decltype(AA)::value;
-#ifndef X6W_EXP_NOMMA
 #pragma unroll
             for (int c = 0; c < 6; ++c)
 #pragma unroll
                 for (int b = 6; b < 8; ++b)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Af[a][PA[c]], Bf[b & 3][PB[c]], acc[a][b], 0, 0, 0);
-#endif
         };
         rdB(sn, 0);
         joint(x6w_ic<0>{});
@@ -1167,45 +919,7 @@ FN_DEVINL void gemm_tn_x6v_kernel_item(int M, int N, int K, float alpha, const f
         rdA(sn, 3);
         __builtin_amdgcn_sched_barrier(0);
     }
-    const int m0 = mb + 64 * wm, n0 = nb + 128 * wn;
-    if (slabs != nullptr && (N & 3) == 0) {              // split-K slabs: a lane's four column tiles of a set are four consecutive columns - 16-byte stores
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + 4 * (lg * 4 + r) + a;
-                if (row >= M) continue;
-#pragma unroll
-                for (int bs = 0; bs < 2; ++bs) {
-                    const int col = n0 + 64 * bs + 4 * li;
-                    if (col >= N) continue;
-                    const f32x4 v = {acc[a][4 * bs][r], acc[a][4 * bs + 1][r], acc[a][4 * bs + 2][r], acc[a][4 * bs + 3][r]};
-                    *reinterpret_cast<f32x4*>(slabs + ((long)zk * M + row) * N + col) = v;
-                }
-            }
-        return;
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = m0 + 4 * (lg * 4 + r) + a;
-            if (row >= M) continue;
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const int col = n0 + 64 * (b >> 2) + 4 * li + (b & 3);
-                if (col >= N) continue;
-                const float v = acc[a][b][r];
-                if (slabs) {
-                    slabs[((long)zk * M + row) * N + col] = v;
-                } else {
-                    float o = alpha * v;
-                    if (bias) o += bias[col];
-                    if (beta != 0.f) o += beta * C[(long)row * ldc + col];
-                    C[(long)row * ldc + col] = o;
-                }
-            }
-        }
+    x6_tn_store(g, acc, mb + 64 * wm, nb + 128 * wn, li, lg, zk);
 }
 
 __global__ __launch_bounds__(X6W_NT) void gemm_tn_x6v_kernel(int M, int N, int K, float alpha, const float* __restrict__ A, long lda,
@@ -1213,17 +927,8 @@ __global__ __launch_bounds__(X6W_NT) void gemm_tn_x6v_kernel(int M, int N, int K
                                                               const float* __restrict__ bias, int ksplit_len, float* __restrict__ slabs,
                                                               const float* __restrict__ A2, long lda2, int msplit) {
     extern __shared__ __attribute__((aligned(16))) u32x4 x6v_lds[];      // [2 stages][6 sets][4 tiles][3 pieces][64 lanes]
-    const int ntn = (N + 255) / 256, ntm = (M + 127) / 128;
-    if (gridDim.z == 1 && slabs != nullptr) {            // K ranges dealt to the XCDs (see gemm_tn_body); a workgroup walks items blockIdx.x, + gridDim.x, ...
-        const int S = (K + ksplit_len - 1) / ksplit_len, items = S * ntn * ntm;      // (gridDim.x < items only when it is a multiple of 8: the items of a workgroup stay on its XCD)
-#pragma unroll 1
-        for (int v = blockIdx.x; v < items; v += gridDim.x) {
-            const int c = v & 7, q = v >> 3;
-            gemm_tn_x6v_kernel_item(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, ksplit_len, slabs, A2, lda2, msplit, x6v_lds, ntn, q % (ntn * ntm), c * (S >> 3) + q / (ntn * ntm));
-        }
-    } else {
-        gemm_tn_x6v_kernel_item(M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, ksplit_len, slabs, A2, lda2, msplit, x6v_lds, ntn, fn_xcd_remap(blockIdx.x, ntn * ntm), blockIdx.z);
-    }
+    const X6Tn g = {M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, ksplit_len, slabs, A2, lda2, msplit};
+    x6_tn_walk<256>(g, [&](int mb, int nb, int zk) __attribute__((always_inline)) { gemm_tn_x6v_kernel_item(g, x6v_lds, mb, nb, zk); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1799,44 +1504,58 @@ static int launch_tn_x6(int mode, int tiles, int splitk, hipStream_t st, int M, 
     return FN_OK;
 }
 
+// the flag bits that ride on the `splitk` argument of fn_gemm_f32 / fn_gru_dwhh_f32 (fadernets.h)
+struct SplitkFlags {
+    static constexpr int X6_MODES = FN_GEMM_X6_PERWAVE | FN_GEMM_X6_WIDE | FN_GEMM_X6_PERTILE;
+    bool lean, x6;
+    int x6_mode, xflags, splitk;                         // xflags: the bf16 x 6 bits as they came, to hand on; splitk: the number of K ranges asked for
+    explicit SplitkFlags(int v)
+        : lean((v & FN_GEMM_LEAN) != 0), x6((v & FN_GEMM_BF16X6) != 0), x6_mode(v & X6_MODES), xflags(v & (FN_GEMM_BF16X6 | X6_MODES)),
+          splitk(v & ~(FN_GEMM_LEAN | FN_GEMM_BF16X6 | X6_MODES)) {}
+};
+
+// the TN product (both operands with K as their slow dimension, 16-byte aligned): bf16 x 6 or fp32 kernel over `splitk` K ranges, then the slab reduce
+static int launch_tn(const SplitkFlags& f, hipStream_t st, int M, int N, int K, float alpha, const float* A, long lda, const float* B, long ldb, float beta,
+                     float* C, long ldc, const float* bias, float* ws, const float* A2, long lda2, int msplit) {
+    int klen = K, splitk = f.splitk;
+    if (splitk > 1) {
+        // K ranges of whole 32-k blocks for the bf16 x 6 kernel (no fp32-MFMA tail inside a range), of 4 rows otherwise
+        const int gran = f.x6 ? 32 : 4;
+        klen = ((K + splitk - 1) / splitk + gran - 1) / gran * gran;
+        splitk = (K + klen - 1) / klen;
+    }
+    const int ntm = (M + 127) / 128, ntn = (N + 127) / 128;
+    float* slabs = splitk > 1 ? ws : nullptr;
+    if (f.x6) {
+        const int rc = launch_tn_x6(f.x6_mode, ntm * ntn, splitk, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, klen, slabs, A2, lda2, msplit);
+        if (rc != FN_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(f.lean ? gemm_tn_lean_kernel : gemm_tn_kernel, tn_grid(ntm * ntn, splitk), dim3(NT), 0, st, M, N, K, alpha, A, lda, B, ldb, beta, C,
+                           ldc, bias, klen, slabs, A2, lda2, msplit);
+    }
+    FN_CHECK_LAUNCH();
+    if (splitk > 1) {
+        launch_slab_reduce(st, slabs, splitk, M, N, alpha, beta, C, ldc, bias);
+        FN_CHECK_LAUNCH();
+    }
+    return FN_OK;
+}
+
 size_t fn_gemm_ws_bytes(int M, int N, int splitk) { return splitk > 1 ? (size_t)splitk * M * N * sizeof(float) : 0; }
 
 int fn_gemm_f32(int a_kmajor, int b_kmajor, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
                 float beta, float* C, int ldc, const float* bias, int splitk, float* ws, size_t ws_bytes, void* stream) {
     if (!A || !B || !C) return FN_E_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc < N) return FN_E_SHAPE;
-    const bool lean = (splitk & FN_GEMM_LEAN) != 0;
-    const bool x6 = (splitk & FN_GEMM_BF16X6) != 0;
-    const int x6_mode = splitk & (FN_GEMM_X6_PERWAVE | FN_GEMM_X6_WIDE | FN_GEMM_X6_PERTILE);
-    splitk &= ~(FN_GEMM_LEAN | FN_GEMM_BF16X6 | FN_GEMM_X6_PERWAVE | FN_GEMM_X6_WIDE | FN_GEMM_X6_PERTILE);
+    const SplitkFlags f(splitk);
+    const bool lean = f.lean, x6 = f.x6;
+    const int x6_mode = f.x6_mode;
+    splitk = f.splitk;
     if (splitk > 1 && (!ws || ws_bytes < fn_gemm_ws_bytes(M, N, splitk))) return FN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (!a_kmajor && !b_kmajor && (lda % 4) == 0 && (ldb % 4) == 0 && lda >= 4 && ldb >= 4 &&
-        (((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0)) {
-        int klen = K;
-        if (splitk > 1) {
-            // K ranges of whole 32-k blocks for the bf16 x 6 kernel (no fp32-MFMA tail inside a range), of 4 rows otherwise
-            const int gran = x6 ? 32 : 4;
-            klen = ((K + splitk - 1) / splitk + gran - 1) / gran * gran;
-            splitk = (K + klen - 1) / klen;
-        }
-        const int ntm = (M + 127) / 128, ntn = (N + 127) / 128;
-        float* slabs = splitk > 1 ? ws : nullptr;
-        if (x6) {
-            const int rc = launch_tn_x6(x6_mode, ntm * ntn, splitk, st, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C, (long)ldc, bias, klen, slabs,
-                                        (const float*)nullptr, 0L, 0);
-            if (rc != FN_OK) return rc;
-        } else {
-            hipLaunchKernelGGL(lean ? gemm_tn_lean_kernel : gemm_tn_kernel, tn_grid(ntm * ntn, splitk), dim3(NT), 0, st, M, N, K, alpha, A,
-                               (long)lda, B, (long)ldb, beta, C, (long)ldc, bias, klen, slabs, (const float*)nullptr, 0L, 0);
-        }
-        FN_CHECK_LAUNCH();
-        if (splitk > 1) {
-            launch_slab_reduce(st, slabs, splitk, M, N, alpha, beta, C, (long)ldc, bias);
-            FN_CHECK_LAUNCH();
-        }
-        return FN_OK;
-    }
+        (((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0))
+        return launch_tn(f, st, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C, (long)ldc, bias, ws, (const float*)nullptr, 0L, 0);
     // bf16 x 6, K-contiguous operands, whole 128 x 128 tiles and 32-k blocks, no split: the producer / consumer kernel
     if (x6 && a_kmajor && b_kmajor && splitk <= 1 && (M % 128) == 0 && (N % 128) == 0 && (K % 32) == 0 && K >= 128 && (lda % 4) == 0 && (ldb % 4) == 0 &&
         (ldc % 4) == 0 && (((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) == 0) && (long)(M / 128) * (N / 128) >= 128) {
@@ -1891,43 +1610,17 @@ int fn_gru_dwhh_f32(const float* dgx, const float* dghn, const float* hprev, int
                     float* ws, size_t ws_bytes, void* stream) {
     if (!dgx || !dghn || !hprev || !dW) return FN_E_NULL;
     if (rows <= 0 || rows > 0x7fffffff || H <= 0) return FN_E_SHAPE;
-    const bool lean = (splitk & FN_GEMM_LEAN) != 0;
-    const bool x6 = (splitk & FN_GEMM_BF16X6) != 0;
-    const int x6_mode = splitk & (FN_GEMM_X6_PERWAVE | FN_GEMM_X6_WIDE | FN_GEMM_X6_PERTILE);
-    const int xflags = splitk & (FN_GEMM_BF16X6 | FN_GEMM_X6_PERWAVE | FN_GEMM_X6_WIDE | FN_GEMM_X6_PERTILE);
-    splitk &= ~(FN_GEMM_LEAN | FN_GEMM_BF16X6 | FN_GEMM_X6_PERWAVE | FN_GEMM_X6_WIDE | FN_GEMM_X6_PERTILE);
-    if (splitk > 1 && (!ws || ws_bytes < fn_gru_dwhh_ws_bytes(H, splitk))) return FN_E_WORKSPACE;
+    const SplitkFlags f(splitk);
+    if (f.splitk > 1 && (!ws || ws_bytes < fn_gru_dwhh_ws_bytes(H, f.splitk))) return FN_E_WORKSPACE;
     const int M = 3 * H, N = H, K = (int)rows;
     const bool one_launch = (2 * H) % 128 == 0 && (H % 4) == 0 && (((((uintptr_t)dgx) | ((uintptr_t)dghn) | ((uintptr_t)hprev)) & 15) == 0);
     if (!one_launch) {          // two products: rows [0, 2H) from dgx, rows [2H, 3H) from dghn
-        const int fl = splitk | xflags;
+        const int fl = f.splitk | f.xflags;
         int rc = fn_gemm_f32(0, 0, 2 * H, N, K, 1.0f, dgx, 3 * H, hprev, H, beta, dW, H, nullptr, fl, ws, ws_bytes, stream);
         if (rc != FN_OK) return rc;
         return fn_gemm_f32(0, 0, H, N, K, 1.0f, dghn, H, hprev, H, beta, dW + (size_t)2 * H * H, H, nullptr, fl, ws, ws_bytes, stream);
     }
-    hipStream_t st = (hipStream_t)stream;
-    int klen = K;
-    if (splitk > 1) {
-        const int gran = x6 ? 32 : 4;
-        klen = ((K + splitk - 1) / splitk + gran - 1) / gran * gran;
-        splitk = (K + klen - 1) / klen;
-    }
-    const int ntm = (M + 127) / 128, ntn = (N + 127) / 128;
-    float* slabs = splitk > 1 ? ws : nullptr;
-    if (x6) {
-        const int rc = launch_tn_x6(x6_mode, ntm * ntn, splitk, st, M, N, K, 1.0f, dgx, (long)3 * H, hprev, (long)H, beta, dW, (long)H, (const float*)nullptr, klen,
-                                    slabs, dghn, (long)H, 2 * H);
-        if (rc != FN_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(lean ? gemm_tn_lean_kernel : gemm_tn_kernel, tn_grid(ntm * ntn, splitk), dim3(NT), 0, st, M, N, K, 1.0f, dgx,
-                           (long)3 * H, hprev, (long)H, beta, dW, (long)H, (const float*)nullptr, klen, slabs, dghn, (long)H, 2 * H);
-    }
-    FN_CHECK_LAUNCH();
-    if (splitk > 1) {
-        launch_slab_reduce(st, slabs, splitk, M, N, 1.0f, beta, dW, (long)H, (const float*)nullptr);
-        FN_CHECK_LAUNCH();
-    }
-    return FN_OK;
+    return launch_tn(f, (hipStream_t)stream, M, N, K, 1.0f, dgx, (long)3 * H, hprev, (long)H, beta, dW, (long)H, (const float*)nullptr, ws, dghn, (long)H, 2 * H);
 }
 
 int fn_transpose_f32(const float* src, int R, int C, int src_ld, float* dst, int dst_ld, void* stream) {

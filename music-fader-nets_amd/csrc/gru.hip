@@ -1513,13 +1513,15 @@ int launch_cell_wlds(const CellArgs& a, hipStream_t st) {
 // new state.  B % 128 == 0, H % 32 == 0, K1 % 32 == 0, 16-byte aligned operands.  Same gate arithmetic as the fp32 cells; the products are summed
 // in another order (fp32-class): greedy tokens agree up to the reference's own near-ties (tests/test_gpu_parity.py).
 // ---------------------------------------------------------------------------------------------------------------
+// producer wavefront (trip schedule: x6w_trips, x6w_core.h; register sets filled row-wise as in gemm_nt_x6w_kernel): blocks [0, nbx) come from the
+// four rows px, the others from ph; no interleaved form - a fused trip is the request, then the cut
 template <bool RN>
 FN_DEVINL void cell_x6_produce(u32x4* __restrict__ lds, const float* const (&px)[4], const float* const (&ph)[4], bool zero_x, bool zero_h, int nbx, int ps, int lane,
                                int nblk) {
     constexpr int NS = X6W_NS;
     const int r = lane >> 2, q = lane & 3;
     f32x4 fa[NS][8];                                     // [set][2 e + j]: set row 4 r + e, k = 8 q + 4 j ..
-    auto gload = [&](auto SET, int blk) __attribute__((always_inline)) {
+    auto request = [&](auto SET, int blk) __attribute__((always_inline)) {
         constexpr int set = decltype(SET)::value;
         const bool xp = blk < nbx;
         const long off = xp ? 32L * blk : 32L * (blk - nbx);
@@ -1531,58 +1533,16 @@ FN_DEVINL void cell_x6_produce(u32x4* __restrict__ lds, const float* const (&px)
         }
     };
     auto cut = [&](auto SET, int blk, int stage) __attribute__((always_inline)) {
-        constexpr int set = decltype(SET)::value;
         const bool zero = blk < nbx ? zero_x : zero_h;   // this lane's rows do not take part in this K part: zeros (the loads above fetched legal rows)
         u32x4* dst = lds + stage * X6W_STAGE + ps * X6W_SET + r + 16 * q;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float x[8], hi[8], r1[8], mi[8], r2[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = zero ? 0.f : fa[set][2 * e + (j >> 2)][j & 3];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { hi[j] = RN ? fn_rn16(x[j]) : fn_top16(x[j]); r1[j] = x[j] - hi[j]; }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { mi[j] = RN ? fn_rn16(r1[j]) : fn_top16(r1[j]); r2[j] = r1[j] - mi[j]; }
-            u32x4 Hh, Mm, Ll;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Hh[j] = fn_pack_top16(hi[2 * j], hi[2 * j + 1]);
-                Mm[j] = fn_pack_top16(mi[2 * j], mi[2 * j + 1]);
-                Ll[j] = fn_pack_top16(r2[2 * j], r2[2 * j + 1]);
-            }
-            dst[(e * 3 + 0) * 64] = Hh;
-            dst[(e * 3 + 1) * 64] = Mm;
-            dst[(e * 3 + 2) * 64] = Ll;
-        }
+        for (int e = 0; e < 4; ++e) x6w_cut_row<RN>(dst, e, fa[decltype(SET)::value], zero);
     };
-    // the trip structure of x6w_produce_nt (gemm.hip): blocks 0, 1 cut and 2 .. NS requested, then per trip request t + NS + 1 | cut t + 2 | barrier
-    x6w_for<NS>([&](auto I) __attribute__((always_inline)) {
-        if (decltype(I)::value < nblk) gload(I, decltype(I)::value);
-    });
-    cut(x6w_ic<0>{}, 0, 0);
-    if (nblk > 1) cut(x6w_ic<1>{}, 1, 1);
-    if (nblk > NS) gload(x6w_ic<0>{}, NS);
-    x6w_barrier_p();
-    int stage = 2, t = 0;
-#pragma unroll 1
-    for (; t + 2 * NS < nblk; t += NS) {
-        x6w_for<NS>([&](auto R) __attribute__((always_inline)) {
-            constexpr int rr = decltype(R)::value;
-            gload(x6w_ic<(rr + 1) % NS>{}, t + rr + NS + 1);
-            cut(x6w_ic<(rr + 2) % NS>{}, t + rr + 2, stage);
-            stage = stage == 2 ? 0 : stage + 1;
-            x6w_barrier_p();
-        });
-    }
-    x6w_for<2 * NS>([&](auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value, rr = i % NS;
-        if (t + i < nblk) {
-            if (t + i + NS + 1 < nblk) gload(x6w_ic<(rr + 1) % NS>{}, t + i + NS + 1);
-            if (t + i + 2 < nblk) cut(x6w_ic<(rr + 2) % NS>{}, t + i + 2, stage);
-            stage = stage == 2 ? 0 : stage + 1;
-            x6w_barrier_p();
-        }
-    });
+    auto fused = [&](auto LS, int lblk, auto CS, int cblk, int stage) __attribute__((always_inline)) {
+        request(LS, lblk);
+        cut(CS, cblk, stage);
+    };
+    x6w_trips<NS, 2, false>(nblk, request, cut, fused);
 }
 
 constexpr int CX_LDT = 68;                           // floats per row of an accumulator tile in LDS (64 + 4: 16-byte rows, conflict-free column reads)

@@ -613,6 +613,76 @@ def test_gemm_nt_bf16x6(ops, M, N, K):
         ops.dw_x6, ops.nt_x6, ops.x6_per_tile = _x6_default(), True, False
 
 
+@pytest.mark.parametrize("nblk", range(1, 14))
+def test_bf16x6_producer_trips_at_every_block_count(ops, nblk):
+    """The shared producer trip schedule (x6w_trips, csrc/x6w_core.h) at its boundaries: 1 .. 13 blocks of 32 k per K range = no steady-state pass, one
+    pass (NS = 3 trips) with every tail length, two passes - for every kernel that runs on it.
+    TN (128 x 256 x 32 nblk, one K range): gemm_tn_x6w_kernel and gemm_tn_x6v_kernel bit-identical to the per-wave kernel; with K = 32 nblk - 5 (the last
+    block partial) bit-identical to each other and within the fp32 kernels' float64 bound.  NT (2048 x 1024 - 128 tiles, the dispatch threshold -, from 4
+    blocks on: the dispatch takes K >= 128): the float64 bound of test_gemm_nt_bf16x6, one workgroup per tile == one per CU.  Cell (128 rows, no dense
+    input, H = 32 nblk; H = 32 is below what the bf16 x 6 cell takes and runs on the fp32 cell): against the fp32 cell, tolerance of test_gru_cell_bf16x6."""
+    torch.manual_seed(1000 + nblk)
+    try:
+        ops.dw_x6 = True
+        M, N = 128, 256
+        for K in (32 * nblk, 32 * nblk - 5):
+            A = torch.randn(K, M, device=DEV)
+            B = torch.randn(K, N, device=DEV) * 0.3
+            ref = A.double().t() @ B.double()
+            scale = float((A.double().abs().t() @ B.double().abs()).max())
+            out = {}
+            for name, wide, pw in (("perwave", False, True), ("tile128", False, False), ("tile256", "force", False)):
+                ops.x6_wide, ops.x6_perwave = wide, pw
+                out[name] = torch.full((M, N), float("nan"), device=DEV)
+                ops.gemm(A, B, out[name], a_k=False, b_k=False, splitk=1)
+            ops.x6_wide, ops.x6_perwave = True, False
+            for name in out:
+                err = float((out[name].double() - ref).abs().max()) / scale
+                print("TN nblk %d K %d %s err %.3e" % (nblk, K, name, err))
+                assert err < 2e-6, (name, K)
+            if K % 32 == 0:
+                assert torch.equal(out["tile128"], out["perwave"]) and torch.equal(out["tile256"], out["perwave"]), K
+            else:                                         # both multiply the K tail as a zero-padded block
+                assert torch.equal(out["tile128"], out["tile256"]), K
+        if nblk >= 4:
+            M, N, K = 2048, 1024, 32 * nblk
+            A = torch.randn(M, K, device=DEV)
+            W = torch.randn(N, K, device=DEV) * 0.2
+            ref = A.double() @ W.double().t()
+            scale = float((A.double().abs() @ W.double().abs().t()).max())
+            err, outs = {}, {}
+            for x6 in (False, True):
+                ops.dw_x6, ops.nt_x6 = x6, x6
+                outs[x6] = torch.full((M, N), float("nan"), device=DEV)
+                ops.gemm(A, W, outs[x6], a_k=True, b_k=True)
+                err[x6] = float((outs[x6].double() - ref).abs().max()) / scale
+            print("NT nblk %d err fp32 %.3e bf16x6 %.3e" % (nblk, err[False], err[True]))
+            assert err[True] < 2e-6 and err[True] <= 2.0 * err[False] + 1e-9, err
+            ops.x6_per_tile = True
+            C = torch.full((M, N), float("nan"), device=DEV)
+            ops.gemm(A, W, C, a_k=True, b_k=True)
+            assert torch.equal(C, outs[True])
+        Bc, H, V = 128, 32 * nblk, 50
+        hp = torch.randn(Bc, H) * 0.5
+        whh, bhh, bih = torch.randn(3 * H, H) / H ** 0.5, torch.randn(3 * H) * 0.1, torch.randn(3 * H) * 0.1
+        kw = dict(b_ih=bih, gx_table=torch.randn(V, 3 * H) * 0.3, gx_rowbias=torch.randn(Bc, 3 * H) * 0.3, start_token=V - 1)
+        ref = torch.zeros(Bc, H)
+        idx = torch.randint(0, V, (Bc,), dtype=torch.int32)
+        FakeOps().gru_cell(hp, whh, bhh, ref, idx=idx, **kw)
+        dkw = {k: (g(v) if torch.is_tensor(v) else v) for k, v in kw.items()}
+        outs = {}
+        for x6 in (False, True):
+            ops.dw_x6, ops.cell_x6, ops.cell_x6_rows = x6, x6, 0
+            outs[x6] = torch.full((Bc, H), float("nan"), device=DEV)
+            ops.gru_cell(g(hp), g(whh), g(bhh), outs[x6], idx=g(idx), **dkw)
+            close(outs[x6], ref, 2e-5, "gru_cell x6=%s" % x6)
+        d = float((outs[True] - outs[False]).abs().max())
+        print("cell nblk %d max |x6 - fp32| %.3e" % (nblk, d))
+        assert d < 5e-6
+    finally:
+        ops.dw_x6, ops.x6_perwave, ops.x6_wide, ops.x6_per_tile, ops.nt_x6, ops.cell_x6, ops.cell_x6_rows = _x6_default(), False, True, False, True, True, 2048
+
+
 def test_gemm_bf16x6_kernels_random_shapes():
     """scratch/r6_fuzz_gemm.py (the randomised sweep behind profiles/r06_gemm_fuzz.txt) with a small case count: ragged M / N, K tails, every split depth,
     padded leading dimensions, the two-source form, the Linear-forward form with alpha / beta / bias - the three weight-gradient kernels agree bit for bit
