@@ -480,6 +480,58 @@ typedef struct FnSampleParams {      /* 32 bytes */
 int fn_vocab_sample(const float* logits, int B, int V, int ld, const FnSampleParams* params_dev, int step, float* logp_out,
                     int64_t logp_ld, int32_t* own_out, int own_ld, int32_t* tok_out, int tok_ld, float* u_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Beam search over the same head (decode.beam_decode): select, state reorder, backtrack.  There is NO reference counterpart: the reference's
+ * decode loop (gmm_model.py:73-80,119-149) feeds back the argmax of one stream; these three replace that feedback by the W best streams per
+ * latent.  The text below is the specification.  B sequences of W beams: row r = b*W + w of every [B*W][..] matrix is beam w of sequence b.
+ *   1 <= W <= min(V, FN_BEAM_MAX_W),  1 <= V <= FN_SAMPLE_MAX_V.
+ *
+ * fn_beam_step - one decode step, one launch.  logits [B*W][ld], V valid columns; step >= 0; eos in [0, V) or -1 = none;
+ * score_prev / token_prev: the previous step's score / token slabs [B][prev_ld] (fp32 / int32, W valid entries; not read at step 0, may then
+ * be NULL); score / parent / token: this step's slabs [B][out_ld]; logp_out [B*W][V] (row stride logp_ld) or NULL.  Per sequence b, in fp32:
+ *   lp      lp[w][e] = x[e] - lse of row b*W + w, computed as the greedy head computes it: logp_out, when given, is written for EVERY row and is
+ *           bit-identical to fn_vocab_argmax's logp_out on the same logits;
+ *   beams   beam w is LIVE iff step > 0 || w == 0, FINISHED iff step > 0 && eos >= 0 && token_prev[b][w] == eos.  The logits rows of non-live
+ *           and finished beams play no part in score / parent / token (they may hold NaN);
+ *   cands   a live, unfinished beam contributes the V candidates (w, e) with s = score_prev[b][w] + lp[w][e] - ONE fp32 add, score_prev taken
+ *           as 0.0f at step 0; a finished beam contributes the single candidate (w, eos) with s = score_prev[b][w];
+ *   order   candidates are ordered by the 64-bit word pack(s, w*V + e) of fn_out_argmax_f32 with W*V columns: key(s) in the high half,
+ *           W*V - 1 - (w*V + e) in the low half, the larger word first - higher score, then lower beam, then lower token (key orders
+ *           -0.0f below +0.0f);
+ *   output  j = 0 .. W-1 is the j-th candidate: score[b][j] = s, parent[b][j] = w, token[b][j] = e.  W <= V: there are always >= W candidates.
+ * A live, unfinished row that holds NaN gives unspecified outputs with parent in [0, W) and token in [0, V).  Every input of a sequence is read
+ * before any of its slab outputs is written.  A finished hypothesis is extended by eos at no cost at every later step.
+ * logits, score, parent or token NULL, score_prev or token_prev NULL at step > 0: FN_E_NULL; B < 1, W or V outside the limits, ld < V,
+ * step < 0, eos >= V or < -1, out_ld < W, prev_ld < W at step > 0: FN_E_SHAPE; both before any launch.
+ *
+ * fn_beam_gather - reorder up to FN_BEAM_GATHER_MAX_JOBS state matrices by parent in one launch (jobs is a HOST array):
+ *   dst_k[r][c] = src_k[(r / W) * W + clamp(parent[r], 0, W-1)][c]    for r < rows (= B*W, a multiple of W), c < cols_k;  parent [rows] int32.
+ * 16-byte copies where a job's pointers and leading dimensions allow, scalar copies otherwise; entries beyond cols_k are not touched.
+ * dst must not alias src.  jobs, parent, a src or a dst NULL: FN_E_NULL; n_jobs outside [1, FN_BEAM_GATHER_MAX_JOBS]: FN_E_COUNT; rows < 1,
+ * W outside [1, FN_BEAM_MAX_W], rows % W != 0, cols < 1, a leading dimension < cols, dst == src: FN_E_SHAPE.
+ *
+ * fn_beam_backtrack - the W final hypotheses of every sequence from the slabs parent / token / score [steps][B][W] (contiguous), one thread
+ * per (b, j):  cur = j;  for t = steps-1 .. 0:  p = clamp(parent[t][b][cur], 0, W-1);  tokens_out[b][j][t] = token[t][b][cur];
+ * cum_out[b][j][t] = score[t][b][cur] (the cumulative score along the path);  beam_out[b][j][t] = p - the row of step t's logits / logp_out
+ * the hypothesis extended;  cur = p.   len_out[b][j] = 1 + the first t with tokens_out[b][j][t] == eos, or steps (eos = -1: steps);
+ * score_out[b][j] = score[steps-1][b][j].  As a finished hypothesis keeps being extended by eos, the positions after its end hold eos and
+ * repeat its final score.  tokens_out / beam_out / cum_out [B][W][steps]; beam_out and cum_out may be NULL.
+ * A required pointer NULL: FN_E_NULL; steps, B < 1, W outside [1, FN_BEAM_MAX_W], eos < -1: FN_E_SHAPE. */
+#define FN_BEAM_MAX_W 16
+#define FN_BEAM_GATHER_MAX_JOBS 4
+typedef struct FnBeamGatherJob {
+    const float* src;         /* [rows][src_ld]                                                */
+    int32_t src_ld;
+    float* dst;               /* [rows][dst_ld]                                                */
+    int32_t dst_ld;
+    int32_t cols;
+} FnBeamGatherJob;
+int fn_beam_step(const float* logits, int B, int W, int V, int ld, int step, int eos, const float* score_prev, const int32_t* token_prev,
+                 int prev_ld, float* score, int32_t* parent, int32_t* token, int out_ld, float* logp_out, int64_t logp_ld, void* stream);
+int fn_beam_gather(const FnBeamGatherJob* jobs, int n_jobs, int rows, int W, const int32_t* parent, void* stream);
+int fn_beam_backtrack(const int32_t* parent, const int32_t* token, const float* score, int steps, int B, int W, int eos,
+                      int32_t* tokens_out, int32_t* beam_out, float* cum_out, int32_t* len_out, float* score_out, void* stream);
+
 /* TIME-axis log_softmax of the sub-decoders (gmm_model.py:110,115; the reference's dim=1 quirk).
  * logits [Tr][B][Cc] time-major.  logp_bt [B][Tr][Cc].  target [B][Tr] or NULL.
  * nll_bc [B][Cc] (sum over t with target==c of -logp) ; dlogits [Tr][B][Cc] = grad_scale * dNLLsum/dlogits. */

@@ -33,6 +33,8 @@ FN_E_COMM = -7
 FN_COMM_ID_BYTES = 128
 FN_COLSUM_MAX_JOBS = 64
 FN_SAMPLE_MAX_V = 1024
+FN_BEAM_MAX_W = 16
+FN_BEAM_GATHER_MAX_JOBS = 4
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
 vp = C.c_void_p
@@ -97,6 +99,10 @@ class FnSampleParams(C.Structure):
                 ("inv_temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FnBeamGatherJob(C.Structure):
+    _fields_ = [("src", vp), ("src_ld", C.c_int32), ("dst", vp), ("dst_ld", C.c_int32), ("cols", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fadernets.h
 SIGNATURES = {
     "fn_version": (C.c_int, []),
@@ -144,6 +150,9 @@ SIGNATURES = {
     "fn_out_head_f32": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_float, vp, vp, C.c_int, vp]),
     "fn_vocab_argmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, vp]),
     "fn_vocab_sample": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "fn_beam_step": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, vp]),
+    "fn_beam_gather": (C.c_int, [C.POINTER(FnBeamGatherJob), C.c_int, C.c_int, C.c_int, vp, vp]),
+    "fn_beam_backtrack": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),
     "fn_time_logsoftmax_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_latent_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

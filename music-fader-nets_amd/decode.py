@@ -55,6 +55,7 @@ def fed_tokens(tokens, forced, force):
     return torch.where(m.view(1, -1), forced[:, :tokens.shape[1]].to(device=tokens.device, dtype=tokens.dtype), tokens)
 
 
+BEAM_MAX_WIDTH = 16        # FN_BEAM_MAX_W of include/fadernets.h
 MAX_MASKED_GRAPHS = 4      # cached decode graphs whose key carries a mask (the unmasked ones are bounded by the shapes in use)
 
 
@@ -223,6 +224,124 @@ def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, 
     return logp, tokens
 
 
+def _beam_args(steps, width, eos, length_penalty):
+    """validated (W, eos as the kernels take it: -1 = none, length_penalty as a float); ValueError before anything is launched"""
+    if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)) or steps < 1:
+        raise ValueError("steps: a positive int, got %r" % (steps,))
+    if isinstance(width, (bool, np.bool_)) or not isinstance(width, (int, np.integer)) or not 1 <= int(width) <= BEAM_MAX_WIDTH:
+        raise ValueError("width: an int in [1, %d], got %r" % (BEAM_MAX_WIDTH, width))
+    if eos is not None and (isinstance(eos, (bool, np.bool_)) or not isinstance(eos, (int, np.integer)) or not 0 <= int(eos) < E_VOCAB):
+        raise ValueError("eos: None or a token in [0, %d), got %r" % (E_VOCAB, eos))
+    if (isinstance(length_penalty, (bool, np.bool_)) or not isinstance(length_penalty, (int, float, np.integer, np.floating))
+            or not np.isfinite(length_penalty)):
+        raise ValueError("length_penalty: a finite number, got %r" % (length_penalty,))
+    return int(width), -1 if eos is None else int(eos), float(length_penalty)
+
+
+def _beam_buffers(z, W, steps, keep_logp):
+    """every tensor the beam loop writes, at its final size (nothing is allocated inside a capture)"""
+    Bi, dev = z.shape[0], z.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    return dict(zs=z.clone(), score=torch.zeros(steps, Bi, W, device=dev), parent=torch.zeros(steps, Bi, W, **i32), token=torch.zeros(steps, Bi, W, **i32),
+                rows=torch.empty(steps, Bi * W, E_VOCAB, device=dev) if keep_logp else None,
+                tokens=torch.zeros(Bi, W, steps, **i32), beam=torch.zeros(Bi, W, steps, **i32), cum=torch.zeros(Bi, W, steps, device=dev),
+                lens=torch.zeros(Bi, W, **i32), final=torch.zeros(Bi, W, device=dev))
+
+
+def _beam_body(eng, bufs, W, steps, eos, run_steps=None):
+    """the launches of beam_decode on the buffers of _beam_buffers: per step {layer-1 cell, layer-2 cell with its projection, output GEMM, fn_beam_step,
+    fn_beam_gather}, then one fn_beam_backtrack.  The cells write the `cur` states, the gather writes the states the next step reads (rows reordered by
+    parent beam); layer 1's gx_rowbias is the same for all beams of a sequence and needs no reorder.  run_steps < steps: a warm-up of the first steps."""
+    ops, P, H = eng.ops, eng.p, eng.H
+    z = bufs["zs"]
+    R = z.shape[0] * W
+    zr = eng.buf("beam_z", (R, z.shape[1]))
+    zr.view(z.shape[0], W, z.shape[1]).copy_(z.unsqueeze(1).expand(z.shape[0], W, z.shape[1]))
+    h0g = eng.buf("beam_h0g", (R, H))
+    ops.gemm(zr, P["linear_init_global.weight"], h0g, bias=P["linear_init_global.bias"])
+    rbg = eng.buf("beam_rbg", (R, 3 * H))
+    ops.gemm(zr, P["grucell_g.weight_ih"][:, E_VOCAB:], rbg)
+    cur0, cur1, nxt0, nxt1 = (eng.buf("beam_" + n, (R, H)) for n in ("cur0", "cur1", "nxt0", "nxt1"))
+    logits = eng.buf("beam_logits", (R, LOGIT_LD))
+    score, parent, token, rows = bufs["score"], bufs["parent"], bufs["token"], bufs["rows"]
+    n = steps if run_steps is None else min(steps, run_steps)
+    for i in range(n):
+        ops.gru_cell(h0g if i == 0 else nxt0, P["grucell_g.weight_hh"], P["grucell_g.bias_hh"], cur0, b_ih=P["grucell_g.bias_ih"], gx_table=eng.tab["g"],
+                     start_token=E_VOCAB - 1, gx_rowbias=rbg, idx=token[i - 1].view(-1) if i > 0 else None)
+        ops.gru_cell(cur0 if i == 0 else nxt1, P["grucell_g_2.weight_hh"], P["grucell_g_2.bias_hh"], cur1, x=cur0, w_ih=P["grucell_g_2.weight_ih"],
+                     b_ih=P["grucell_g_2.bias_ih"])
+        ops.gemm(cur1, P["linear_out_g.weight"], logits[:, :E_VOCAB], bias=P["linear_out_g.bias"])
+        ops.beam_step(logits, W, E_VOCAB, i, eos, score[i - 1] if i > 0 else None, token[i - 1] if i > 0 else None, score[i], parent[i], token[i],
+                      logp_out=None if rows is None else rows[i])
+        if i + 1 < steps:          # nothing reads the states of the last step
+            ops.beam_gather([(cur0, nxt0), (cur1, nxt1)], parent[i].view(-1), W)
+    if n == steps:
+        ops.beam_backtrack(parent, token, score, eos, bufs["tokens"], bufs["lens"], bufs["final"], beam_out=bufs["beam"], cum_out=bufs["cum"])
+
+
+@torch.no_grad()
+def beam_decode(model, z, steps, width=4, eos=None, length_penalty=0.0, want_logp=False, use_graph=None, trace=False):
+    """Beam search to width W: z (Bi, 2Z+24) -> (tokens (Bi, W, steps) int32, scores (Bi, W) fp32, lengths (Bi, W) int32), the W most likely token
+    sequences the search finds under each latent, best first; scores are the summed log-probs (fp32, include/fadernets.h at fn_beam_step has the
+    exact arithmetic and the tie order: higher score, then lower beam, then lower token).
+
+    eos: None, or a token that ends a hypothesis - it is then extended by eos at no cost, so the positions after its end hold eos, its score stays
+    and lengths = 1 + the first position holding eos (steps where there is none).  length_penalty != 0 re-sorts the W hypotheses of a latent by
+    score / length ** length_penalty (stable; the scores returned stay the sums).  want_logp: a fourth result (Bi, W, steps, 342), the model's own
+    log-probs along each returned hypothesis (the row that scored its token at every step; after a hypothesis' end: the model fed eos).  trace=True
+    appends a dict of the raw slabs score / parent / token (steps, Bi, W), rows (steps, Bi*W, 342) = every step's log-prob rows, beam / cum
+    (Bi, W, steps) and order (Bi, W), all but order in the kernels' order (before the length_penalty sort).  width = 1 is a greedy decode.
+
+    The reference has no counterpart (its loop feeds one argmax stream, gmm_model.py:73-80,119-149).  Every batch size takes Bi*W rows (z repeated
+    W-fold) through per-token launches: the two fn_gru_cell_f32 cells, the output GEMM, fn_beam_step and fn_beam_gather per step, one
+    fn_beam_backtrack at the end.  On the GPU the loop is captured once per (Bi, W, steps, eos, log-probs kept, arithmetic) into Engine._beam_graphs
+    (at most MAX_MASKED_GRAPHS stay, the oldest goes) and replayed on a copy of z.  Not covered: a prompt with beams, and the one-launch decode
+    kernel (it feeds back its own argmax)."""
+    W, eos_k, lpen = _beam_args(steps, width, eos, length_penalty)
+    eng = model.engine()
+    z = z.float().contiguous()
+    keep = bool(want_logp or trace)
+    if use_graph is None:
+        use_graph = z.is_cuda
+    if not use_graph:
+        bufs = _beam_buffers(z, W, steps, keep)
+        _beam_body(eng, bufs, W, steps, eos_k)
+    else:
+        cache = eng.__dict__.setdefault("_beam_graphs", {})
+        key = (z.shape[0], W, steps, eos_k, keep, bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)),
+               getattr(eng.ops, "cell_x6_rows", None), bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)))
+        ent = cache.get(key)
+        if ent is None:
+            bufs = _beam_buffers(z, W, steps, keep)
+            _beam_body(eng, bufs, W, steps, eos_k, run_steps=2)          # warm-up: every scratch buffer exists at its final size before the capture
+            g = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            getattr(eng.ops, "begin_capture", lambda: None)()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                _beam_body(eng, bufs, W, steps, eos_k)
+            ent = cache[key] = (g, bufs)
+            if len(cache) > MAX_MASKED_GRAPHS:        # every entry owns static slabs (and log-prob rows): the oldest goes
+                del cache[next(iter(cache))]
+        g, bufs = ent
+        bufs["zs"].copy_(z)
+        g.replay()
+        bufs = {k: (None if v is None else v.clone()) for k, v in bufs.items()}
+    tokens, scores, lens, beam = bufs["tokens"], bufs["final"], bufs["lens"], bufs["beam"]
+    Bi = z.shape[0]
+    order = torch.arange(W, device=z.device).view(1, W).expand(Bi, W)
+    if lpen != 0.0:
+        order = torch.sort(-(scores / lens.to(scores.dtype) ** lpen), dim=1, stable=True)[1]
+    ar = torch.arange(Bi, device=z.device).view(Bi, 1)
+    res = [tokens[ar, order], scores[ar, order], lens[ar, order]]
+    if want_logp:
+        rows = bufs["rows"].view(steps, Bi, W, E_VOCAB)
+        b = beam[ar, order].long()                                                      # (Bi, W, steps)
+        res.append(rows[torch.arange(steps, device=z.device).view(1, 1, steps), ar.view(Bi, 1, 1), b])
+    if trace:
+        res.append(dict(score=bufs["score"], parent=bufs["parent"], token=bufs["token"], rows=bufs["rows"], beam=beam, cum=bufs["cum"], order=order))
+    return tuple(res)
+
+
 def _single_launch_ok(eng, z):
     """small batches decode as ONE launch (fn_decode_greedy: weight slices resident in LDS, activations handed over through L2)"""
     lo, hi = getattr(eng, "single_launch_skip", (0, -1))
@@ -343,7 +462,7 @@ def clean_output(out):
 
 
 @torch.no_grad()
-def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None, sample=None):
+def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None, sample=None, beam=None):
     """Batched RhythmEvaluator.shift / NoteEvaluator.shift (test_class.py:233-254, :282-303) and the notebook's
     lambda*shift-vector transfer (cells 11 + 15): every (sample, fader value) pair is one row of ONE decode batch.
 
@@ -354,9 +473,17 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
     which is what V separate reference calls consume; None = drawn here (r first, then n).
     prompt: (P,) or (1, P) tokens every (sample, value) row starts with (continue_from), or None.
     sample: None = the greedy decode; a dict of sample_decode's keywords (temperature, top_k, top_p, seed, offset) = drawn continuations.
+    beam: None, or a dict of beam_decode's keywords (width, eos, length_penalty) = every row's best hypothesis; not with sample or prompt.
     Returns (tokens (n, V, steps) int32, z0 (n,) or (n, V): the value of z_which[:, 0] before the change; which="both": z_r's)."""
     if which not in ("r", "n", "both") or mode not in ("set", "shift") or (which == "both" and mode == "set"):
         raise ValueError("which in {r, n, both}, mode in {set, shift}; 'both' only with mode='shift'")
+    if beam is not None:
+        if sample is not None or prompt is not None:
+            raise ValueError("beam goes with neither sample nor prompt")
+        unknown = set(beam) - {"width", "eos", "length_penalty"}
+        if unknown:
+            raise ValueError("beam: keys among width, eos, length_penalty; got %s" % sorted(unknown, key=str))
+        _beam_args(steps, beam.get("width", 4), beam.get("eos"), beam.get("length_penalty", 0.0))
     was_training = model.training
     model.eval()
     try:
@@ -385,7 +512,9 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
         c = chroma.float().to(dev).unsqueeze(1).expand(n, V, chroma.shape[-1])
         z = torch.cat([zr, zn, c], dim=2).reshape(n * V, -1)
         pr = None if prompt is None else (prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))).reshape(1, -1)
-        if sample is not None:
+        if beam is not None:
+            tok = beam_decode(model, z, steps, **beam)[0][:, 0].contiguous()
+        elif sample is not None:
             unknown = set(sample) - {"temperature", "top_k", "top_p", "seed", "offset"}
             if unknown:
                 raise ValueError("sample: keys among temperature, top_k, top_p, seed, offset; got %s" % sorted(unknown, key=str))

@@ -598,6 +598,51 @@ class HipOps:
                                             0 if own_out is None else (own_out.stride(0) if own_out.dim() else 1), _p(tok_out),
                                             tok_out.stride(0) if tok_out.dim() else 1, _p(u_out), self.stream()), "fn_vocab_sample")
 
+    def beam_step(self, logits, W, V, step, eos, score_prev, token_prev, score, parent, token, logp_out=None):
+        """fn_beam_step: logits [B*W][ld]; score_prev / token_prev (None at step 0) and score / parent / token: 2-D views [B][W] (fp32 / int32, any row
+        stride, the two previous ones sharing theirs, the three outputs theirs); eos: a token or -1; logp_out: 2-D view [B*W][V] (any row stride) or None"""
+        pl, rows, _, ld = _mat(logits, "logits")
+        if rows % W or any(t is not None and (t.dim() != 2 or tuple(t.shape) != (rows // W, W) or (W > 1 and t.stride(1) != 1))
+                           for t in (score_prev, token_prev, score, parent, token)):
+            raise RuntimeError("beam_step: %d rows do not make [B][%d] slabs" % (rows, W))
+        _chk(score_prev, name="score_prev"), _chk(token_prev, torch.int32, "token_prev"), _chk(score, name="score")
+        _chk(parent, torch.int32, "parent"), _chk(token, torch.int32, "token")
+        sld = lambda t: t.stride(0) if t.shape[0] > 1 else max(W, t.stride(0))      # noqa: E731
+        if len({sld(t) for t in (score, parent, token)}) != 1 or (score_prev is not None and token_prev is not None and sld(score_prev) != sld(token_prev)):
+            raise RuntimeError("beam_step: the slabs of one step share a row stride")
+        lp_ld = 0
+        if logp_out is not None:
+            _chk(logp_out, name="logp_out")
+            lp_ld = logp_out.stride(0)
+        _lib.check(self.lib.fn_beam_step(pl, rows // W, W, V, ld, int(step), int(eos), _p(score_prev), _p(token_prev),
+                                         0 if score_prev is None else sld(score_prev), _p(score), _p(parent), _p(token), sld(score), _p(logp_out), lp_ld,
+                                         self.stream()), "fn_beam_step")
+
+    def beam_gather(self, jobs, parent, W):
+        """fn_beam_gather: jobs = up to 4 (src, dst) pairs of 2-D views [rows][cols]; dst[r] = src[(r // W) * W + parent[r]]; parent: contiguous [rows] int32"""
+        arr = (_lib.FnBeamGatherJob * len(jobs))()
+        _dense(parent, torch.int32, "parent")
+        rows = parent.numel()
+        for j, (src, dst) in zip(arr, jobs):
+            ps, rs, cs, lds = _mat(src, "src")
+            pd, rd, cd, ldd = _mat(dst, "dst")
+            if (rs, cs) != (rd, cd) or rs != rows:
+                raise RuntimeError("beam_gather: src%s dst%s for %d rows" % (tuple(src.shape), tuple(dst.shape), rows))
+            j.src, j.src_ld, j.dst, j.dst_ld, j.cols = ps, lds, pd, ldd, cs
+        _lib.check(self.lib.fn_beam_gather(arr, len(jobs), rows, int(W), _p(parent), self.stream()), "fn_beam_gather")
+
+    def beam_backtrack(self, parent, token, score, eos, tokens_out, len_out, score_out, beam_out=None, cum_out=None):
+        """fn_beam_backtrack: contiguous slabs [steps][B][W] -> tokens_out / beam_out / cum_out [B][W][steps], len_out / score_out [B][W]"""
+        steps, B, W = parent.shape
+        for t, d, n, shp in ((parent, torch.int32, "parent", (steps, B, W)), (token, torch.int32, "token", (steps, B, W)), (score, torch.float32, "score", (steps, B, W)),
+                             (tokens_out, torch.int32, "tokens_out", (B, W, steps)), (beam_out, torch.int32, "beam_out", (B, W, steps)),
+                             (cum_out, torch.float32, "cum_out", (B, W, steps)), (len_out, torch.int32, "len_out", (B, W)), (score_out, torch.float32, "score_out", (B, W))):
+            _dense(t, d, n)
+            if t is not None and tuple(t.shape) != shp:
+                raise RuntimeError("beam_backtrack: %s%s, expected %s" % (n, tuple(t.shape), shp))
+        _lib.check(self.lib.fn_beam_backtrack(_p(parent), _p(token), _p(score), steps, B, W, int(eos), _p(tokens_out), _p(beam_out), _p(cum_out),
+                                              _p(len_out), _p(score_out), self.stream()), "fn_beam_backtrack")
+
     def time_logsoftmax(self, logits, logp_bt=None, target=None, nll_bc=None, grad_scale=0.0, dlogits=None):
         _dense(logits, name="logits"), _dense(logp_bt, name="logp_bt"), _dense(target, torch.int32, "target")
         _dense(nll_bc, name="nll_bc"), _dense(dlogits, name="dlogits")
