@@ -532,6 +532,56 @@ int fn_beam_gather(const FnBeamGatherJob* jobs, int n_jobs, int rows, int W, con
 int fn_beam_backtrack(const int32_t* parent, const int32_t* token, const float* score, int steps, int B, int W, int eos,
                       int32_t* tokens_out, int32_t* beam_out, float* cum_out, int32_t* len_out, float* score_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Constrained decode (decode.Constraints): a logit processor in front of the three heads above and a state update behind them.  There is NO
+ * reference counterpart (the reference's loop feeds back its argmax, gmm_model.py:73-80,119-149); the text below is the specification.  The heads
+ * take -inf logits as they are (lp = -inf, weight 0, a key below every real score), so a ban is a logit of -inf and no head changes.
+ *
+ * The scalars are read from DEVICE memory (params_dev), so a captured graph serves any setting; as they come from memory they are clamped:
+ * n = min(max(n_pitch, 0), 128); token e in [0, V) is the NOTE-ON of pitch p iff p = e - on_lo lies in [0, n), else the NOTE-OFF of pitch p iff
+ * p = e - off_lo lies in [0, n) (the ranges are so cut to [0, V); where they overlap the on range has precedence), else neither.
+ * held [rows][4] uint32: bit p & 31 of word p >> 5 of row r is set iff pitch p sounds in row r.
+ *
+ * fn_constrain_apply - in place on logits [rows][ld], V valid columns (1 <= V <= FN_SAMPLE_MAX_V), columns [V, ld) are not touched; step >= 0;
+ * bias fp32 or NULL, row r reads bias[r*bias_rs + e] (bias_rs = 0: one shared [V] vector); held or NULL; stuck [rows] int32 or NULL.  Per row r:
+ *   1. y[e] = bias ? x[e] + bias[r*bias_rs + e] : x[e]                                  (ONE fp32 add; -inf entries of bias are bans)
+ *   2. G = the eos and grammar bans:  {eos} if 0 <= eos < V && step < min_len;  and, with held != NULL && n > 0, c = popcount(held[r]):
+ *        the note-off of p for every p NOT sounding    if flags & FN_CONSTRAIN_OFF_NEEDS_ON,
+ *        the note-on  of p for every p sounding        if flags & FN_CONSTRAIN_NO_REONSET,
+ *        the note-on  of p for every p NOT sounding    if max_poly > 0 && c >= max_poly   (all 128 bits of held[r] count);
+ *   3. if no e in [0, V) has y[e] > -inf && e not in G, the row is STUCK: G is dropped for this row at this step and stuck[r], when given, is
+ *      incremented (a plain load, add and store by one lane of the row's wavefront; the caller zeroes it);
+ *   4. x[e] = (e in G, row not stuck) ? -inf : y[e].
+ * A row whose bias alone leaves nothing above -inf, or which holds NaN, is stuck or not - unspecified -, every access stays in bounds.
+ * logits or params_dev NULL: FN_E_NULL; rows < 1, V outside [1, FN_SAMPLE_MAX_V], ld < V, step < 0, bias != NULL with bias_rs neither 0 nor
+ * >= V: FN_E_SHAPE; both before any launch.
+ *
+ * fn_constrain_advance - behind the head, one thread per row r; tok = tok_io[r*tok_ld]:
+ *   fix-up  only with logits != NULL ([rows][ld], the rows fn_constrain_apply left): if tok is outside [0, V) or logits[r*ld + tok] == -inf then
+ *           tok = min(max(fallback[r*fb_ld], 0), V - 1) is written back to tok_io[r*tok_ld] and fixed[r] ([rows] int32 or NULL, zeroed by the
+ *           caller) is incremented.  (fn_vocab_sample's draw is a COUNT over fp32 prefix sums that can step down by an ulp across a block border,
+ *           so a zero-weight entry behind the last positive one can be counted in when u is the largest uniform; fallback = its own_out, the
+ *           first-index argmax of the constrained row, is always allowed.  With fn_vocab_argmax the fix-up never fires.)  Without logits tok_io
+ *           is only read.
+ *   state   only with held_in != NULL: held_out[r] = held_in[r] with bit p set if tok is the note-on of p, cleared if tok is the note-off of p
+ *           (a tok outside [0, V) is neither).  held_out may equal held_in; the four words of a row are read before any is written.
+ * tok_io or params_dev NULL, fallback NULL with logits, held_out NULL with held_in: FN_E_NULL; rows < 1, V outside [1, FN_SAMPLE_MAX_V],
+ * tok_ld < 1, with logits: ld < V or fb_ld < 1: FN_E_SHAPE; both before any launch. */
+#define FN_CONSTRAIN_OFF_NEEDS_ON 1
+#define FN_CONSTRAIN_NO_REONSET 2
+#define FN_CONSTRAIN_MAX_PITCH 128
+typedef struct FnConstrainParams {   /* 32 bytes */
+    int32_t on_lo, off_lo, n_pitch;  /* note-on tokens [on_lo, on_lo+n_pitch), note-off [off_lo, off_lo+n_pitch); n_pitch 0 = no grammar, <= 128 */
+    int32_t max_poly;                /* 0: off */
+    int32_t eos, min_len;            /* eos -1: none; eos is banned while step < min_len */
+    uint32_t flags;                  /* FN_CONSTRAIN_OFF_NEEDS_ON = 1, FN_CONSTRAIN_NO_REONSET = 2 */
+    int32_t reserved;
+} FnConstrainParams;
+int fn_constrain_apply(float* logits, int rows, int V, int ld, int step, const FnConstrainParams* params_dev, const float* bias, int64_t bias_rs,
+                       const uint32_t* held, int32_t* stuck, void* stream);
+int fn_constrain_advance(int32_t* tok_io, int tok_ld, int rows, int V, const FnConstrainParams* params_dev, const float* logits, int ld,
+                         const int32_t* fallback, int fb_ld, const uint32_t* held_in, uint32_t* held_out, int32_t* fixed, void* stream);
+
 /* TIME-axis log_softmax of the sub-decoders (gmm_model.py:110,115; the reference's dim=1 quirk).
  * logits [Tr][B][Cc] time-major.  logp_bt [B][Tr][Cc].  target [B][Tr] or NULL.
  * nll_bc [B][Cc] (sum over t with target==c of -logp) ; dlogits [Tr][B][Cc] = grad_scale * dNLLsum/dlogits. */

@@ -64,6 +64,11 @@ int fn_decode_greedy_host(const FnDecode* d, void* stream);                     
 int fn_decode_forced_host(const FnDecode* d, const FnDecodeForce* f, void* stream);                      /* fn_decode_forced */
 int fn_vocab_sample_host(const float* logits, int B, int V, int ld, const FnSampleParams* params, int step, float* logp_out,
                          int64_t logp_ld, int32_t* own_out, int own_ld, int32_t* tok_out, int tok_ld, float* u_out, void* stream);   /* fn_vocab_sample */
+int fn_constrain_apply_host(float* logits, int rows, int V, int ld, int step, const FnConstrainParams* params, const float* bias, int64_t bias_rs,
+                            const uint32_t* held, int32_t* stuck, void* stream);                         /* fn_constrain_apply */
+int fn_constrain_advance_host(int32_t* tok_io, int tok_ld, int rows, int V, const FnConstrainParams* params, const float* logits, int ld,
+                              const int32_t* fallback, int fb_ld, const uint32_t* held_in, uint32_t* held_out, int32_t* fixed,
+                              void* stream);                                                              /* fn_constrain_advance */
 size_t fn_frag_floats_host(int rows, int K);                                                             /* fn_frag_floats */
 size_t fn_gru_gates_floats_host(int B, int H);                                                           /* fn_gru_gates_floats */
 

@@ -35,6 +35,9 @@ FN_COLSUM_MAX_JOBS = 64
 FN_SAMPLE_MAX_V = 1024
 FN_BEAM_MAX_W = 16
 FN_BEAM_GATHER_MAX_JOBS = 4
+CONSTRAIN_OFF_NEEDS_ON = 1      # FN_CONSTRAIN_OFF_NEEDS_ON
+CONSTRAIN_NO_REONSET = 2        # FN_CONSTRAIN_NO_REONSET
+FN_CONSTRAIN_MAX_PITCH = 128
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
 vp = C.c_void_p
@@ -103,6 +106,11 @@ class FnBeamGatherJob(C.Structure):
     _fields_ = [("src", vp), ("src_ld", C.c_int32), ("dst", vp), ("dst_ld", C.c_int32), ("cols", C.c_int32)]
 
 
+class FnConstrainParams(C.Structure):
+    _fields_ = [("on_lo", C.c_int32), ("off_lo", C.c_int32), ("n_pitch", C.c_int32), ("max_poly", C.c_int32), ("eos", C.c_int32),
+                ("min_len", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fadernets.h
 SIGNATURES = {
     "fn_version": (C.c_int, []),
@@ -153,6 +161,8 @@ SIGNATURES = {
     "fn_beam_step": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int64, vp]),
     "fn_beam_gather": (C.c_int, [C.POINTER(FnBeamGatherJob), C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_beam_backtrack": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "fn_constrain_apply": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp, vp, vp]),
+    "fn_constrain_advance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),
     "fn_time_logsoftmax_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_latent_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -9,6 +9,7 @@
 
 #include "../../../include/fadernets_host.h"
 #include "sample_host.h"
+#include "constrain_host.h"
 
 namespace {
 
@@ -562,6 +563,16 @@ int fn_best_tokens_host(const uint64_t* best, int steps, int B, int V, int32_t* 
 int fn_vocab_sample_host(const float* logits, int B, int V, int ld, const FnSampleParams* params, int step, float* logp_out, int64_t logp_ld,
                          int32_t* own_out, int own_ld, int32_t* tok_out, int tok_ld, float* u_out, void*) {
     return fn_sample_host::vocab_sample(logits, B, V, ld, params, step, logp_out, logp_ld, own_out, own_ld, tok_out, tok_ld, u_out);
+}
+
+int fn_constrain_apply_host(float* logits, int rows, int V, int ld, int step, const FnConstrainParams* params, const float* bias, int64_t bias_rs,
+                            const uint32_t* held, int32_t* stuck, void*) {
+    return fn_constrain_host::constrain_apply(logits, rows, V, ld, step, params, bias, bias_rs, held, stuck);
+}
+
+int fn_constrain_advance_host(int32_t* tok_io, int tok_ld, int rows, int V, const FnConstrainParams* params, const float* logits, int ld,
+                              const int32_t* fallback, int fb_ld, const uint32_t* held_in, uint32_t* held_out, int32_t* fixed, void*) {
+    return fn_constrain_host::constrain_advance(tok_io, tok_ld, rows, V, params, logits, ld, fallback, fb_ld, held_in, held_out, fixed);
 }
 
 size_t fn_decode_ws_bytes_host(int B, int H, int) { return (size_t)4 * B * H * sizeof(float) + 16; }

@@ -8,6 +8,7 @@ GEMM, log_softmax + first-index argmax written straight into the token matrix th
 import numpy as np
 import torch
 
+from .constrain import Constraints, constraint_buffers, constraint_stats, load_constraints
 from .engine import E_VOCAB, LOGIT_LD
 
 
@@ -59,8 +60,20 @@ BEAM_MAX_WIDTH = 16        # FN_BEAM_MAX_W of include/fadernets.h
 MAX_MASKED_GRAPHS = 4      # cached decode graphs whose key carries a mask (the unmasked ones are bounded by the shapes in use)
 
 
+def _constraints_arg(constraints, Bi, eos=None, beam=False):
+    """None or the validated Constraints of a decode of Bi sequences; ValueError before anything is launched"""
+    if constraints is None:
+        return None
+    if not isinstance(constraints, Constraints):
+        raise ValueError("constraints: None or a Constraints, got %r" % (constraints,))
+    constraints.bias_rows(Bi)                  # a per-row bias has one row per sequence
+    if beam and constraints.eos is not None and constraints.eos != eos:
+        raise ValueError("constraints.eos (%d) is the beam's eos (%r) or None" % (constraints.eos, eos))
+    return constraints
+
+
 @torch.no_grad()
-def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, force=None):
+def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, force=None, constraints=None):
     """z (Bi, 2Z+24) -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32).
 
     forced (Bi, >= steps) integer tokens + force (a bool per step, or an int P = the first P steps): after step i the decoder is fed
@@ -73,13 +86,21 @@ def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, 
     its projection - fn_gru_cell_f32 -, output GEMM, argmax}; with want_logp=False: {layer-1 cell, layer-2 cell, output layer with the
     argmax in its epilogue - fn_out_argmax_f32}) captured once per (Bi, steps) into a hipGraph and replayed.  The captured
     kernels read the parameters and the engine's weight images IN PLACE (stable addresses, refreshed by Engine.refresh_weights
-    after every optimiser step / load_state_dict), so a graph stays valid when the weights change."""
+    after every optimiser step / load_state_dict), so a graph stays valid when the weights change.
+
+    constraints: None or a Constraints - every step's logits go through fn_constrain_apply before the head and the token that is FED (the forced
+    one at a forced step) through fn_constrain_advance after it, so the log-probs and tokens are those of the constrained distribution (banned
+    entries exactly -inf); want_stats appends dict(stuck, fixed).  Limitation: a constrained decode takes the per-token launches only - never the
+    one-launch kernels fn_decode_greedy / fn_decode_forced and never the fused output layer fn_out_argmax_f32, which feed back their own argmax."""
     eng = model.engine()
     z = z.float().contiguous()
     mask = None
     if forced is not None or force is not None:
         forced, mask = _forced_args(z, steps, forced, force)
-    if _single_launch_ok(eng, z):
+    con = _constraints_arg(constraints, z.shape[0])
+    if con is not None and (not isinstance(steps, (int, np.integer)) or steps < 1):
+        raise ValueError("steps: a positive int, got %r" % (steps,))
+    if con is None and _single_launch_ok(eng, z):
         res = _decode_single_launch(eng, z, steps, want_logp, forced, mask)
         if res is not None:
             return res
@@ -88,52 +109,59 @@ def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, 
         # step draws a new one - goes launch by launch unless the caller asks for the graph
         use_graph = z.is_cuda and (mask is None or not any(b and not a for a, b in zip(mask, mask[1:])))
     if not use_graph:
-        return _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask)
+        cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
+        logp, tokens = _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask, con=cb)
+        return (logp, tokens, constraint_stats(cb)) if con is not None and con.want_stats else (logp, tokens)
     cache = eng.__dict__.setdefault("_decode_graphs", {})
-    # the captured launches depend on the path taken, on the cells' / GEMMs' arithmetic switches and - the per-token paths pick every step's
-    # token pointer on the host - on the mask
+    # the captured launches depend on the path taken, on the cells' / GEMMs' arithmetic switches, on the form of the constraints and - the per-token
+    # paths pick every step's token pointer on the host - on the mask
     key = (z.shape[0], steps, bool(want_logp), z.shape[0] >= eng.cell_decode_rows, bool(getattr(eng, "fused_argmax", True)),
            bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)),
-           getattr(eng.ops, "cell_x6_rows", None), bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)), mask)
+           getattr(eng.ops, "cell_x6_rows", None), bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)),
+           None if con is None else con.key(), mask)
     ent = cache.get(key)
     if ent is None:
         zs = z.clone()
         fs = None if mask is None else forced.clone()
+        cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
         tokens = torch.zeros(z.shape[0], steps, dtype=torch.int32, device=z.device)
         logp = torch.empty(z.shape[0], steps, E_VOCAB, device=z.device) if want_logp else None
-        _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask)      # warm-up: allocates every buffer at its FINAL size (nothing is allocated inside the capture)
+        _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask, con=cb)      # warm-up: allocates every buffer at its FINAL size (nothing is allocated inside the capture)
         g = torch.cuda.CUDAGraph()
         torch.cuda.synchronize()
         getattr(eng.ops, "begin_capture", lambda: None)()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask)
-        ent = cache[key] = (g, zs, logp, tokens, fs)
+            _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask, con=cb)
+        ent = cache[key] = (g, zs, logp, tokens, fs, cb)
         masked = [k for k in cache if k[-1] is not None]
         if len(masked) > MAX_MASKED_GRAPHS:           # each entry keeps its own static logp / tokens buffers: the oldest masked graph goes
             del cache[masked[0]]
-    g, zs, logp, tokens, fs = ent
+    g, zs, logp, tokens, fs, cb = ent
     zs.copy_(z)
     if fs is not None:
         fs.copy_(forced)
+    if cb is not None:
+        load_constraints(cb, con, z.shape[0])
     g.replay()
-    return (None if logp is None else logp.clone()), tokens.clone()
+    logp, tokens = (None if logp is None else logp.clone()), tokens.clone()
+    return (logp, tokens, constraint_stats(cb)) if con is not None and con.want_stats else (logp, tokens)
 
 
-def continue_from(model, z, prompt, steps, want_logp=True):
+def continue_from(model, z, prompt, steps, want_logp=True, constraints=None):
     """Prompted continuation: prompt (Bi, P) tokens, 0 <= P <= steps -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32) where
     tokens[:, :P] is the prompt and the rest is what the model wrote after it (the stream that was fed back); the log-probs are
-    the model's own at every step, i.e. logp[:, i] scores tokens[:, i] given the start token and tokens[:, :i]."""
+    the model's own at every step, i.e. logp[:, i] scores tokens[:, i] given the start token and tokens[:, :i].  constraints: as greedy_decode."""
     prompt = prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))
     if prompt.dim() != 2 or prompt.shape[0] != z.shape[0] or prompt.shape[1] > steps:
         raise ValueError("prompt: (%d, <= %d) tokens, got %s" % (z.shape[0], steps, tuple(prompt.shape)))
     P = prompt.shape[1]
     if P == 0:
-        return greedy_decode(model, z, steps, want_logp)
+        return greedy_decode(model, z, steps, want_logp, constraints=constraints)
     forced = torch.zeros(z.shape[0], steps, dtype=prompt.dtype)
     forced[:, :P] = prompt.cpu()
-    logp, tokens = greedy_decode(model, z, steps, want_logp, forced=forced, force=P)
-    tokens[:, :P] = forced[:, :P].to(device=tokens.device, dtype=tokens.dtype)
-    return logp, tokens
+    res = greedy_decode(model, z, steps, want_logp, forced=forced, force=P, constraints=constraints)
+    res[1][:, :P] = forced[:, :P].to(device=res[1].device, dtype=res[1].dtype)
+    return res
 
 
 def _sample_args(z, steps, temperature, top_k, top_p, seed, offset, prompt):
@@ -169,7 +197,8 @@ def _sample_args(z, steps, temperature, top_k, top_p, seed, offset, prompt):
 
 
 @torch.no_grad()
-def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, want_logp=True, prompt=None, use_graph=None):
+def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, want_logp=True, prompt=None, use_graph=None,
+                  constraints=None):
     """Seeded temperature / top-k / top-p sampling: z (Bi, 2Z+24) -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32).
 
     tokens is the stream that was fed back: the draws, with tokens[:, :P] = prompt (Bi, P <= steps) when one is given; the log-probs are the
@@ -183,45 +212,56 @@ def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, 
     scan steps below Engine.cell_decode_rows rows, cells from there on - with the output GEMM and fn_vocab_sample as the head; the
     one-launch decode kernel is not involved.  On the GPU the launches are captured once per (Bi, steps, want_logp, P, arithmetic) into
     Engine._sample_graphs (at most MAX_MASKED_GRAPHS of them with a prompt: the oldest goes); z, the prompt and the 32 parameter bytes are copied
-    into the graph's buffers, so any seed or setting replays it."""
+    into the graph's buffers, so any seed or setting replays it.
+
+    constraints: None or a Constraints, as greedy_decode takes it: the draw is from the constrained distribution (a banned token has weight 0) and the
+    log-probs are that distribution's.  fn_constrain_advance replaces a drawn token that is banned after all - the draw counts fp32 prefix sums, see
+    include/fadernets.h - by the row's argmax, so a banned token is never fed; want_stats appends dict(stuck, fixed).  The graph's key gains
+    Constraints.key(); the 32 parameter bytes and the bias are copied into its buffers."""
     params, forced, mask, P = _sample_args(z, steps, temperature, top_k, top_p, seed, offset, prompt)
+    con = _constraints_arg(constraints, z.shape[0])
     eng = model.engine()
     z = z.float().contiguous()
+    cb = None
     if use_graph is None:
         use_graph = z.is_cuda
     if not use_graph:
-        logp, tokens = _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask, sample=params.to(z.device))
+        cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
+        logp, tokens = _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask, sample=params.to(z.device), con=cb)
     else:
         cache = eng.__dict__.setdefault("_sample_graphs", {})
-        key = (z.shape[0], steps, bool(want_logp), P, z.shape[0] >= eng.cell_decode_rows,
+        key = (z.shape[0], steps, bool(want_logp), P, z.shape[0] >= eng.cell_decode_rows, None if con is None else con.key(),
                bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)), getattr(eng.ops, "cell_x6_rows", None),
                bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)))
         ent = cache.get(key)
         if ent is None:
             zs, ps = z.clone(), params.to(z.device)
             fs = None if forced is None else forced.clone()
+            cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
             tokens = torch.zeros(z.shape[0], steps, dtype=torch.int32, device=z.device)
             logp = torch.empty(z.shape[0], steps, E_VOCAB, device=z.device) if want_logp else None
-            _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask, sample=ps)   # warm-up, as greedy_decode
+            _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask, sample=ps, con=cb)   # warm-up, as greedy_decode
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
             getattr(eng.ops, "begin_capture", lambda: None)()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask, sample=ps)
-            ent = cache[key] = (g, zs, ps, fs, logp, tokens)
+                _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask, sample=ps, con=cb)
+            ent = cache[key] = (g, zs, ps, fs, logp, tokens, cb)
             prompted = [k for k in cache if k[3]]
             if len(prompted) > MAX_MASKED_GRAPHS:         # as greedy_decode bounds its masked graphs: every prompt length owns static logp / tokens buffers
                 del cache[prompted[0]]
-        g, zs, ps, fs, logp, tokens = ent
+        g, zs, ps, fs, logp, tokens, cb = ent
         zs.copy_(z)
         ps.copy_(params)
         if fs is not None:
             fs.copy_(forced)
+        if cb is not None:
+            load_constraints(cb, con, z.shape[0])
         g.replay()
         logp, tokens = (None if logp is None else logp.clone()), tokens.clone()
     if P:
         tokens[:, :P] = forced[:, :P]
-    return logp, tokens
+    return (logp, tokens, constraint_stats(cb)) if con is not None and con.want_stats else (logp, tokens)
 
 
 def _beam_args(steps, width, eos, length_penalty):
@@ -248,10 +288,13 @@ def _beam_buffers(z, W, steps, keep_logp):
                 lens=torch.zeros(Bi, W, **i32), final=torch.zeros(Bi, W, device=dev))
 
 
-def _beam_body(eng, bufs, W, steps, eos, run_steps=None):
+def _beam_body(eng, bufs, W, steps, eos, run_steps=None, con=None):
     """the launches of beam_decode on the buffers of _beam_buffers: per step {layer-1 cell, layer-2 cell with its projection, output GEMM, fn_beam_step,
     fn_beam_gather}, then one fn_beam_backtrack.  The cells write the `cur` states, the gather writes the states the next step reads (rows reordered by
-    parent beam); layer 1's gx_rowbias is the same for all beams of a sequence and needs no reorder.  run_steps < steps: a warm-up of the first steps."""
+    parent beam); layer 1's gx_rowbias is the same for all beams of a sequence and needs no reorder.  run_steps < steps: a warm-up of the first steps.
+    con: None, or the buffers of constraint_buffers - then fn_constrain_apply runs on the Bi*W rows in front of fn_beam_step, the sounding-pitch words
+    travel through the gather as a third job (4 columns, the words carried as floats: the copy moves all 32 bits) and fn_constrain_advance moves
+    them by the step's tokens."""
     ops, P, H = eng.ops, eng.p, eng.H
     z = bufs["zs"]
     R = z.shape[0] * W
@@ -265,22 +308,34 @@ def _beam_body(eng, bufs, W, steps, eos, run_steps=None):
     logits = eng.buf("beam_logits", (R, LOGIT_LD))
     score, parent, token, rows = bufs["score"], bufs["parent"], bufs["token"], bufs["rows"]
     n = steps if run_steps is None else min(steps, run_steps)
+    held = None
+    if con is not None:
+        held = con["held"]
+        con["stuck"].zero_(), con["fixed"].zero_()
+        if held is not None:
+            held.zero_()
     for i in range(n):
         ops.gru_cell(h0g if i == 0 else nxt0, P["grucell_g.weight_hh"], P["grucell_g.bias_hh"], cur0, b_ih=P["grucell_g.bias_ih"], gx_table=eng.tab["g"],
                      start_token=E_VOCAB - 1, gx_rowbias=rbg, idx=token[i - 1].view(-1) if i > 0 else None)
         ops.gru_cell(cur0 if i == 0 else nxt1, P["grucell_g_2.weight_hh"], P["grucell_g_2.bias_hh"], cur1, x=cur0, w_ih=P["grucell_g_2.weight_ih"],
                      b_ih=P["grucell_g_2.bias_ih"])
         ops.gemm(cur1, P["linear_out_g.weight"], logits[:, :E_VOCAB], bias=P["linear_out_g.bias"])
+        if con is not None:
+            ops.constrain_apply(logits, E_VOCAB, i, con["params"], bias=con["bias"], held=held, stuck=con["stuck"])
         ops.beam_step(logits, W, E_VOCAB, i, eos, score[i - 1] if i > 0 else None, token[i - 1] if i > 0 else None, score[i], parent[i], token[i],
                       logp_out=None if rows is None else rows[i])
         if i + 1 < steps:          # nothing reads the states of the last step
-            ops.beam_gather([(cur0, nxt0), (cur1, nxt1)], parent[i].view(-1), W)
+            if held is None:
+                ops.beam_gather([(cur0, nxt0), (cur1, nxt1)], parent[i].view(-1), W)
+            else:
+                ops.beam_gather([(cur0, nxt0), (cur1, nxt1), (held.view(torch.float32), con["held_g"].view(torch.float32))], parent[i].view(-1), W)
+                ops.constrain_advance(token[i].view(-1), E_VOCAB, con["params"], held_in=con["held_g"], held_out=held)
     if n == steps:
         ops.beam_backtrack(parent, token, score, eos, bufs["tokens"], bufs["lens"], bufs["final"], beam_out=bufs["beam"], cum_out=bufs["cum"])
 
 
 @torch.no_grad()
-def beam_decode(model, z, steps, width=4, eos=None, length_penalty=0.0, want_logp=False, use_graph=None, trace=False):
+def beam_decode(model, z, steps, width=4, eos=None, length_penalty=0.0, want_logp=False, use_graph=None, trace=False, constraints=None):
     """Beam search to width W: z (Bi, 2Z+24) -> (tokens (Bi, W, steps) int32, scores (Bi, W) fp32, lengths (Bi, W) int32), the W most likely token
     sequences the search finds under each latent, best first; scores are the summed log-probs (fp32, include/fadernets.h at fn_beam_step has the
     exact arithmetic and the tie order: higher score, then lower beam, then lower token).
@@ -296,34 +351,45 @@ def beam_decode(model, z, steps, width=4, eos=None, length_penalty=0.0, want_log
     W-fold) through per-token launches: the two fn_gru_cell_f32 cells, the output GEMM, fn_beam_step and fn_beam_gather per step, one
     fn_beam_backtrack at the end.  On the GPU the loop is captured once per (Bi, W, steps, eos, log-probs kept, arithmetic) into Engine._beam_graphs
     (at most MAX_MASKED_GRAPHS stay, the oldest goes) and replayed on a copy of z.  Not covered: a prompt with beams, and the one-launch decode
-    kernel (it feeds back its own argmax)."""
+    kernel (it feeds back its own argmax).
+
+    constraints: None or a Constraints (its eos None or the beam's): every beam row's logits go through fn_constrain_apply, each beam carries its
+    own sounding pitches (reordered by parent with the decoder states), and scores, log-probs and the trace rows are those of the constrained
+    distribution.  A sequence with fewer than W allowed continuations yields hypotheses of score -inf; they are reported as they are.  A per-row bias
+    has one row per latent, shared by its W beams.  want_stats appends dict(stuck, fixed) over the Bi*W beam rows (fixed stays 0) as the last result."""
     W, eos_k, lpen = _beam_args(steps, width, eos, length_penalty)
+    con = _constraints_arg(constraints, z.shape[0], eos, beam=True)
     eng = model.engine()
     z = z.float().contiguous()
     keep = bool(want_logp or trace)
+    cb = None
     if use_graph is None:
         use_graph = z.is_cuda
     if not use_graph:
         bufs = _beam_buffers(z, W, steps, keep)
-        _beam_body(eng, bufs, W, steps, eos_k)
+        cb = None if con is None else constraint_buffers(con, z.shape[0], z.device, repeat=W, gather=True)
+        _beam_body(eng, bufs, W, steps, eos_k, con=cb)
     else:
         cache = eng.__dict__.setdefault("_beam_graphs", {})
-        key = (z.shape[0], W, steps, eos_k, keep, bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)),
+        key = (z.shape[0], W, steps, eos_k, keep, None if con is None else con.key(), bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)),
                getattr(eng.ops, "cell_x6_rows", None), bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)))
         ent = cache.get(key)
         if ent is None:
             bufs = _beam_buffers(z, W, steps, keep)
-            _beam_body(eng, bufs, W, steps, eos_k, run_steps=2)          # warm-up: every scratch buffer exists at its final size before the capture
+            cb = None if con is None else constraint_buffers(con, z.shape[0], z.device, repeat=W, gather=True)
+            _beam_body(eng, bufs, W, steps, eos_k, run_steps=2, con=cb)          # warm-up: every scratch buffer exists at its final size before the capture
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
             getattr(eng.ops, "begin_capture", lambda: None)()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                _beam_body(eng, bufs, W, steps, eos_k)
-            ent = cache[key] = (g, bufs)
+                _beam_body(eng, bufs, W, steps, eos_k, con=cb)
+            ent = cache[key] = (g, bufs, cb)
             if len(cache) > MAX_MASKED_GRAPHS:        # every entry owns static slabs (and log-prob rows): the oldest goes
                 del cache[next(iter(cache))]
-        g, bufs = ent
+        g, bufs, cb = ent
         bufs["zs"].copy_(z)
+        if cb is not None:
+            load_constraints(cb, con, z.shape[0], repeat=W)
         g.replay()
         bufs = {k: (None if v is None else v.clone()) for k, v in bufs.items()}
     tokens, scores, lens, beam = bufs["tokens"], bufs["final"], bufs["lens"], bufs["beam"]
@@ -339,6 +405,8 @@ def beam_decode(model, z, steps, width=4, eos=None, length_penalty=0.0, want_log
         res.append(rows[torch.arange(steps, device=z.device).view(1, 1, steps), ar.view(Bi, 1, 1), b])
     if trace:
         res.append(dict(score=bufs["score"], parent=bufs["parent"], token=bufs["token"], rows=bufs["rows"], beam=beam, cum=bufs["cum"], order=order))
+    if con is not None and con.want_stats:
+        res.append(constraint_stats(cb))
     return tuple(res)
 
 
@@ -374,9 +442,12 @@ def _decode_single_launch(eng, z, steps, want_logp, forced=None, mask=None):
     return logp, tokens
 
 
-def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, forced=None, mask=None, sample=None):
+def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, forced=None, mask=None, sample=None, con=None):
     """sample: None, or the 32 device bytes of FnSampleParams - then `tokens` receives the DRAWN tokens (fn_vocab_sample in place of the argmax
-    launch, never the fused output layer), which are what the next step is fed; forced / mask keep their meaning (a prompt)"""
+    launch, never the fused output layer), which are what the next step is fed; forced / mask keep their meaning (a prompt).
+    con: None, or the buffers of constraint_buffers - then every step is {output GEMM, fn_constrain_apply, the head, fn_constrain_advance on the token
+    that is fed: the forced column at a forced step (state only), else tokens[:, i] with the fix-up}, never the fused output layer.  The advance is
+    left out where it can do nothing: no sounding-pitch state and either a forced token or the argmax head, whose token is never a banned one."""
     ops, P, H = eng.ops, eng.p, eng.H
     Bi = z.shape[0]
     dev = z.device
@@ -397,11 +468,31 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
     hf0 = [eng.buf("dec_hf0_a", (nf,)), eng.buf("dec_hf0_b", (nf,))]
     hf1 = [eng.buf("dec_hf1_a", (nf,)), eng.buf("dec_hf1_b", (nf,))]
 
+    held = None
+    if con is not None:
+        held = con["held"]
+        con["stuck"].zero_(), con["fixed"].zero_()
+        if held is not None:
+            held.zero_()
+
     def head(i):
+        if con is not None:
+            ops.constrain_apply(logits, E_VOCAB, i, con["params"], bias=con["bias"], held=held, stuck=con["stuck"])
         if sample is None:
             ops.vocab_argmax(logits, E_VOCAB, logp[:, i, :] if want_logp else None, tokens[:, i])
-        else:
+        elif con is None:
             ops.vocab_sample(logits, E_VOCAB, sample, i, logp[:, i, :] if want_logp else None, tokens[:, i])
+        else:
+            ops.vocab_sample(logits, E_VOCAB, sample, i, logp[:, i, :] if want_logp else None, tokens[:, i], own_out=con["own"])
+        if con is None:
+            return
+        if mask is not None and mask[i]:
+            if held is not None:
+                ops.constrain_advance(forced[:, i], E_VOCAB, con["params"], held_in=held, held_out=held)
+        elif sample is not None:
+            ops.constrain_advance(tokens[:, i], E_VOCAB, con["params"], logits=logits, fallback=con["own"], held_in=held, held_out=held, fixed=con["fixed"])
+        elif held is not None:
+            ops.constrain_advance(tokens[:, i], E_VOCAB, con["params"], held_in=held, held_out=held)
 
     if Bi >= eng.cell_decode_rows:
         # thousands of rows: every cell is ONE MFMA launch with the gates in its epilogue (fn_gru_cell_f32: LDS-free loop above 512 rows); layer 2 takes its input
@@ -409,7 +500,7 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
         # tokens only (the evaluators' sweeps): the output layer takes the argmax into its epilogue (fn_out_argmax_f32: packed (logit, column)
         # words by 64-bit atomic max, no logits, no argmax launch) and the next layer-1 cell reads its token from the packed word -
         # 3 launches per token; the int32 tokens are unpacked once at the end
-        fused = not want_logp and sample is None and getattr(eng, "fused_argmax", True) and hasattr(ops, "out_argmax")
+        fused = not want_logp and sample is None and con is None and getattr(eng, "fused_argmax", True) and hasattr(ops, "out_argmax")
         best = eng.buf("dec_best", (max(steps, alloc_steps or 0), Bi), dtype=torch.int64)[:steps] if fused else None
         if fused:
             best.zero_()
@@ -462,7 +553,7 @@ def clean_output(out):
 
 
 @torch.no_grad()
-def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None, sample=None, beam=None):
+def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None, sample=None, beam=None, constraints=None):
     """Batched RhythmEvaluator.shift / NoteEvaluator.shift (test_class.py:233-254, :282-303) and the notebook's
     lambda*shift-vector transfer (cells 11 + 15): every (sample, fader value) pair is one row of ONE decode batch.
 
@@ -474,6 +565,7 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
     prompt: (P,) or (1, P) tokens every (sample, value) row starts with (continue_from), or None.
     sample: None = the greedy decode; a dict of sample_decode's keywords (temperature, top_k, top_p, seed, offset) = drawn continuations.
     beam: None, or a dict of beam_decode's keywords (width, eos, length_penalty) = every row's best hypothesis; not with sample or prompt.
+    constraints: None, or a Constraints for whichever decode runs (a per-row bias has n * V rows; its want_stats is not reported here).
     Returns (tokens (n, V, steps) int32, z0 (n,) or (n, V): the value of z_which[:, 0] before the change; which="both": z_r's)."""
     if which not in ("r", "n", "both") or mode not in ("set", "shift") or (which == "both" and mode == "set"):
         raise ValueError("which in {r, n, both}, mode in {set, shift}; 'both' only with mode='shift'")
@@ -513,16 +605,17 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
         z = torch.cat([zr, zn, c], dim=2).reshape(n * V, -1)
         pr = None if prompt is None else (prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))).reshape(1, -1)
         if beam is not None:
-            tok = beam_decode(model, z, steps, **beam)[0][:, 0].contiguous()
+            tok = beam_decode(model, z, steps, constraints=constraints, **beam)[0][:, 0].contiguous()
         elif sample is not None:
             unknown = set(sample) - {"temperature", "top_k", "top_p", "seed", "offset"}
             if unknown:
                 raise ValueError("sample: keys among temperature, top_k, top_p, seed, offset; got %s" % sorted(unknown, key=str))
-            _, tok = sample_decode(model, z, steps, want_logp=False, prompt=None if pr is None else pr.expand(n * V, pr.shape[1]), **sample)
+            tok = sample_decode(model, z, steps, want_logp=False, prompt=None if pr is None else pr.expand(n * V, pr.shape[1]), constraints=constraints,
+                                **sample)[1]
         elif prompt is None:
-            _, tok = greedy_decode(model, z, steps, want_logp=False)
+            tok = greedy_decode(model, z, steps, want_logp=False, constraints=constraints)[1]
         else:
-            _, tok = continue_from(model, z, pr.expand(n * V, pr.shape[1]), steps, want_logp=False)
+            tok = continue_from(model, z, pr.expand(n * V, pr.shape[1]), steps, want_logp=False, constraints=constraints)[1]
         return tok.view(n, V, steps), z0
     finally:
         model.train(was_training)

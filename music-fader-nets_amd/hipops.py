@@ -643,6 +643,41 @@ class HipOps:
         _lib.check(self.lib.fn_beam_backtrack(_p(parent), _p(token), _p(score), steps, B, W, int(eos), _p(tokens_out), _p(beam_out), _p(cum_out),
                                               _p(len_out), _p(score_out), self.stream()), "fn_beam_backtrack")
 
+    def constrain_apply(self, logits, V, step, params, bias=None, held=None, stuck=None):
+        """fn_constrain_apply, in place on logits [rows][ld]; params: the 32 bytes of FnConstrainParams on the device; bias: [V] (shared) or a 2-D view
+        [rows][V] (any row stride), fp32, or None; held: contiguous [rows][4] int32 (the 128 sounding-pitch bits) or None; stuck: [rows] int32 or None"""
+        pl, rows, _, ld = _mat(logits, "logits")
+        _dense(params, torch.uint8, "params"), _dense(held, torch.int32, "held"), _dense(stuck, torch.int32, "stuck")
+        bias_rs = 0
+        if bias is not None and bias.dim() == 2:
+            _, br, bc, bias_rs = _mat(bias, "bias")
+        else:
+            _dense(bias, name="bias")
+            br, bc = rows, (V if bias is None else bias.numel())
+        if (params.numel() != C.sizeof(_lib.FnConstrainParams) or (br, bc) != (rows, V) or (held is not None and tuple(held.shape) != (rows, 4))
+                or (stuck is not None and stuck.numel() != rows)):
+            raise RuntimeError("constrain_apply: params of %d bytes, bias / held / stuck for %d rows of %d tokens" % (C.sizeof(_lib.FnConstrainParams), rows, V))
+        _lib.check(self.lib.fn_constrain_apply(pl, rows, V, ld, int(step), _p(params), _p(bias), bias_rs, _p(held), _p(stuck), self.stream()),
+                   "fn_constrain_apply")
+
+    def constrain_advance(self, tok, V, params, logits=None, fallback=None, held_in=None, held_out=None, fixed=None):
+        """fn_constrain_advance: tok / fallback: int32 1-D views [rows] (any stride); logits [rows][ld] (then the fix-up runs and may rewrite tok) or None;
+        held_in / held_out: contiguous [rows][4] int32 (may be the same tensor) or None; fixed: [rows] int32 or None"""
+        _chk(tok, torch.int32, "tok"), _chk(fallback, torch.int32, "fallback")
+        _dense(params, torch.uint8, "params"), _dense(held_in, torch.int32, "held_in"), _dense(held_out, torch.int32, "held_out"), _dense(fixed, torch.int32, "fixed")
+        rows = tok.numel()
+        pl, ld = None, 0
+        if logits is not None:
+            pl, lr, _, ld = _mat(logits, "logits")
+            if lr != rows or fallback is None or fallback.numel() != rows:
+                raise RuntimeError("constrain_advance: logits and fallback for %d rows" % rows)
+        if (tok.dim() != 1 or params.numel() != C.sizeof(_lib.FnConstrainParams) or (held_in is None) != (held_out is None)
+                or any(h is not None and tuple(h.shape) != (rows, 4) for h in (held_in, held_out)) or (fixed is not None and fixed.numel() != rows)):
+            raise RuntimeError("constrain_advance: a 1-D tok, params of %d bytes, held_in and held_out [%d][4]" % (C.sizeof(_lib.FnConstrainParams), rows))
+        _lib.check(self.lib.fn_constrain_advance(_p(tok), max(1, tok.stride(0)), rows, V, _p(params), pl, ld, _p(fallback),
+                                                 1 if fallback is None else max(1, fallback.stride(0)), _p(held_in), _p(held_out), _p(fixed),
+                                                 self.stream()), "fn_constrain_advance")
+
     def time_logsoftmax(self, logits, logp_bt=None, target=None, nll_bc=None, grad_scale=0.0, dlogits=None):
         _dense(logits, name="logits"), _dense(logp_bt, name="logp_bt"), _dense(target, torch.int32, "target")
         _dense(nll_bc, name="nll_bc"), _dense(dlogits, name="dlogits")
