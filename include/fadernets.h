@@ -582,6 +582,78 @@ int fn_constrain_apply(float* logits, int rows, int V, int ld, int step, const F
 int fn_constrain_advance(int32_t* tok_io, int tok_ld, int rows, int V, const FnConstrainParams* params_dev, const float* logits, int ld,
                          const int32_t* fallback, int fb_ld, const uint32_t* held_in, uint32_t* held_out, int32_t* fixed, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Controllability metrics of decoded event tokens (attributes.py): rhythm density and note density per row (fn_event_attributes)
+ * and the three scores of a fader sweep (fn_sweep_scores).  The reference measures through a MIDI file (test_class.py:124-139); the
+ * part that decides the numbers is restated here in integers.  The reference's: the piano-roll fill (the vendored parse_pretty_midi,
+ * polyphonic_event_based_v2.py:334-414), convert_pr_to_pitch_lst / pitch_lst_to_rhythm (:13-29, :140-158), get_classes
+ * (test_class.py:59-70) and the calculate_* methods (:259-272, :308-321).  OURS: the step from tokens to timed notes - Magenta's
+ * performance decoder was not at hand - and the beat grid, which pretty_midi estimates and which is fixed here to a first beat at 0
+ * and 120 qpm.
+ *
+ * fn_event_attributes: tokens [rows][tok_ld] int32, `steps` columns used.  Parameters as read from device memory and clamped:
+ * n_pitch to [0, 128], n_shift to [0, 4096], ticks_num to [1, 32768], ticks_den to [1, 256], beat_cells to [1, 64] (so that every n_cells fits
+ * an int32); the other fields as they are.  A token e with vocab_size > 0 and e outside [0, vocab_size) belongs to no range.
+ *   tokens -> notes   A row is read from column 0 up to, not including, the first token equal to eos (eos < 0: none), or to
+ *           `steps`.  A clock t counts ticks of 10 ms from 0.  In this order: a token in [on_lo, on_lo + n_pitch) is the note-on of
+ *           pitch p = e - on_lo: if p is open, its note is first closed at t (re-strike); then p is open with t0 = t.  A token in
+ *           [off_lo, off_lo + n_pitch) is the note-off of p: the open note of p is closed at t1 = t; ignored if none is open.  A token
+ *           in [shift_lo, shift_lo + n_shift) adds e - shift_lo + 1 to t.  Every other token (pad, velocity, ...) is skipped;
+ *           velocity is not tracked (the attributes ask pr > 0 only, and every decodable velocity is >= 1).  The end of the row closes
+ *           every open note at the final t.  A closed note with t1 == t0 is dropped.
+ *   notes -> grid     One cell is ticks_num / ticks_den ticks (25/2: sixteenth notes at 120 qpm).  Onset cell
+ *           a = (2*den*t0 + num) / (2*num) (round), end cell b = (den*t1) / num (floor), integer divisions in 64 bits.  t_last = the
+ *           largest t1 of a kept note; n_cells = beat_cells * ((t_last*den) / (num*beat_cells) + 1).  Per pitch, in the order the
+ *           notes close (polyphonic_event_based_v2.py:394-412): if 0 < a < n_cells and cell a-1 of p is set, it is cleared; if
+ *           b < n_cells - 1 and cell b of p is set, b -= 1; cells [a, min(b, n_cells)) of p are set.  The clear happens even when the
+ *           note then fills nothing.
+ *   grid -> attributes  With S[c] the set of pitches set in cell c: notes[c] = |S[c]|; rhythm[c] = 0 if S[c] is empty, else 1 for
+ *           c == 0, else 2 (hold) if S[c] is a subset of S[c-1], else 1 (onset).  onsets = #{c: rhythm[c] == 1}, total = sum notes[c].
+ *           r_density = (float)((double)onsets / n_cells), n_density = (float)((double)total / n_cells);
+ *           c_r = 0 if 10*onsets < 3*n_cells, 1 if 2*onsets < n_cells, else 2;  c_n = 0 if total <= 2*n_cells, 1 if 2*total <=
+ *           7*n_cells, else 2 (get_classes' thresholds 0.3 / 0.5 and 2 / 3.5, decided on the integers).
+ *   status  0; FN_ATTR_EMPTY: no kept note - n_cells 0, densities 0, classes 0 (the reference skips such a track);
+ *           FN_ATTR_OVERFLOW: n_cells > cells_ld - n_cells is the true count, densities NaN, classes -1.
+ * Outputs [rows] each: n_cells, status, r_density, n_density, c_r, c_n; optional (NULL: not wanted) rhythm, notes uint8
+ * [rows][cells_ld]: cells [0, n_cells) of a row with status 0, 0 in every other cell up to cells_ld; nothing behind cells_ld.
+ * One wavefront per row; dynamic LDS 4*steps + 512*ceil(cells_ld/32) bytes (<= 36 KB).
+ * NULL tokens / params_dev / one of the six [rows] outputs: FN_E_NULL; rows < 1, steps outside [1, FN_ATTR_MAX_STEPS], cells_ld
+ * outside [1, FN_ATTR_MAX_CELLS], tok_ld < steps: FN_E_SHAPE; both before any launch.
+ *
+ * fn_sweep_scores (test_class.py:169-175, 259-272, 308-321), everything in fp64: r, n [S][Vn] fp32 densities of S samples at Vn
+ * fader values, status [S][Vn], values [Vn] fp64 on the device, which 0: rhythm is swept / 1: note.  A sample with any non-zero
+ * status is left out; n_used counts the others.  x = the swept attribute / its std, o = the other one / its std (r_std, n_std):
+ *   scores[0] consistency     = 1 - mean_v std_s(x)
+ *   scores[1] restrictiveness = 1 - mean_s std_v(o)
+ *   scores[2] monotonicity    = mean_s R2_s, R2_s = 1 - SS_res / SS_tot of the least-squares line of the UNSCALED swept density
+ *                               against values (slope 0 when the values are all equal); R2_s = 1 where SS_tot == 0, which is what
+ *                               LinearRegression().score gives for a flat response
+ *   scores[3] variance        = mean_s std_v(x)                       (calculate_variance, :262-263; printed by nobody)
+ * std is the population std about the mean.  n_used == 0: four NaN.  Order of the sums, so that a result does not depend on the
+ * launch: over values ascending from 0.0; over samples in 16 partial sums - partial j takes the used samples s = j, j + 16, ...
+ * ascending from 0.0 - combined as a[i] += a[i + h] for h = 8, 4, 2, 1.
+ * One launch of one workgroup of 16 wavefronts.  NULL r / n / status / values / scores / n_used: FN_E_NULL; S outside
+ * [1, FN_ATTR_MAX_SAMPLES], Vn outside [2, 64], which outside {0, 1}: FN_E_SHAPE; both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_ATTR_MAX_STEPS 1024
+#define FN_ATTR_MAX_CELLS 2048
+#define FN_ATTR_MAX_SAMPLES 4096
+#define FN_ATTR_EMPTY 1
+#define FN_ATTR_OVERFLOW 2
+typedef struct FnAttrParams {        /* 48 bytes */
+    int32_t on_lo, off_lo, n_pitch;  /* as FnConstrainParams */
+    int32_t shift_lo, n_shift;       /* time-shift tokens [shift_lo, shift_lo+n_shift): shift_lo + k = k + 1 ticks */
+    int32_t eos;                     /* -1: none */
+    int32_t ticks_num, ticks_den;    /* ticks per cell */
+    int32_t beat_cells;              /* cells per beat: n_cells is a whole number of beats */
+    int32_t vocab_size;              /* <= 0: no cut */
+    int32_t reserved[2];
+} FnAttrParams;
+int fn_event_attributes(const int32_t* tokens, int tok_ld, int rows, int steps, const FnAttrParams* params_dev, int32_t* n_cells, int32_t* status,
+                        float* r_density, float* n_density, int32_t* c_r, int32_t* c_n, uint8_t* rhythm, uint8_t* notes, int cells_ld, void* stream);
+int fn_sweep_scores(const float* r, const float* n, const int32_t* status, int S, int Vn, const double* values, int which, double r_std,
+                    double n_std, double* scores, int32_t* n_used, void* stream);
+
 /* TIME-axis log_softmax of the sub-decoders (gmm_model.py:110,115; the reference's dim=1 quirk).
  * logits [Tr][B][Cc] time-major.  logp_bt [B][Tr][Cc].  target [B][Tr] or NULL.
  * nll_bc [B][Cc] (sum over t with target==c of -logp) ; dlogits [Tr][B][Cc] = grad_scale * dNLLsum/dlogits. */

@@ -38,6 +38,8 @@ FN_BEAM_GATHER_MAX_JOBS = 4
 CONSTRAIN_OFF_NEEDS_ON = 1      # FN_CONSTRAIN_OFF_NEEDS_ON
 CONSTRAIN_NO_REONSET = 2        # FN_CONSTRAIN_NO_REONSET
 FN_CONSTRAIN_MAX_PITCH = 128
+FN_ATTR_MAX_STEPS, FN_ATTR_MAX_CELLS, FN_ATTR_MAX_SAMPLES = 1024, 2048, 4096
+FN_ATTR_EMPTY, FN_ATTR_OVERFLOW = 1, 2
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
 vp = C.c_void_p
@@ -111,6 +113,11 @@ class FnConstrainParams(C.Structure):
                 ("min_len", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32)]
 
 
+class FnAttrParams(C.Structure):
+    _fields_ = [("on_lo", C.c_int32), ("off_lo", C.c_int32), ("n_pitch", C.c_int32), ("shift_lo", C.c_int32), ("n_shift", C.c_int32), ("eos", C.c_int32),
+                ("ticks_num", C.c_int32), ("ticks_den", C.c_int32), ("beat_cells", C.c_int32), ("vocab_size", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fadernets.h
 SIGNATURES = {
     "fn_version": (C.c_int, []),
@@ -163,6 +170,8 @@ SIGNATURES = {
     "fn_beam_backtrack": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "fn_constrain_apply": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp, vp, vp]),
     "fn_constrain_advance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+    "fn_event_attributes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "fn_sweep_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),
     "fn_time_logsoftmax_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_latent_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -7,9 +7,15 @@
 RNG contract: the reference draws from torch's global CPU generator (``Normal(0, 1).sample`` == ``torch.randn``,
 ``dis.rsample()`` == ``torch.randn``); every function here makes the SAME draws in the same order, so
 ``torch.manual_seed(s); shift(...)`` returns what the reference returns after the same seed (tokens bit-exact up to float32
-near-ties; pinned by tests/golden/eval.npz).  The MIDI round trip and the sklearn metrics of ``BaseEvaluator.evaluate``
-(test_class.py:79-194) stay out of scope; ``fader_sweep`` (decode.py) is the batched form of the same shift for throughput.
+near-ties; pinned by tests/golden/eval.npz).  ``fader_sweep`` (decode.py) is the batched form of the same shift for throughput.
+
+  GMMRhythmEvaluator.evaluate / GMMNoteEvaluator.evaluate   test_class.py:79-194, batched: attributes.controllability per round
+
+``evaluate`` measures on the device what the reference measures through a MIDI file (attributes.py says which part is the reference's and which is
+ours); it does NOT keep the reference's one-sample-at-a-time redraw loop or its RNG order - a batched round cannot.
 """
+import random
+
 import numpy as np
 import torch
 
@@ -52,6 +58,37 @@ class GMMRhythmEvaluator:
     def shift(self, model, d, r, n, c, target_z_value, steps=100):
         """-> (out (1, steps, 342) log-probabilities, value of z[:, 0] before the shift)"""
         return _shift(model, d, r, n, c, target_z_value, self.which, steps)
+
+    def evaluate(self, model, min_val, max_val, r_std, n_std, steps=100, **decode):
+        """BaseEvaluator.evaluate (test_class.py:79-194) in batches: `epochs` rounds; a round draws `num_of_samples` indices with
+        random.randint(0, len(ds) - 1) (:106) and makes ONE attributes.controllability call over eight fader values (min + k * (max - min) / 8).
+        Prints the reference's three lines per round and its summary block (:178-194); returns (c_lst, r_lst, m_lst), arrays of length `epochs`.
+        A sample whose decode is empty at some value is discarded as in the reference (:134, :141-145) but NOT redrawn: the round's scores are over the
+        n_used samples that are left, and n_used is printed when it is below num_of_samples.  The reference's one-at-a-time redraw loop and its RNG
+        order are not kept.  **decode: sample / beam / constraints / eps for controllability."""
+        from .attributes import controllability
+        dev = model.mu_r.weight.device
+        c_lst, r_lst, m_lst = [], [], []
+        for _ in range(self.epochs):
+            items = [self.ds[random.randint(0, len(self.ds) - 1)] for _ in range(self.num_of_samples)]
+            d = torch.as_tensor(np.stack([np.asarray(it[0]) for it in items])).to(dev)
+            if d.dim() == 2:
+                d = d.long()                                 # the datasets yield ids as float32 (ptb_v2.py:459-470)
+            c = torch.as_tensor(np.stack([np.asarray(it[3]) for it in items])).float().to(dev)
+            res = controllability(model, d, c, self.which, min_val, max_val, r_std, n_std, steps=steps, n_values=8, **decode)
+            if res["n_used"] < self.num_of_samples:
+                print("Samples used: {} of {}".format(res["n_used"], self.num_of_samples))
+            print("Generator consistency: ", res["consistency"])
+            print("Generator restrictiveness: ", res["restrictiveness"])
+            print("Generator monotonicity:", res["monotonicity"])
+            c_lst.append(res["consistency"]), r_lst.append(res["restrictiveness"]), m_lst.append(res["monotonicity"])
+        c_lst, r_lst, m_lst = np.array(c_lst), np.array(r_lst), np.array(m_lst)
+        print("============================================")
+        print("Consistency: {} +/- {}".format(np.mean(c_lst), np.std(c_lst)))
+        print("Restrictiveness: {} +/- {}".format(np.mean(r_lst), np.std(r_lst)))
+        print("Monotonicity: {} +/- {}".format(np.mean(m_lst), np.std(m_lst)))
+        print("============================================")
+        return c_lst, r_lst, m_lst
 
 
 class GMMNoteEvaluator(GMMRhythmEvaluator):

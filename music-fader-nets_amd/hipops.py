@@ -678,6 +678,38 @@ class HipOps:
                                                  1 if fallback is None else max(1, fallback.stride(0)), _p(held_in), _p(held_out), _p(fixed),
                                                  self.stream()), "fn_constrain_advance")
 
+    def event_attributes(self, tokens, steps, params, n_cells, status, r_density, n_density, c_r, c_n, rhythm=None, notes=None, cells_ld=_lib.FN_ATTR_MAX_CELLS):
+        """fn_event_attributes: tokens int32 [rows][>= steps] (any row stride); params: the 48 bytes of FnAttrParams on the device; six [rows] outputs;
+        rhythm / notes: contiguous uint8 [rows][cells_ld] or None"""
+        _chk(tokens, torch.int32, "tokens"), _dense(params, torch.uint8, "params")
+        if tokens.dim() != 2 or (tokens.shape[1] > 1 and tokens.stride(1) != 1) or tokens.shape[1] < steps:
+            raise RuntimeError("event_attributes: tokens 2-D with contiguous rows of at least %d, got shape %s strides %s" % (steps, tuple(tokens.shape), tokens.stride()))
+        rows = tokens.shape[0]
+        ld = tokens.stride(0) if rows > 1 else max(tokens.shape[1], tokens.stride(0))
+        for t, d, nm in ((n_cells, torch.int32, "n_cells"), (status, torch.int32, "status"), (r_density, torch.float32, "r_density"),
+                         (n_density, torch.float32, "n_density"), (c_r, torch.int32, "c_r"), (c_n, torch.int32, "c_n")):
+            _dense(t, d, nm)
+            if t is None or t.numel() != rows:
+                raise RuntimeError("event_attributes: %s for %d rows" % (nm, rows))
+        for t, nm in ((rhythm, "rhythm"), (notes, "notes")):
+            _dense(t, torch.uint8, nm)
+            if t is not None and tuple(t.shape) != (rows, cells_ld):
+                raise RuntimeError("event_attributes: %s%s, expected %s" % (nm, tuple(t.shape), (rows, cells_ld)))
+        if params.numel() != C.sizeof(_lib.FnAttrParams):
+            raise RuntimeError("event_attributes: params of %d bytes" % C.sizeof(_lib.FnAttrParams))
+        _lib.check(self.lib.fn_event_attributes(_p(tokens), ld, rows, int(steps), _p(params), _p(n_cells), _p(status), _p(r_density), _p(n_density), _p(c_r),
+                                                _p(c_n), _p(rhythm), _p(notes), int(cells_ld), self.stream()), "fn_event_attributes")
+
+    def sweep_scores(self, r, n, status, values, which, r_std, n_std, scores, n_used):
+        """fn_sweep_scores: r, n fp32 and status int32 contiguous [S][Vn]; values fp64 [Vn]; scores fp64 [4]; n_used int32 [1]"""
+        _dense(r, name="r"), _dense(n, name="n"), _dense(status, torch.int32, "status"), _dense(values, torch.float64, "values")
+        _dense(scores, torch.float64, "scores"), _dense(n_used, torch.int32, "n_used")
+        if r.dim() != 2 or n.shape != r.shape or status.shape != r.shape or values.numel() != r.shape[1] or scores.numel() != 4 or n_used.numel() != 1:
+            raise RuntimeError("sweep_scores: r, n, status [S][Vn], values [Vn], scores [4], n_used [1]; got %s %s %s %d" % (
+                tuple(r.shape), tuple(n.shape), tuple(status.shape), values.numel()))
+        _lib.check(self.lib.fn_sweep_scores(_p(r), _p(n), _p(status), r.shape[0], r.shape[1], _p(values), int(which), float(r_std), float(n_std), _p(scores),
+                                            _p(n_used), self.stream()), "fn_sweep_scores")
+
     def time_logsoftmax(self, logits, logp_bt=None, target=None, nll_bc=None, grad_scale=0.0, dlogits=None):
         _dense(logits, name="logits"), _dense(logp_bt, name="logp_bt"), _dense(target, torch.int32, "target")
         _dense(nll_bc, name="nll_bc"), _dense(dlogits, name="dlogits")
