@@ -654,6 +654,74 @@ int fn_event_attributes(const int32_t* tokens, int tok_ld, int rows, int steps, 
 int fn_sweep_scores(const float* r, const float* n, const int32_t* status, int S, int Vn, const double* values, int which, double r_std,
                     double n_std, double* scores, int32_t* n_used, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Event tokens <-> timed notes (notes.py, midi.py): fn_notes_from_tokens publishes the "tokens -> notes" step of fn_event_attributes,
+ * with velocity; fn_tokens_from_notes is its inverse, the tokeniser (magenta_encode_midi over windows, ptb_v2.py:217-273).  The
+ * reference's: the window cut (slice_midi, ptb_v2.py:60-92, made half-open here: the reference also keeps a note that starts exactly
+ * at the window's end, as a zero-length one) and dropping a segment that does not fit (:264; here a status the caller filters by).
+ * OURS, pinned against nothing of Magenta's: the walk from tokens to notes, the order of simultaneous events, and the velocity bins,
+ * which follow Magenta's performance encoding as far as we know it.  Integers only.
+ *
+ * Parameters as read from device memory and clamped: on_lo, off_lo, n_pitch, shift_lo, n_shift, eos, vocab_size exactly as FnAttrParams
+ * (n_pitch to [0, 128], n_shift to [0, 4096]); n_vel to [0, 128]; default_vel to [1, 127]; the other fields as they are.
+ *   velocity  vstep = (127 + n_vel - 1) / n_vel (2 for 64 bins).  Bin k is velocity min(1 + k*vstep, 127); velocity v in [1, 127] is bin
+ *           min((v - 1) / vstep, n_vel - 1).  n_vel == 0: velocity is neither read nor written.
+ *
+ * fn_notes_from_tokens: tokens [rows][tok_ld] int32, `steps` columns used -> notes [rows][notes_ld] FnNote, n_notes, t_end, status [rows].
+ *   The walk is the "tokens -> notes" clause of fn_event_attributes word for word (the row's end at the first eos, re-strike, an ignored
+ *   unmatched note-off, the row's end closing every open note at the final t, a dropped t1 == t0, the vocab_size cut), and one addition:
+ *   the current velocity starts at default_vel, and a token that is in none of the note-on, note-off and time-shift ranges but in
+ *   [vel_lo, vel_lo + n_vel) sets it to the velocity of bin e - vel_lo.  A note carries the velocity current at its note-on token.
+ *   notes[r] holds the kept notes ascending by (t0, pitch) - unique, two kept notes of one pitch cannot share t0.  n_notes is the true
+ *   count; when it exceeds notes_ld the first notes_ld notes of that order are written and status is FN_NOTES_OVERFLOW; n_notes == 0:
+ *   FN_NOTES_EMPTY; else 0.  Entries [n_notes, notes_ld) are zeroed, nothing is written behind notes_ld.  t_end is the final t.
+ *   notes_ld = steps never overflows (every note has its own note-on token).
+ *   One wavefront per row; dynamic LDS 9*steps + 8*P bytes, P = the power of two >= steps (<= 17 KB).
+ *   NULL tokens / params_dev / notes / n_notes / t_end / status: FN_E_NULL; rows < 1, steps outside [1, FN_ATTR_MAX_STEPS], tok_ld < steps,
+ *   notes_ld < 1: FN_E_SHAPE; both before any launch.
+ *
+ * fn_tokens_from_notes: notes [n_total] FnNote in any order, spans [rows] FnNoteSpan -> tokens [rows][tok_ld] (`steps` columns written),
+ * n_tokens, n_kept, status [rows].  Per row with span (first, count, t_lo, t_hi), differences in 64 bits:
+ *   1. count is clamped to [0, FN_NOTES_MAX].  The span is notes[first + k], k < count; a k with first + k outside [0, n_total) is no note.
+ *   2. t_hi is clamped to [t_lo, t_lo + FN_NOTES_MAX_TICK].
+ *   3. A note is kept iff 0 <= pitch < n_pitch, t_lo <= t0 < t_hi and min(t1, t_hi) > t0.
+ *   4. A kept note has the events (t0 - t_lo, ON) and (min(t1, t_hi) - t_lo, OFF); its vel is clamped to [1, 127].
+ *   5. The 2 * n_kept events are ordered ascending by (tick, OFF before ON, pitch, k).  OFF first: a note that ends where the next one of
+ *      its pitch begins survives the decoder's re-strike rule.
+ *   6. The stream starts at clock 0 with no current bin.  Per event, with g = tick - clock: g / n_shift tokens shift_lo + n_shift - 1;
+ *      if g % n_shift, the token shift_lo + g % n_shift - 1; for an ON with n_vel > 0 whose bin differs from the current one, vel_lo + bin
+ *      (which becomes the current one); then on_lo + pitch or off_lo + pitch.  After the last event eos, if add_eos != 0 and eos >= 0
+ *      (a row without a kept note is then eos alone).
+ *   7. n_tokens is the stream's true length (eos included; at most 2^22 + 3 * 1024 + 1).  The first min(n_tokens, steps) tokens are written,
+ *      the columns from there up to `steps` hold pad; nothing is written behind `steps`.
+ *   8. status FN_NOTES_OVERFLOW if n_tokens > steps (the reference drops such a segment), else FN_NOTES_EMPTY if n_kept == 0, else 0.
+ *   9. n_shift == 0: time cannot be written; the result is unspecified (here: no time-shift token), every access stays in bounds.
+ *   Decoding a row with status 0 gives back the kept notes, times relative to t_lo and velocities snapped to their bins, except where two
+ *   kept notes of one pitch overlap or coincide: the decoder's re-strike rule ends the earlier one at the later one's start, and the
+ *   later one at the first note-off that follows.
+ *   One wavefront per row; static LDS 8.5 KB (1024 event keys of tick:23 | kind:1 | pitch:7 | k:10 in 64 bits, 512 bins).
+ *   NULL spans / params_dev / tokens / n_tokens / n_kept / status, or NULL notes with n_total > 0: FN_E_NULL; rows < 1, steps outside
+ *   [1, FN_ATTR_MAX_STEPS], tok_ld < steps, n_total < 0: FN_E_SHAPE; both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_NOTES_MAX 512
+#define FN_NOTES_MAX_TICK (1 << 22)
+#define FN_NOTES_EMPTY 1
+#define FN_NOTES_OVERFLOW 2
+typedef struct FnNote { int32_t t0, t1, pitch, vel; } FnNote;                /* 16 bytes; ticks of 10 ms; pitch = offset in the note range; vel 1..127 */
+typedef struct FnNoteSpan { int32_t first, count, t_lo, t_hi; } FnNoteSpan;  /* 16 bytes */
+typedef struct FnNoteParams {        /* 64 bytes, read from DEVICE memory like FnAttrParams, so a captured graph serves any setting */
+    int32_t on_lo, off_lo, n_pitch, shift_lo, n_shift, eos, vocab_size;      /* as FnAttrParams */
+    int32_t vel_lo, n_vel;           /* velocity tokens [vel_lo, vel_lo + n_vel) */
+    int32_t default_vel;             /* the velocity before the first velocity token (100) */
+    int32_t pad;                     /* written behind the end of a tokenised row (0) */
+    int32_t add_eos;                 /* != 0 and eos >= 0: the tokeniser ends every row with eos */
+    int32_t reserved[4];
+} FnNoteParams;
+int fn_notes_from_tokens(const int32_t* tokens, int tok_ld, int rows, int steps, const FnNoteParams* params_dev, FnNote* notes, int notes_ld,
+                         int32_t* n_notes, int32_t* t_end, int32_t* status, void* stream);
+int fn_tokens_from_notes(const FnNote* notes, int n_total, const FnNoteSpan* spans, int rows, const FnNoteParams* params_dev, int32_t* tokens,
+                         int tok_ld, int steps, int32_t* n_tokens, int32_t* n_kept, int32_t* status, void* stream);
+
 /* TIME-axis log_softmax of the sub-decoders (gmm_model.py:110,115; the reference's dim=1 quirk).
  * logits [Tr][B][Cc] time-major.  logp_bt [B][Tr][Cc].  target [B][Tr] or NULL.
  * nll_bc [B][Cc] (sum over t with target==c of -logp) ; dlogits [Tr][B][Cc] = grad_scale * dNLLsum/dlogits. */

@@ -40,6 +40,8 @@ CONSTRAIN_NO_REONSET = 2        # FN_CONSTRAIN_NO_REONSET
 FN_CONSTRAIN_MAX_PITCH = 128
 FN_ATTR_MAX_STEPS, FN_ATTR_MAX_CELLS, FN_ATTR_MAX_SAMPLES = 1024, 2048, 4096
 FN_ATTR_EMPTY, FN_ATTR_OVERFLOW = 1, 2
+FN_NOTES_MAX, FN_NOTES_MAX_TICK = 512, 1 << 22
+FN_NOTES_EMPTY, FN_NOTES_OVERFLOW = 1, 2
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
 vp = C.c_void_p
@@ -118,6 +120,20 @@ class FnAttrParams(C.Structure):
                 ("ticks_num", C.c_int32), ("ticks_den", C.c_int32), ("beat_cells", C.c_int32), ("vocab_size", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class FnNote(C.Structure):
+    _fields_ = [("t0", C.c_int32), ("t1", C.c_int32), ("pitch", C.c_int32), ("vel", C.c_int32)]
+
+
+class FnNoteSpan(C.Structure):
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("t_lo", C.c_int32), ("t_hi", C.c_int32)]
+
+
+class FnNoteParams(C.Structure):
+    _fields_ = [("on_lo", C.c_int32), ("off_lo", C.c_int32), ("n_pitch", C.c_int32), ("shift_lo", C.c_int32), ("n_shift", C.c_int32), ("eos", C.c_int32),
+                ("vocab_size", C.c_int32), ("vel_lo", C.c_int32), ("n_vel", C.c_int32), ("default_vel", C.c_int32), ("pad", C.c_int32),
+                ("add_eos", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fadernets.h
 SIGNATURES = {
     "fn_version": (C.c_int, []),
@@ -172,6 +188,8 @@ SIGNATURES = {
     "fn_constrain_advance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "fn_event_attributes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "fn_sweep_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp]),
+    "fn_notes_from_tokens": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "fn_tokens_from_notes": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),
     "fn_time_logsoftmax_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_latent_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,0 +1,280 @@
+// notes.hip - event tokens <-> timed notes (notes.py, midi.py): fn_notes_from_tokens publishes the notes that event_raster_kernel (attributes.hip)
+// keeps in registers, with velocity; fn_tokens_from_notes is the tokeniser.  include/fadernets.h has the definition.
+// Plain HIP: no inline assembly, no atomics, nothing between workgroups; one wavefront per row, every lane reaches every barrier.
+#include "common.h"
+
+namespace {
+
+struct NoteView {
+    int on_lo, off_lo, np, shift_lo, ns, eos, vocab, vel_lo, nv, vstep, def_vel, pad, add_eos;
+};
+
+__device__ __forceinline__ NoteView note_view(const FnNoteParams* __restrict__ p) {
+    NoteView c;
+    c.on_lo = p->on_lo, c.off_lo = p->off_lo, c.shift_lo = p->shift_lo, c.eos = p->eos, c.vocab = p->vocab_size, c.vel_lo = p->vel_lo;
+    c.np = min(max(p->n_pitch, 0), 128), c.ns = min(max(p->n_shift, 0), 4096), c.nv = min(max(p->n_vel, 0), 128);
+    c.vstep = c.nv > 0 ? (127 + c.nv - 1) / c.nv : 1;
+    c.def_vel = min(max(p->default_vel, 1), 127), c.pad = p->pad, c.add_eos = p->add_eos;
+    return c;
+}
+
+// offset of token e in the range of n tokens that starts at lo, or -1 (64-bit difference: lo is whatever the memory held)
+__device__ __forceinline__ int note_in_range(int e, int lo, int n) {
+    const long d = (long)e - (long)lo;
+    return (d >= 0 && d < n) ? (int)d : -1;
+}
+
+// Ascending bitonic sort of n 64-bit keys in LDS by one wavefront; n a power of two (1: nothing to do).  Pair t of a pass is (lo, lo + stride) with
+// bit `stride` of lo clear; the direction of a pair is bit `size` of lo.  A barrier in front of every pass and one behind the last.
+__device__ __forceinline__ void lds_bitonic_sort(unsigned long long* k, int n, int lane) {
+    for (int size = 2; size <= n; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int t = lane; t < (n >> 1); t += 64) {
+                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const unsigned long long a = k[lo], b = k[hi];
+                if ((a > b) == ((lo & size) == 0)) k[lo] = b, k[hi] = a;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ int pow2_at_least(int n) {
+    int p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+extern __shared__ __attribute__((aligned(16))) char note_smem[];
+
+constexpr unsigned long long NOTE_NO_KEY = ~0ull;
+
+// LDS: key[P] (t0 << 17 | pitch << 10 | index of the note-on token; NOTE_NO_KEY where the token opens no kept note), P = the power of two >= steps;
+// ev[steps] (tick << 9 | code, as event_raster_kernel has it); t1[steps] by note-on token; vel[steps], the velocity current at every token.
+// Phase 1 is event_raster_kernel's (the ballot for the eos, the shuffle scan of the clock) with a second, carry-forward scan for the velocity.
+// Phase 2: every lane walks all events (the same LDS word for all: a broadcast) and follows pitches l and l + 64; a note that closes goes to the slot
+// of its note-on token, which no other note has.  Phase 3: sort the keys; rank j of the order is note j.
+__global__ __launch_bounds__(64) void notes_from_tokens_kernel(const int32_t* __restrict__ tokens, int tok_ld, int steps, const FnNoteParams* __restrict__ params,
+                                                               FnNote* __restrict__ notes, int notes_ld, int32_t* __restrict__ n_notes,
+                                                               int32_t* __restrict__ t_end_out, int32_t* __restrict__ status) {
+    const int lane = threadIdx.x;
+    const long r = blockIdx.x;
+    const NoteView c = note_view(params);
+    const int P = pow2_at_least(steps);
+    unsigned long long* key = reinterpret_cast<unsigned long long*>(note_smem);
+    uint32_t* ev = reinterpret_cast<uint32_t*>(key + P);
+    uint32_t* t1s = ev + steps;
+    uint8_t* vel = reinterpret_cast<uint8_t*>(t1s + steps);
+    const int32_t* row = tokens + r * tok_ld;
+
+    // phase 1
+    int len = steps;
+    uint32_t carry = 0, vcarry = (uint32_t)c.def_vel;
+    bool found = false;
+    for (int base = 0; base < steps && !found; base += 64) {
+        const int i = base + lane;
+        const int e = i < steps ? row[i] : 0;
+        const unsigned long long m = __ballot(i < steps && c.eos >= 0 && e == c.eos);
+        if (m != 0ull) found = true, len = base + __ffsll((long long)m) - 1;
+        const bool live = i < len;                      // len <= steps
+        uint32_t amount = 0, code = 0, v = 0;
+        if (live && (c.vocab <= 0 || (e >= 0 && e < c.vocab))) {
+            int p;
+            if ((p = note_in_range(e, c.on_lo, c.np)) >= 0) code = 1u + (uint32_t)p;
+            else if ((p = note_in_range(e, c.off_lo, c.np)) >= 0) code = 129u + (uint32_t)p;
+            else if ((p = note_in_range(e, c.shift_lo, c.ns)) >= 0) amount = (uint32_t)p + 1u;
+            else if ((p = note_in_range(e, c.vel_lo, c.nv)) >= 0) v = (uint32_t)min(1 + p * c.vstep, 127);
+        }
+        uint32_t x = amount;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {              // the last non-zero value at or before the lane
+            const uint32_t y = __shfl_up(v, o, 64);
+            if (lane >= o && v == 0u) v = y;
+        }
+        if (v == 0u) v = vcarry;
+        if (live) ev[i] = ((carry + x) << 9) | code, vel[i] = (uint8_t)v;
+        carry += __shfl(x, 63, 64);
+        vcarry = __shfl(v, 63, 64);
+    }
+    const uint32_t t_end = carry;
+    for (int k = lane; k < P; k += 64) key[k] = NOTE_NO_KEY;
+    __syncthreads();
+
+    // phase 2
+    int open0 = -1, open1 = -1, at0 = 0, at1 = 0, mine = 0;
+    for (int i = 0; i < len; ++i) {
+        const uint32_t w = ev[i];
+        const int code = (int)(w & 511u);
+        if (code == 0) continue;
+        const bool is_on = code <= 128;
+        const int p = is_on ? code - 1 : code - 129;
+        if ((p & 63) != lane) continue;
+        const uint32_t t = w >> 9;
+        const int open = (p >> 6) ? open1 : open0, at = (p >> 6) ? at1 : at0;
+        if (open >= 0 && t > (uint32_t)open) {
+            key[at] = ((unsigned long long)(uint32_t)open << 17) | ((unsigned long long)p << 10) | (unsigned long long)at;
+            t1s[at] = t, ++mine;
+        }
+        const int now = is_on ? (int)t : -1;
+        if (p >> 6) open1 = now, at1 = i; else open0 = now, at0 = i;
+    }
+    if (open0 >= 0 && t_end > (uint32_t)open0) {
+        key[at0] = ((unsigned long long)(uint32_t)open0 << 17) | ((unsigned long long)lane << 10) | (unsigned long long)at0;
+        t1s[at0] = t_end, ++mine;
+    }
+    if (open1 >= 0 && t_end > (uint32_t)open1) {
+        key[at1] = ((unsigned long long)(uint32_t)open1 << 17) | ((unsigned long long)(lane + 64) << 10) | (unsigned long long)at1;
+        t1s[at1] = t_end, ++mine;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    const int n = mine;                                 // <= len
+
+    // phase 3
+    lds_bitonic_sort(key, P, lane);
+    FnNote* out = notes + r * notes_ld;
+    for (int j = lane; j < notes_ld; j += 64) {
+        FnNote q = {0, 0, 0, 0};
+        if (j < n) {
+            const unsigned long long k = key[j];
+            const int at = (int)(k & 1023ull);
+            q.t0 = (int32_t)(k >> 17), q.t1 = (int32_t)t1s[at], q.pitch = (int32_t)((k >> 10) & 127ull), q.vel = (int32_t)vel[at];
+        }
+        out[j] = q;
+    }
+    if (lane == 0) n_notes[r] = n, t_end_out[r] = (int32_t)t_end, status[r] = n == 0 ? FN_NOTES_EMPTY : n > notes_ld ? FN_NOTES_OVERFLOW : 0;
+}
+
+// LDS: key[1024] (tick << 18 | kind << 17 | pitch << 10 | k; kind 0 = OFF, 1 = ON; NOTE_NO_KEY for no event), bin[512] by k.
+// Phase 1: lane l takes the span's notes k = l, l + 64, ...: the kept ones leave their two events in slots 2k, 2k + 1.  Phase 2: the sort.
+// Phase 3, 64 events of the order at a time: the gap to the event before, the bin of the ON before (a carry-forward scan), the count of
+// tokens (a sum scan), then every lane writes its own event's tokens as far as they lie in front of `steps`.
+__global__ __launch_bounds__(64) void tokens_from_notes_kernel(const FnNote* __restrict__ notes, int n_total, const FnNoteSpan* __restrict__ spans,
+                                                               const FnNoteParams* __restrict__ params, int32_t* __restrict__ tokens, int tok_ld, int steps,
+                                                               int32_t* __restrict__ n_tokens, int32_t* __restrict__ n_kept, int32_t* __restrict__ status) {
+    __shared__ unsigned long long key[2 * FN_NOTES_MAX];
+    __shared__ uint8_t bin[FN_NOTES_MAX];
+    const int lane = threadIdx.x;
+    const long r = blockIdx.x;
+    const NoteView c = note_view(params);
+    const FnNoteSpan sp = spans[r];
+    const int count = min(max(sp.count, 0), FN_NOTES_MAX);
+    const long t_lo = sp.t_lo, t_hi = min(max((long)sp.t_hi, t_lo), t_lo + FN_NOTES_MAX_TICK);
+    const int P = pow2_at_least(2 * count);             // count 0: 1, nothing to sort
+
+    // phase 1
+    int kept = 0;
+    for (int k = lane; k < (P >> 1); k += 64) {
+        unsigned long long on = NOTE_NO_KEY, off = NOTE_NO_KEY;
+        const long at = (long)sp.first + k;
+        if (k < count && at >= 0 && at < n_total) {
+            const FnNote q = notes[at];
+            const long t1 = min((long)q.t1, t_hi);
+            if (q.pitch >= 0 && q.pitch < c.np && q.t0 >= t_lo && q.t0 < t_hi && t1 > q.t0) {
+                const unsigned long long low = ((unsigned long long)q.pitch << 10) | (unsigned long long)k;
+                on = ((unsigned long long)(q.t0 - t_lo) << 18) | (1ull << 17) | low;
+                off = ((unsigned long long)(t1 - t_lo) << 18) | low;
+                bin[k] = c.nv > 0 ? (uint8_t)min((min(max(q.vel, 1), 127) - 1) / c.vstep, c.nv - 1) : (uint8_t)0;
+                ++kept;
+            }
+        }
+        key[2 * k] = on, key[2 * k + 1] = off;          // 2k + 1 < P
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o, 64);
+
+    // phase 2
+    lds_bitonic_sort(key, P, lane);
+
+    // phase 3
+    const int n_ev = 2 * kept;                          // the events are the first n_ev keys of the order
+    int32_t* row = tokens + r * tok_ld;
+    const uint32_t ns = (uint32_t)c.ns;
+    uint32_t total = 0, prev_bin = 0;                   // prev_bin: 1 + the bin of the last ON so far; 0: none
+    for (int base = 0; base < n_ev; base += 64) {
+        const int j = base + lane;
+        const bool live = j < n_ev;
+        const unsigned long long k = live ? key[j] : 0ull;
+        const uint32_t tick = (uint32_t)(k >> 18), before = (live && j > 0) ? (uint32_t)(key[j - 1] >> 18) : 0u;
+        const bool is_on = live && ((k >> 17) & 1ull);
+        const int pitch = (int)((k >> 10) & 127ull);
+        const uint32_t g = tick - before;
+        const uint32_t full = ns ? g / ns : 0u, rest = ns ? g % ns : 0u;
+        const uint32_t b = (is_on && c.nv > 0) ? 1u + (uint32_t)bin[k & 1023ull] : 0u;
+        uint32_t last = b;                              // the last non-zero b at or before the lane ...
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(last, o, 64);
+            if (lane >= o && last == 0u) last = y;
+        }
+        if (last == 0u) last = prev_bin;
+        uint32_t seen = __shfl_up(last, 1, 64);         // ... and before it
+        if (lane == 0) seen = prev_bin;
+        prev_bin = __shfl(last, 63, 64);
+        const bool vel_tok = b != 0u && b != seen;
+        const uint32_t cnt = live ? full + (rest ? 1u : 0u) + (vel_tok ? 1u : 0u) + 1u : 0u;
+        uint32_t x = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        const uint32_t start = total + x - cnt;         // < 2^23: the gaps of a row sum to at most FN_NOTES_MAX_TICK
+        total += __shfl(x, 63, 64);
+        if (live) {
+            const uint32_t lim = (uint32_t)steps;
+            for (uint32_t q = start, stop = min(start + full, lim); q < stop; ++q) row[q] = c.shift_lo + c.ns - 1;
+            uint32_t q = start + full;
+            if (rest) {
+                if (q < lim) row[q] = c.shift_lo + (int)rest - 1;
+                ++q;
+            }
+            if (vel_tok) {
+                if (q < lim) row[q] = c.vel_lo + (int)b - 1;
+                ++q;
+            }
+            if (q < lim) row[q] = (is_on ? c.on_lo : c.off_lo) + pitch;
+        }
+    }
+    if (c.add_eos != 0 && c.eos >= 0) {
+        if (lane == 0 && total < (uint32_t)steps) row[total] = c.eos;
+        total += 1u;
+    }
+    for (uint32_t q = min(total, (uint32_t)steps) + lane; q < (uint32_t)steps; q += 64) row[q] = c.pad;
+    if (lane == 0) n_tokens[r] = (int32_t)total, n_kept[r] = kept, status[r] = total > (uint32_t)steps ? FN_NOTES_OVERFLOW : kept == 0 ? FN_NOTES_EMPTY : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fn_notes_from_tokens(const int32_t* tokens, int tok_ld, int rows, int steps, const FnNoteParams* params_dev, FnNote* notes, int notes_ld,
+                         int32_t* n_notes, int32_t* t_end, int32_t* status, void* stream) {
+    if (!tokens || !params_dev || !notes || !n_notes || !t_end || !status) return FN_E_NULL;
+    if (rows < 1 || steps < 1 || steps > FN_ATTR_MAX_STEPS || tok_ld < steps || notes_ld < 1) return FN_E_SHAPE;
+    size_t P = 1;
+    while (P < (size_t)steps) P <<= 1;
+    const size_t lds = 8u * P + 9u * (size_t)steps;          // <= 17 KB: below what a launch may ask for without an attribute
+    hipLaunchKernelGGL(notes_from_tokens_kernel, dim3((unsigned)rows), dim3(64), lds, (hipStream_t)stream, tokens, tok_ld, steps, params_dev, notes,
+                       notes_ld, n_notes, t_end, status);
+    FN_CHECK_LAUNCH();
+    return FN_OK;
+}
+
+int fn_tokens_from_notes(const FnNote* notes, int n_total, const FnNoteSpan* spans, int rows, const FnNoteParams* params_dev, int32_t* tokens,
+                         int tok_ld, int steps, int32_t* n_tokens, int32_t* n_kept, int32_t* status, void* stream) {
+    if (!spans || !params_dev || !tokens || !n_tokens || !n_kept || !status || (!notes && n_total > 0)) return FN_E_NULL;
+    if (rows < 1 || steps < 1 || steps > FN_ATTR_MAX_STEPS || tok_ld < steps || n_total < 0) return FN_E_SHAPE;
+    hipLaunchKernelGGL(tokens_from_notes_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, notes, n_total, spans, params_dev, tokens,
+                       tok_ld, steps, n_tokens, n_kept, status);
+    FN_CHECK_LAUNCH();
+    return FN_OK;
+}
+
+}  // extern "C"

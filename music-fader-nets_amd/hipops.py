@@ -700,6 +700,44 @@ class HipOps:
         _lib.check(self.lib.fn_event_attributes(_p(tokens), ld, rows, int(steps), _p(params), _p(n_cells), _p(status), _p(r_density), _p(n_density), _p(c_r),
                                                 _p(c_n), _p(rhythm), _p(notes), int(cells_ld), self.stream()), "fn_event_attributes")
 
+    def notes_from_tokens(self, tokens, steps, params, notes, n_notes, t_end, status):
+        """fn_notes_from_tokens: tokens int32 [rows][>= steps] (any row stride); params: the 64 bytes of FnNoteParams on the device; notes: contiguous
+        int32 [rows][notes_ld][4]; three [rows] outputs"""
+        _chk(tokens, torch.int32, "tokens"), _dense(params, torch.uint8, "params"), _dense(notes, torch.int32, "notes")
+        if tokens.dim() != 2 or (tokens.shape[1] > 1 and tokens.stride(1) != 1) or tokens.shape[1] < steps:
+            raise RuntimeError("notes_from_tokens: tokens 2-D with contiguous rows of at least %d, got shape %s strides %s" % (steps, tuple(tokens.shape), tokens.stride()))
+        rows = tokens.shape[0]
+        ld = tokens.stride(0) if rows > 1 else max(tokens.shape[1], tokens.stride(0))
+        if notes.dim() != 3 or notes.shape[0] != rows or notes.shape[2] != 4:
+            raise RuntimeError("notes_from_tokens: notes (%d, notes_ld, 4), got %s" % (rows, tuple(notes.shape)))
+        for t, nm in ((n_notes, "n_notes"), (t_end, "t_end"), (status, "status")):
+            _dense(t, torch.int32, nm)
+            if t is None or t.numel() != rows:
+                raise RuntimeError("notes_from_tokens: %s for %d rows" % (nm, rows))
+        if params.numel() != C.sizeof(_lib.FnNoteParams):
+            raise RuntimeError("notes_from_tokens: params of %d bytes" % C.sizeof(_lib.FnNoteParams))
+        _lib.check(self.lib.fn_notes_from_tokens(_p(tokens), ld, rows, int(steps), _p(params), _p(notes), notes.shape[1], _p(n_notes), _p(t_end), _p(status),
+                                                 self.stream()), "fn_notes_from_tokens")
+
+    def tokens_from_notes(self, notes, spans, params, tokens, steps, n_tokens, n_kept, status):
+        """fn_tokens_from_notes: notes contiguous int32 [n_total][4], spans contiguous int32 [rows][4]; params: the 64 bytes of FnNoteParams on the
+        device; tokens int32 [rows][>= steps] (any row stride) and three [rows] outputs are written"""
+        _dense(notes, torch.int32, "notes"), _dense(spans, torch.int32, "spans"), _dense(params, torch.uint8, "params"), _chk(tokens, torch.int32, "tokens")
+        if notes.dim() != 2 or notes.shape[1] != 4 or spans.dim() != 2 or spans.shape[1] != 4:
+            raise RuntimeError("tokens_from_notes: notes (n_total, 4) and spans (rows, 4), got %s and %s" % (tuple(notes.shape), tuple(spans.shape)))
+        rows = spans.shape[0]
+        if tokens.dim() != 2 or tokens.shape[0] != rows or (tokens.shape[1] > 1 and tokens.stride(1) != 1) or tokens.shape[1] < steps:
+            raise RuntimeError("tokens_from_notes: tokens (%d, >= %d) with contiguous rows, got shape %s strides %s" % (rows, steps, tuple(tokens.shape), tokens.stride()))
+        ld = tokens.stride(0) if rows > 1 else max(tokens.shape[1], tokens.stride(0))
+        for t, nm in ((n_tokens, "n_tokens"), (n_kept, "n_kept"), (status, "status")):
+            _dense(t, torch.int32, nm)
+            if t is None or t.numel() != rows:
+                raise RuntimeError("tokens_from_notes: %s for %d rows" % (nm, rows))
+        if params.numel() != C.sizeof(_lib.FnNoteParams):
+            raise RuntimeError("tokens_from_notes: params of %d bytes" % C.sizeof(_lib.FnNoteParams))
+        _lib.check(self.lib.fn_tokens_from_notes(_p(notes) if notes.shape[0] else None, notes.shape[0], _p(spans), rows, _p(params), _p(tokens), ld, int(steps),
+                                                 _p(n_tokens), _p(n_kept), _p(status), self.stream()), "fn_tokens_from_notes")
+
     def sweep_scores(self, r, n, status, values, which, r_std, n_std, scores, n_used):
         """fn_sweep_scores: r, n fp32 and status int32 contiguous [S][Vn]; values fp64 [Vn]; scores fp64 [4]; n_used int32 [1]"""
         _dense(r, name="r"), _dense(n, name="n"), _dense(status, torch.int32, "status"), _dense(values, torch.float64, "values")
