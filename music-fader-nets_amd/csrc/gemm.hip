@@ -943,10 +943,8 @@ __global__ __launch_bounds__(X6W_NT) void gemm_tn_x6v_kernel(int M, int N, int K
 // step + a fixed 32-bit lane offset (no vector address arithmetic in the loop).  Requires M, N multiples of 128, K a multiple of 16,
 // 16-byte aligned operands with ld % 4 == 0 and < 4 GB spans (fn_gemm_f32 falls back to the staged kernel otherwise).
 // ---------------------------------------------------------------------------------------------------------
-FN_DEVINL void fn_gld4_s(f32x4& dst, unsigned voff, const float* sbase) {
-    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
-}
-
+// The K loop below is the ring of ring_core.h written out (its drain has no scheduling barrier behind the multiplies): on fn_ring_run the
+// 128-register instance <1, 4> spilled (profiles/decode_cells_refactor.txt), so this kernel keeps its own copy.
 template <int PF, int WGS>
 __global__ __launch_bounds__(NT, WGS) void gemm_nt_direct_kernel(int M, int N, int K, float alpha, const float* __restrict__ A, long lda,
                                                             const float* __restrict__ B, long ldb, float beta, float* __restrict__ C, long ldc,

@@ -591,7 +591,8 @@ __global__ __launch_bounds__(NT, 2) void gru_cell_kernel(const CellArgs a) {
     using SB = Stage<GC_BN, GC_BK, true, NT>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int nut = a.H >> 5;
-    // 4 x 8 super-tiles (row panels x unit tiles) in consecutive virtual ids = on one XCD
+    // 4 x 8 super-tiles (row panels x unit tiles) in consecutive virtual ids = on one XCD (fn_supertile written out: through the helper the kernel
+    // came out two instructions shorter and one of its timings 0.02 us above the bound - profiles/decode_cells_refactor.txt)
     const int v = fn_xcd_remap(blockIdx.x, gridDim.x);
     const int ntm = (a.B + BM - 1) / BM;
     int tm, tu;
@@ -687,6 +688,172 @@ __global__ __launch_bounds__(NT, 2) void gru_cell_kernel(const CellArgs a) {
         }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Shared pieces of the large-batch decode kernels below (the K-loop ring itself is ring_core.h).
+//
+// Weight slice in LDS: 48 weight rows x K floats laid out once as MFMA fragments [k step][tile of 16 rows][lane] (16-byte LDS reads).
+// Item (row r of 48, k quad c of K / 4) -> step c >> 2, tile r >> 4, lane group c & 3, slot (r & 15) rotated by the k quad: 16 consecutive
+// quads of a row hit 16 bank groups.
+FN_DEVINL int wfrag_slot(int r, int c) { return (c >> 2) * 192 + (r >> 4) * 64 + (c & 3) * 16 + (((r & 15) + 4 * (c & 3) + (c >> 2)) & 15); }
+// the three fragments (row tiles 0, 1, 2) of k step s for lane (li = l & 15, lg = l >> 4)
+FN_DEVINL void wfrag_read(const f32x4* wl, int s, int lane, f32x4 (&b)[3]) {
+    const int li = lane & 15, lg = lane >> 4;
+    const int sl = lg * 16 + ((li + 4 * lg + s) & 15);
+    b[0] = wl[s * 192 + sl];
+    b[1] = wl[s * 192 + 64 + sl];
+    b[2] = wl[s * 192 + 128 + sl];
+}
+// Fill by NTH threads, rowp(r) = first element of weight row r of the 48; consecutive threads read one row.
+// Eight independent 16-byte loads per thread in flight, then their eight LDS writes (a load -> write pair per iteration serialised 24
+// memory latencies: 7.4 us of a 19 us launch); (row, quad) advance by NTH items without a division
+template <int NTH, class RowPtr>
+FN_DEVINL void wfrag_fill(f32x4* wl, int K, RowPtr&& rowp) {
+    const int kq = K >> 2;
+    const int total = 48 * kq, dq = NTH / kq, dr = NTH % kq;
+    int fr = threadIdx.x / kq, fc = threadIdx.x % kq;
+    for (int base = threadIdx.x; base < total; base += NTH * 8) {
+        f32x4 v[8];
+        int rr[8], cc[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            rr[u] = fr;
+            cc[u] = fc;
+            v[u] = *reinterpret_cast<const f32x4*>(rowp(min(fr, 47)) + 4 * fc);
+            fc += dr;
+            fr += dq;
+            if (fc >= kq) { fc -= kq; ++fr; }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (rr[u] < 48) wl[wfrag_slot(rr[u], cc[u])] = v[u];
+    }
+}
+
+// Gate epilogue of the LDS-free cell and of the cells with an LDS-resident weight slice, on (row, 4 units) items: the accumulator tiles of
+// row tile m go through a wave-private LDS tile tw (D layout in, lane (row = l >> 2, units 4 (l & 3) ..) out), so every other operand - old
+// state, token row, row constant - is ONE 16-byte load per gate and item and the new state one 16-byte store (the element-per-lane form
+// issued 7 scalar loads per (row, unit), 112 per lane).  Absent sources are not loaded (HAS_TAB / HAS_RB).  Request and finish are apart:
+// every kernel asks for the operands at its own point (plain loads: older than every ring load issued behind them, so the counted waits
+// cover them).
+template <int RT>
+struct CellEpi { f32x4 bi[3], bh[3], hv[RT], tv[RT][3], rv[RT][3]; };    // biases; old state, token row, row constant of the item of row tile m
+template <int RT>
+FN_DEVINL void cell_epilogue_request_bias(const CellArgs& a, int u0, int lane, CellEpi<RT>& p) {
+    const int eu = u0 + 4 * (lane & 3);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        p.bh[q] = *reinterpret_cast<const f32x4*>(a.b_hh + q * a.H + eu);
+        p.bi[q] = a.b_ih ? *reinterpret_cast<const f32x4*>(a.b_ih + q * a.H + eu) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+}
+// per row tile: old state (HV), token row (TAB) and / or row constant (RB); tokf(m, rc): the token of the lane's row rc of tile m
+template <int RT, bool HV, bool TAB, bool RB, class TokF>
+FN_DEVINL void cell_epilogue_request_rows(const CellArgs& a, int m0, int u0, int lane, TokF&& tokf, CellEpi<RT>& p) {
+    const int er = lane >> 2, eu = u0 + 4 * (lane & 3);
+    const long H3 = 3L * a.H;
+#pragma unroll
+    for (int m = 0; m < RT; ++m) {
+        const int rc = min(m0 + 16 * m + er, a.B - 1);
+        if (HV) p.hv[m] = *reinterpret_cast<const f32x4*>(a.h_prev + (long)rc * a.ldh + eu);
+        if (TAB) {
+            const int tok = tokf(m, rc);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) p.tv[m][q] = *reinterpret_cast<const f32x4*>(a.gx_table + (long)tok * H3 + q * a.H + eu);
+        }
+        if (RB) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) p.rv[m][q] = *reinterpret_cast<const f32x4*>(a.gx_rowbias + (long)rc * H3 + q * a.H + eu);
+        }
+    }
+}
+template <int RT, bool HAS_TAB, bool HAS_RB>
+FN_DEVINL void cell_epilogue_finish(const CellArgs& a, int m0, int u0, int lane, float* tw, const f32x4 (&arz)[RT][2], const f32x4 (&anx)[RT],
+                                    const f32x4 (&anh)[RT], const CellEpi<RT>& p) {
+    const int li = lane & 15, lg = lane >> 4;
+    const int er = lane >> 2, eu = u0 + 4 * (lane & 3);
+#pragma unroll
+    for (int m = 0; m < RT; ++m) {
+        // D layout: lane (li, lg) holds rows 4 lg + i, column li
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            tw[0 * 320 + (4 * lg + i) * 20 + li] = arz[m][0][i];
+            tw[1 * 320 + (4 * lg + i) * 20 + li] = arz[m][1][i];
+            tw[2 * 320 + (4 * lg + i) * 20 + li] = anx[m][i];
+            tw[3 * 320 + (4 * lg + i) * 20 + li] = anh[m][i];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const f32x4 g_r = *reinterpret_cast<const f32x4*>(tw + 0 * 320 + er * 20 + 4 * (lane & 3));
+        const f32x4 g_z = *reinterpret_cast<const f32x4*>(tw + 1 * 320 + er * 20 + 4 * (lane & 3));
+        const f32x4 g_nx = *reinterpret_cast<const f32x4*>(tw + 2 * 320 + er * 20 + 4 * (lane & 3));
+        const f32x4 g_nh = *reinterpret_cast<const f32x4*>(tw + 3 * 320 + er * 20 + 4 * (lane & 3));
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        f32x4 o;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float gi[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                float e = p.bi[q][c];
+                if (HAS_TAB) e += p.tv[m][q][c];
+                if (HAS_RB) e += p.rv[m][q][c];
+                gi[q] = e;
+            }
+            const float r = fn_sigmoid((gi[0] + p.bh[0][c]) + g_r[c]);
+            const float z = fn_sigmoid((gi[1] + p.bh[1][c]) + g_z[c]);
+            const float n = fn_tanh((gi[2] + g_nx[c]) + r * (g_nh[c] + p.bh[2][c]));
+            o[c] = (1.0f - z) * n + z * p.hv[m][c];
+        }
+        const int row = m0 + 16 * m + er;
+        if (row < a.B) *reinterpret_cast<f32x4*>(a.h_out + (long)row * a.ldo + eu) = o;
+    }
+}
+
+// Packed-argmax epilogue of the output kernels: lane (li, lg) holds the logits of rows m0 + 4 lg + i, columns n0 + 16 q + li - the best
+// packed word of its three columns per row, a 16-lane butterfly over li, one 64-bit atomic max per row and wave.
+FN_DEVINL unsigned long long fn_pack_best(float x, int v, int V) {
+    const unsigned b = __float_as_uint(x);
+    const unsigned key = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+    return ((unsigned long long)key << 32) | (unsigned)(V - 1 - v);
+}
+FN_DEVINL void out_argmax_bias(const float* __restrict__ bias, int n0, int lane, int V, float (&bv)[3]) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) bv[q] = bias[min(n0 + 16 * q + (lane & 15), V - 1)];
+}
+FN_DEVINL void out_argmax_epilogue(const f32x4 (&acc)[3], const float (&bv)[3], int m0, int n0, int lane, int B, int V,
+                                   unsigned long long* __restrict__ best) {
+    const int li = lane & 15, lg = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned long long w = 0ull;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int col = n0 + 16 * q + li;
+            const unsigned long long c = col < V ? fn_pack_best(acc[q][i] + bv[q], col, V) : 0ull;
+            w = c > w ? c : w;
+        }
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) {
+            const unsigned lo = __shfl_xor((unsigned)(w & 0xffffffffull), d, 64), hi = __shfl_xor((unsigned)(w >> 32), d, 64);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            w = o > w ? o : w;
+        }
+        const int row = m0 + 4 * lg + i;
+        if (li == 0 && row < B) atomicMax(best + row, w);
+    }
+}
+
+// the four HAS_TAB / HAS_RB instantiations of a cell launcher: f(std::bool_constant<HAS_TAB>, std::bool_constant<HAS_RB>)
+template <class F>
+int cell_tab_rb_switch(const CellArgs& a, F&& f) {
+    using T_ = std::integral_constant<bool, true>;
+    using F_ = std::integral_constant<bool, false>;
+    const bool tab = a.gx_table != nullptr, rb = a.gx_rowbias != nullptr;
+    if (tab && rb) return f(T_{}, T_{});
+    if (tab) return f(T_{}, F_{});
+    if (rb) return f(F_{}, T_{});
+    return f(F_{}, F_{});
+}
+
 // The same cell WITHOUT LDS (the loop of gemm_nt_direct_kernel, gemm.hip): both operands are K-contiguous rows, so lane (i = l & 15, g = l >> 4)
 // reads the float4 [row i of a 16-row tile][k0 + 4g .. 4g + 3] of its RT state-row tiles and of the three gate rows of its 16 hidden units
 // straight from memory; MFMA j of a 16-k step takes element j of every lane (a permutation of the step's k values, the same for A and B).
@@ -695,23 +862,11 @@ __global__ __launch_bounds__(NT, 2) void gru_cell_kernel(const CellArgs a) {
 // One wave = 16 RT rows x 16 units x {r, z, n}: r and z accumulate the x part and the h part in ONE tile, the n gate keeps them apart
 // (tanh(gi_n + r * gh_n)); a workgroup = 2 x 2 waves = 32 RT rows x 32 units.  Loads use a scalar base (64 bytes per step) + a fixed
 // 32-bit lane offset.  Needs K1, H multiples of 16, 16-byte aligned operands, row strides multiples of 4 floats, spans below 4 GB.
-FN_DEVINL void fn_gld4_sb(f32x4& dst, unsigned voff, const float* sbase) {
-    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
-}
-
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
 __global__ __launch_bounds__(NT, RT >= 4 ? 1 : 2) void gru_cell_direct_kernel(const CellArgs a) {
-    const int nut = a.H >> 5, ntm = (a.B + 32 * RT - 1) / (32 * RT);
-    const int v = fn_xcd_remap(blockIdx.x, gridDim.x);
+    const int nut = a.H >> 5;
     int tm, tu;
-    if ((ntm % 4) == 0 && (nut % 8) == 0) {          // 4 x 8 super-tiles (row panels x unit tiles) in consecutive virtual ids = on one XCD
-        const int sb = v >> 5, l = v & 31, sbu = nut >> 3;
-        tm = (sb / sbu) * 4 + (l >> 3);
-        tu = (sb % sbu) * 8 + (l & 7);
-    } else {
-        tm = v / nut;
-        tu = v % nut;
-    }
+    fn_supertile(blockIdx.x, gridDim.x, a.B, 32 * RT, nut, tm, tu);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m0 = tm * 32 * RT + (wave >> 1) * 16 * RT, u0 = tu * 32 + (wave & 1) * 16;
     const int li = lane & 15, lg = lane >> 4;
@@ -730,13 +885,13 @@ __global__ __launch_bounds__(NT, RT >= 4 ? 1 : 2) void gru_cell_direct_kernel(co
         const float* pb = W;
         auto load = [&](int set) {
 #pragma unroll
-            for (int m = 0; m < RT; ++m) fn_gld4_sb(fa[set][m], oa[m], pa);
+            for (int m = 0; m < RT; ++m) fn_gld4_s(fa[set][m], oa[m], pa);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) fn_gld4_sb(fb[set][q], ob[q], pb);
+            for (int q = 0; q < 3; ++q) fn_gld4_s(fb[set][q], ob[q], pb);
             pa += 16;
             pb += 16;
         };
-        auto mma = [&](int u) {
+        auto mma = [&](int u, int) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -746,51 +901,16 @@ __global__ __launch_bounds__(NT, RT >= 4 ? 1 : 2) void gru_cell_direct_kernel(co
                     accn[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][m][j], fb[u][2][j], accn[m], 0, 0, 0);
                 }
         };
-        constexpr int NL = RT + 3;
-        const int nmain = nks / PF * PF;
-        if (nmain > 0) {
+        auto keep = [&](int set) {
 #pragma unroll
-            for (int s = 0; s < PF; ++s) load(s);
-            for (int base = 0; base + PF < nmain; base += PF) {
+            for (int m = 0; m < RT; ++m) fn_keep(fa[set][m]);
 #pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    fn_wait_vm<NL * (PF - 1)>();
-                    mma(u);
-                    load(u);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                if (u == 0) fn_wait_vm<NL * (PF - 1)>();
-                else if (u == 1 && PF > 1) fn_wait_vm<(PF > 1 ? NL * (PF - 2) : 0)>();
-                else if (u == 2 && PF > 2) fn_wait_vm<(PF > 2 ? NL * (PF - 3) : 0)>();
-                else fn_wait_vm<0>();
-                mma(u);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int s = 0; s < PF; ++s) {
-#pragma unroll
-                for (int m = 0; m < RT; ++m) fn_keep(fa[s][m]);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) fn_keep(fb[s][q]);
-            }
-        }
-        for (int ks = nmain; ks < nks; ++ks) {
-            load(0);
-            fn_wait_vm<0>();
-            mma(0);
-#pragma unroll
-            for (int m = 0; m < RT; ++m) fn_keep(fa[0][m]);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) fn_keep(fb[0][q]);
-        }
+            for (int q = 0; q < 3; ++q) fn_keep(fb[set][q]);
+        };
+        fn_ring_run<PF, RT + 3, false>(nks, load, mma, keep);
     };
-    // Epilogue on (row, 4 units) items: the accumulator tiles of row tile m go through a wave-private LDS tile (D layout in, lane
-    // (row = l >> 2, units 4 (l & 3) ..) out), so every other operand - old state, token row, row constant - is ONE 16-byte load per
-    // gate and item and the new state one 16-byte store (the element-per-lane form issued 7 scalar loads per (row, unit), 112 per lane).
-    // All of them are requested HERE, in front of the K loops (plain loads: older than every ring load, so the counted waits cover them);
+    // The gate epilogue of cell_epilogue_request_* / cell_epilogue_finish written out (on the shared functions the instance <4, 2, true, true>
+    // took 256 registers for 254 - profiles/decode_cells_refactor.txt).  All of its operands are requested HERE, in front of the K loops (plain loads: older than every ring load, so the counted waits cover them);
     // absent sources are not loaded (HAS_TAB / HAS_RB).
     // (128-row form with both a token row and a row constant: the row constants would push the ring into AGPR copies - an asm-load
     // destination must never be moved before its counted wait - so they are requested behind the K loops there)
@@ -868,16 +988,9 @@ __global__ __launch_bounds__(NT, RT >= 4 ? 1 : 2) void gru_cell_direct_kernel(co
 
 // ---------------------------------------------------------------------------------------------------------------
 // Output layer of the large-batch decode with the argmax in its epilogue (fn_out_argmax_f32): the same LDS-free loop; a wave owns
-// 16 rows x 48 vocabulary columns (weight rows past V are the last row again, masked below), a workgroup 2 x 2 waves = 32 rows x 96
-// columns - 256 workgroups at 2048 rows.  Lane (li, lg) ends up with the logits of rows 4 lg + i, columns n0 + 16 q + li: the best
-// packed word of its three columns per row, a 16-lane butterfly over li, one 64-bit atomic max per row and wave.  The staged GEMM
-// took 16 us for this 0.7-GFLOP product (16 barrier-separated tiles) and the separate argmax kernel 5 us per token.
-FN_DEVINL unsigned long long fn_pack_best(float x, int v, int V) {
-    const unsigned b = __float_as_uint(x);
-    const unsigned key = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-    return ((unsigned long long)key << 32) | (unsigned)(V - 1 - v);
-}
-
+// 16 rows x 48 vocabulary columns (weight rows past V are the last row again, masked in the epilogue), a workgroup 2 x 2 waves = 32 rows x 96
+// columns - 256 workgroups at 2048 rows.  The staged GEMM took 16 us for this 0.7-GFLOP product (16 barrier-separated tiles) and the
+// separate argmax kernel 5 us per token.
 template <int PF>
 __global__ __launch_bounds__(NT, 2) void out_argmax_direct_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ W, long ldw,
                                                                  const float* __restrict__ bias, int B, int V, int K,
@@ -897,13 +1010,13 @@ __global__ __launch_bounds__(NT, 2) void out_argmax_direct_kernel(const float* _
     const float* pa = h;
     const float* pb = W;
     auto load = [&](int set) {
-        fn_gld4_sb(fa[set], oa, pa);
+        fn_gld4_s(fa[set], oa, pa);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) fn_gld4_sb(fb[set][q], ob[q], pb);
+        for (int q = 0; q < 3; ++q) fn_gld4_s(fb[set][q], ob[q], pb);
         pa += 16;
         pb += 16;
     };
-    auto mma = [&](int u) {
+    auto mma = [&](int u, int) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -914,292 +1027,56 @@ __global__ __launch_bounds__(NT, 2) void out_argmax_direct_kernel(const float* _
 #pragma unroll
         for (int q = 0; q < 3; ++q) fn_keep(fb[set][q]);
     };
-    const int nks = K >> 4, nmain = nks / PF * PF;
-    if (nmain > 0) {
-#pragma unroll
-        for (int s = 0; s < PF; ++s) load(s);
-        for (int base = 0; base + PF < nmain; base += PF) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                fn_wait_vm<4 * (PF - 1)>();
-                mma(u);
-                load(u);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            if (u == 0) fn_wait_vm<4 * (PF - 1)>();
-            else if (u == 1 && PF > 1) fn_wait_vm<(PF > 1 ? 4 * (PF - 2) : 0)>();
-            else if (u == 2 && PF > 2) fn_wait_vm<(PF > 2 ? 4 * (PF - 3) : 0)>();
-            else fn_wait_vm<0>();
-            mma(u);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int s = 0; s < PF; ++s) keep(s);
-    }
-    for (int ks = nmain; ks < nks; ++ks) {
-        load(0);
-        fn_wait_vm<0>();
-        mma(0);
-        keep(0);
-    }
+    fn_ring_run<PF, 4, false>(K >> 4, load, mma, keep);
     float bv[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) bv[q] = bias[min(n0 + 16 * q + li, V - 1)];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned long long w = 0ull;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int col = n0 + 16 * q + li;
-            const unsigned long long c = col < V ? fn_pack_best(acc[q][i] + bv[q], col, V) : 0ull;
-            w = c > w ? c : w;
-        }
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-            const unsigned lo = __shfl_xor((unsigned)(w & 0xffffffffull), d, 64), hi = __shfl_xor((unsigned)(w >> 32), d, 64);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            w = o > w ? o : w;
-        }
-        const int row = m0 + 4 * lg + i;
-        if (li == 0 && row < B) atomicMax(best + row, w);
-    }
+    out_argmax_bias(bias, n0, lane, V, bv);
+    out_argmax_epilogue(acc, bv, m0, n0, lane, B, V, best);
 }
 
 // The same product with the WEIGHT operand resident in LDS: the LDS-free loops of this file all run at about 8 TB/s of operand loads
 // (16 rows x 64 bytes per instruction), and at 16 x 48 outputs per wave that is 134 MB per launch - 17.6 us, no faster than the
 // staged GEMM.  Here a workgroup owns 64 rows x 48 columns: its 48 weight rows (48 x K floats, 96 KB at K = 512) are laid out once as
-// MFMA fragments [k step][column tile][lane] (16-byte LDS reads, conflict-free), only the state rows are read from memory in the loop
-// (one 16-byte load per lane and 12 MFMAs, PF steps in flight).
-template <int PF>
-__global__ __launch_bounds__(NT) void out_argmax_lds_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ W, long ldw,
-                                                            const float* __restrict__ bias, int B, int V, int K,
-                                                            unsigned long long* __restrict__ best) {
-    extern __shared__ __attribute__((aligned(16))) float dsm[];
+// MFMA fragments (wfrag_fill), only the state rows are read from memory in the loop (one 16-byte load per lane and 12 MFMAs, PF steps
+// in flight).  KH = 2 (out_argmax_lds8_kernel, eight waves): waves 4-7 take the second half of K for the row tiles of waves 0-3 and hand
+// their accumulators over through LDS, behind the weight fragments.
+template <int PF, int KH>
+FN_DEVINL void out_argmax_lds_body(float* dsm, const float* __restrict__ h, long ldh, const float* __restrict__ W, long ldw,
+                                   const float* __restrict__ bias, int B, int V, int K, unsigned long long* __restrict__ best) {
     f32x4* wl = reinterpret_cast<f32x4*>(dsm);       // [K / 16][3][64]
     const int ncb = (V + 47) / 48;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = KH > 1 ? (threadIdx.x >> 6) & 3 : threadIdx.x >> 6;
+    const int kh = KH > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;
     const int m0 = (blockIdx.x / ncb) * 64 + wave * 16, n0 = (blockIdx.x % ncb) * 48;
     const int li = lane & 15, lg = lane >> 4;
-    const int nks = K >> 4;
-    const unsigned oa = (unsigned)(((long)min(m0 + li, B - 1) * ldh + 4 * lg) * 4);
-    f32x4 fa[PF];
-    const float* pa = h;
-    auto load = [&](int set) {
-        fn_gld4_sb(fa[set], oa, pa);
-        pa += 16;
-    };
-    const int npro = min(PF, nks);
-#pragma unroll
-    for (int s = 0; s < PF; ++s)
-        if (s < npro) load(s);
-    // weight fragments: item (row r of 48, k quad c of K / 4) -> step c >> 2, tile r >> 4, lane group c & 3, slot (r & 15) rotated; consecutive threads read one row
-    const int kq = K >> 2;
-    // eight independent 16-byte loads per thread in flight, then their eight LDS writes (a load -> write pair per iteration serialised 24
-    // memory latencies: 7.4 us of a 19 us launch); (row, quad) advance by NT items without a division
-    const int total = 48 * kq, dq = NT / kq, dr = NT % kq;
-    int fr = threadIdx.x / kq, fc = threadIdx.x % kq;
-    for (int base = threadIdx.x; base < total; base += NT * 8) {
-        f32x4 v[8];
-        int rr[8], cc[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            rr[u] = fr;
-            cc[u] = fc;
-            v[u] = *reinterpret_cast<const f32x4*>(W + (long)min(n0 + min(fr, 47), V - 1) * ldw + 4 * fc);
-            fc += dr;
-            fr += dq;
-            if (fc >= kq) { fc -= kq; ++fr; }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int r = rr[u], c = cc[u];
-            if (r < 48) wl[(c >> 2) * 192 + (r >> 4) * 64 + (c & 3) * 16 + (((r & 15) + 4 * (c & 3) + (c >> 2)) & 15)] = v[u];     // slot rotated by the k quad: 16 consecutive quads of a row hit 16 bank groups
-        }
-    }
-    __syncthreads();
-    f32x4 acc[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    auto mma = [&](int u, int s) {
-        const int sl = lg * 16 + ((li + 4 * lg + s) & 15);
-        const f32x4 b0 = wl[s * 192 + sl], b1 = wl[s * 192 + 64 + sl], b2 = wl[s * 192 + 128 + sl];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b0[j], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b1[j], acc[1], 0, 0, 0);
-            acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b2[j], acc[2], 0, 0, 0);
-        }
-    };
-    // the plain loads of the fill are older than nothing of the ring that is still needed: every counted wait below also covers them
-    const int nmain = nks / PF * PF;
-    int s = 0;
-    if (nmain > 0) {
-        for (; s + PF < nmain; s += PF) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                fn_wait_vm<PF - 1>();
-                mma(u, s + u);
-                load(u);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // the ring holds steps s .. s + PF - 1
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            if (u == 0) fn_wait_vm<PF - 1>();
-            else if (u == 1 && PF > 1) fn_wait_vm<(PF > 1 ? PF - 2 : 0)>();
-            else if (u == 2 && PF > 2) fn_wait_vm<(PF > 2 ? PF - 3 : 0)>();
-            else fn_wait_vm<0>();
-            mma(u, s + u);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        s += PF;
-    } else {
-        fn_wait_vm<0>();                             // fewer steps than ring slots (K < 16 PF)
-#pragma unroll
-        for (int u = 0; u < PF; ++u)
-            if (u < npro) mma(u, u);
-        s = npro;
-    }
-#pragma unroll
-    for (int u = 0; u < PF; ++u) fn_keep(fa[u]);
-    for (; s < nks; ++s) {                           // < PF leftover steps, unpipelined
-        load(0);
-        fn_wait_vm<0>();
-        mma(0, s);
-        fn_keep(fa[0]);
-    }
-    float bv[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) bv[q] = bias[min(n0 + 16 * q + li, V - 1)];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned long long w = 0ull;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int col = n0 + 16 * q + li;
-            const unsigned long long c = col < V ? fn_pack_best(acc[q][i] + bv[q], col, V) : 0ull;
-            w = c > w ? c : w;
-        }
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-            const unsigned lo = __shfl_xor((unsigned)(w & 0xffffffffull), d, 64), hi = __shfl_xor((unsigned)(w >> 32), d, 64);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            w = o > w ? o : w;
-        }
-        const int row = m0 + 4 * lg + i;
-        if (li == 0 && row < B) atomicMax(best + row, w);
-    }
-}
-
-template <int PF>
-__global__ __launch_bounds__(2 * NT) void out_argmax_lds8_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ W, long ldw,
-                                                            const float* __restrict__ bias, int B, int V, int K,
-                                                            unsigned long long* __restrict__ best) {
-    extern __shared__ __attribute__((aligned(16))) float dsm[];
-    f32x4* wl = reinterpret_cast<f32x4*>(dsm);       // [K / 16][3][64]
-    const int ncb = (V + 47) / 48;
-    // eight waves: waves 4-7 take the second half of K for the row tiles of waves 0-3 and hand their accumulators over through LDS
-    const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & 3, kh = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-    const int m0 = (blockIdx.x / ncb) * 64 + wave * 16, n0 = (blockIdx.x % ncb) * 48;
-    const int li = lane & 15, lg = lane >> 4;
-    const int nks_all = K >> 4, s_first = kh ? nks_all / 2 : 0, nks = kh ? nks_all - nks_all / 2 : nks_all / 2;
+    const int nks_all = K >> 4, s_first = kh ? nks_all / 2 : 0, nks = KH > 1 ? (kh ? nks_all - nks_all / 2 : nks_all / 2) : nks_all;
     const unsigned oa = (unsigned)(((long)min(m0 + li, B - 1) * ldh + 4 * lg) * 4);
     f32x4 fa[PF];
     const float* pa = h + 16 * s_first;
     auto load = [&](int set) {
-        fn_gld4_sb(fa[set], oa, pa);
+        fn_gld4_s(fa[set], oa, pa);
         pa += 16;
     };
-    float bv[3];                                     // requested in front of everything: the epilogue then waits for nothing
-#pragma unroll
-    for (int q = 0; q < 3; ++q) bv[q] = bias[min(n0 + 16 * q + li, V - 1)];
-    const int npro = min(PF, nks);
-#pragma unroll
-    for (int s = 0; s < PF; ++s)
-        if (s < npro) load(s);
-    // weight fragments: item (row r of 48, k quad c of K / 4) -> step c >> 2, tile r >> 4, lane group c & 3, slot (r & 15) rotated; consecutive threads read one row
-    const int kq = K >> 2;
-    // eight independent 16-byte loads per thread in flight, then their eight LDS writes (a load -> write pair per iteration serialised 24
-    // memory latencies: 7.4 us of a 19 us launch); (row, quad) advance by NT items without a division
-    const int total = 48 * kq, dq = (2 * NT) / kq, dr = (2 * NT) % kq;
-    int fr = threadIdx.x / kq, fc = threadIdx.x % kq;
-    for (int base = threadIdx.x; base < total; base += 2 * NT * 8) {
-        f32x4 v[8];
-        int rr[8], cc[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            rr[u] = fr;
-            cc[u] = fc;
-            v[u] = *reinterpret_cast<const f32x4*>(W + (long)min(n0 + min(fr, 47), V - 1) * ldw + 4 * fc);
-            fc += dr;
-            fr += dq;
-            if (fc >= kq) { fc -= kq; ++fr; }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int r = rr[u], c = cc[u];
-            if (r < 48) wl[(c >> 2) * 192 + (r >> 4) * 64 + (c & 3) * 16 + (((r & 15) + 4 * (c & 3) + (c >> 2)) & 15)] = v[u];     // slot rotated by the k quad: 16 consecutive quads of a row hit 16 bank groups
-        }
-    }
+    float bv[3];
+    if (KH > 1) out_argmax_bias(bias, n0, lane, V, bv);       // requested in front of everything: the epilogue then waits for nothing
+    fn_ring_request<PF>(nks, load);
+    wfrag_fill<KH * NT>(wl, K, [&](int r) { return W + (long)min(n0 + r, V - 1) * ldw; });
     __syncthreads();
     f32x4 acc[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto mma = [&](int u, int srel) {
-        const int s = s_first + srel;
-        const int sl = lg * 16 + ((li + 4 * lg + s) & 15);
-        const f32x4 b0 = wl[s * 192 + sl], b1 = wl[s * 192 + 64 + sl], b2 = wl[s * 192 + 128 + sl];
+        f32x4 b[3];
+        wfrag_read(wl, s_first + srel, lane, b);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b0[j], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b1[j], acc[1], 0, 0, 0);
-            acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b2[j], acc[2], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b[0][j], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b[1][j], acc[1], 0, 0, 0);
+            acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][j], b[2][j], acc[2], 0, 0, 0);
         }
     };
-    // the plain loads of the fill are older than nothing of the ring that is still needed: every counted wait below also covers them
-    const int nmain = nks / PF * PF;
-    int s = 0;
-    if (nmain > 0) {
-        for (; s + PF < nmain; s += PF) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                fn_wait_vm<PF - 1>();
-                mma(u, s + u);
-                load(u);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // the ring holds steps s .. s + PF - 1
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            if (u == 0) fn_wait_vm<PF - 1>();
-            else if (u == 1 && PF > 1) fn_wait_vm<(PF > 1 ? PF - 2 : 0)>();
-            else if (u == 2 && PF > 2) fn_wait_vm<(PF > 2 ? PF - 3 : 0)>();
-            else fn_wait_vm<0>();
-            mma(u, s + u);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        s += PF;
-    } else {
-        fn_wait_vm<0>();                             // fewer steps than ring slots (K < 16 PF)
-#pragma unroll
-        for (int u = 0; u < PF; ++u)
-            if (u < npro) mma(u, u);
-        s = npro;
-    }
-#pragma unroll
-    for (int u = 0; u < PF; ++u) fn_keep(fa[u]);
-    for (; s < nks; ++s) {                           // < PF leftover steps, unpipelined
-        load(0);
-        fn_wait_vm<0>();
-        mma(0, s);
-        fn_keep(fa[0]);
-    }
-    {
+    // the plain loads of the fill are older than nothing of the ring that is still needed: every counted wait of the ring also covers them
+    fn_ring_run<PF, 1, true>(nks, load, mma, [&](int set) { fn_keep(fa[set]); });
+    if (KH > 1) {
         f32x4* rd = reinterpret_cast<f32x4*>(dsm + (long)48 * K) + (wave * 3) * 64 + lane;     // behind the weight fragments
         if (kh) {
 #pragma unroll
@@ -1209,25 +1086,26 @@ __global__ __launch_bounds__(2 * NT) void out_argmax_lds8_kernel(const float* __
         if (kh) return;
 #pragma unroll
         for (int q = 0; q < 3; ++q) acc[q] += rd[q * 64];
+    } else {
+        out_argmax_bias(bias, n0, lane, V, bv);
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned long long w = 0ull;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int col = n0 + 16 * q + li;
-            const unsigned long long c = col < V ? fn_pack_best(acc[q][i] + bv[q], col, V) : 0ull;
-            w = c > w ? c : w;
-        }
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-            const unsigned lo = __shfl_xor((unsigned)(w & 0xffffffffull), d, 64), hi = __shfl_xor((unsigned)(w >> 32), d, 64);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            w = o > w ? o : w;
-        }
-        const int row = m0 + 4 * lg + i;
-        if (li == 0 && row < B) atomicMax(best + row, w);
-    }
+    out_argmax_epilogue(acc, bv, m0, n0, lane, B, V, best);
+}
+
+template <int PF>
+__global__ __launch_bounds__(NT) void out_argmax_lds_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ W, long ldw,
+                                                            const float* __restrict__ bias, int B, int V, int K,
+                                                            unsigned long long* __restrict__ best) {
+    extern __shared__ __attribute__((aligned(16))) float dsm[];
+    out_argmax_lds_body<PF, 1>(dsm, h, ldh, W, ldw, bias, B, V, K, best);
+}
+
+template <int PF>
+__global__ __launch_bounds__(2 * NT) void out_argmax_lds8_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ W, long ldw,
+                                                            const float* __restrict__ bias, int B, int V, int K,
+                                                            unsigned long long* __restrict__ best) {
+    extern __shared__ __attribute__((aligned(16))) float dsm[];
+    out_argmax_lds_body<PF, 2>(dsm, h, ldh, W, ldw, bias, B, V, K, best);
 }
 
 __global__ __launch_bounds__(256) void best_tokens_kernel(const unsigned long long* __restrict__ best, long n, int B, int V, int* __restrict__ tokens, long tok_ld) {
@@ -1252,98 +1130,19 @@ static bool cell_direct_ok(const CellArgs& a) {
 template <int RT, int PF>
 int launch_cell_direct(const CellArgs& a, hipStream_t st) {
     const int tiles = ((a.B + 32 * RT - 1) / (32 * RT)) * (a.H / 32);
-    const bool tab = a.gx_table != nullptr, rb = a.gx_rowbias != nullptr;
-    if (tab && rb) hipLaunchKernelGGL((gru_cell_direct_kernel<RT, PF, true, true>), dim3(tiles), dim3(NT), 0, st, a);
-    else if (tab) hipLaunchKernelGGL((gru_cell_direct_kernel<RT, PF, true, false>), dim3(tiles), dim3(NT), 0, st, a);
-    else if (rb) hipLaunchKernelGGL((gru_cell_direct_kernel<RT, PF, false, true>), dim3(tiles), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((gru_cell_direct_kernel<RT, PF, false, false>), dim3(tiles), dim3(NT), 0, st, a);
-    FN_CHECK_LAUNCH();
-    return FN_OK;
-}
-
-// Gate epilogue of the cells with an LDS-resident weight slice, on (row, 4 units) items: the accumulator tiles of row tile m go through the
-// wave-private LDS tile tw (D layout in, lane (row = l >> 2, units 4 (l & 3) ..) out), every other operand - old state, token row, row
-// constant - is ONE 16-byte load per gate and item, the new state one 16-byte store.  tok[m]: the token of the lane's row of tile m.
-// biases and old-state rows of the epilogue items: requested in front of the last K phase where the registers allow it (EARLY)
-template <int RT>
-struct CellEpiPre { f32x4 bi[3], bh[3], hv[RT]; };
-template <int RT>
-FN_DEVINL void cell_epilogue_request(const CellArgs& a, int m0, int u0, int lane, CellEpiPre<RT>& p) {
-    const int er = lane >> 2, eu = u0 + 4 * (lane & 3);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        p.bh[q] = *reinterpret_cast<const f32x4*>(a.b_hh + q * a.H + eu);
-        p.bi[q] = a.b_ih ? *reinterpret_cast<const f32x4*>(a.b_ih + q * a.H + eu) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int m = 0; m < RT; ++m) p.hv[m] = *reinterpret_cast<const f32x4*>(a.h_prev + (long)min(m0 + 16 * m + er, a.B - 1) * a.ldh + eu);
-}
-
-template <int RT, bool HAS_TAB, bool HAS_RB>
-FN_DEVINL void cell_epilogue_items(const CellArgs& a, int m0, int u0, int lane, float* tw, const int (&tok)[RT], const f32x4 (&arz)[RT][2],
-                                   const f32x4 (&anx)[RT], const f32x4 (&anh)[RT], const CellEpiPre<RT>& pre) {
-    const int li = lane & 15, lg = lane >> 4;
-    const int er = lane >> 2, eu = u0 + 4 * (lane & 3);
-    const f32x4 (&bi)[3] = pre.bi;
-    const f32x4 (&bh)[3] = pre.bh;
-    const f32x4 (&hv)[RT] = pre.hv;
-    const long H3 = 3L * a.H;
-    f32x4 tv[RT][3], rv[RT][3];
-    int rows[RT];
-#pragma unroll
-    for (int m = 0; m < RT; ++m) {
-        rows[m] = m0 + 16 * m + er;
-        const int rc = min(rows[m], a.B - 1);
-        if (HAS_TAB) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) tv[m][q] = *reinterpret_cast<const f32x4*>(a.gx_table + (long)tok[m] * H3 + q * a.H + eu);
-        }
-        if (HAS_RB) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) rv[m][q] = *reinterpret_cast<const f32x4*>(a.gx_rowbias + (long)rc * H3 + q * a.H + eu);
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < RT; ++m) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            tw[0 * 320 + (4 * lg + i) * 20 + li] = arz[m][0][i];
-            tw[1 * 320 + (4 * lg + i) * 20 + li] = arz[m][1][i];
-            tw[2 * 320 + (4 * lg + i) * 20 + li] = anx[m][i];
-            tw[3 * 320 + (4 * lg + i) * 20 + li] = anh[m][i];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const f32x4 g_r = *reinterpret_cast<const f32x4*>(tw + 0 * 320 + er * 20 + 4 * (lane & 3));
-        const f32x4 g_z = *reinterpret_cast<const f32x4*>(tw + 1 * 320 + er * 20 + 4 * (lane & 3));
-        const f32x4 g_nx = *reinterpret_cast<const f32x4*>(tw + 2 * 320 + er * 20 + 4 * (lane & 3));
-        const f32x4 g_nh = *reinterpret_cast<const f32x4*>(tw + 3 * 320 + er * 20 + 4 * (lane & 3));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        f32x4 o;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float gi[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                float e = bi[q][c];
-                if (HAS_TAB) e += tv[m][q][c];
-                if (HAS_RB) e += rv[m][q][c];
-                gi[q] = e;
-            }
-            const float r = fn_sigmoid((gi[0] + bh[0][c]) + g_r[c]);
-            const float z = fn_sigmoid((gi[1] + bh[1][c]) + g_z[c]);
-            const float n = fn_tanh((gi[2] + g_nx[c]) + r * (g_nh[c] + bh[2][c]));
-            o[c] = (1.0f - z) * n + z * hv[m][c];
-        }
-        if (rows[m] < a.B) *reinterpret_cast<f32x4*>(a.h_out + (long)rows[m] * a.ldo + eu) = o;
-    }
+    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) {
+        hipLaunchKernelGGL((gru_cell_direct_kernel<RT, PF, decltype(TAB)::value, decltype(RB)::value>), dim3(tiles), dim3(NT), 0, st, a);
+        FN_CHECK_LAUNCH();
+        return (int)FN_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // The cell with the WEIGHT operand of a K phase resident in LDS (as out_argmax_lds_kernel): the LDS-free loop above is bound by its
 // operand loads (~8 TB/s of 16 x 64-byte pieces per instruction: 7 loads per 48 MFMAs), not by the MFMA pipe.  Here a workgroup owns
-// 64 RT rows x 16 hidden units: the 48 weight rows of its units (48 x K floats, 96 KB at K = 512) are laid out once per phase as MFMA
-// fragments [k step][gate][lane] (16-byte LDS reads, slots rotated against bank conflicts), and only the RT state-row tiles of a wave are
-// read from memory in the loop (RT loads per 12 RT MFMAs).  Layer 2 fills the slice twice (W_ih, then W_hh after a barrier).
+// 64 RT rows x 16 hidden units: the 48 weight rows of its units (48 x K floats, 96 KB at K = 512; row r of 48 = gate r >> 4, unit r & 15)
+// are laid out once per phase as MFMA fragments (wfrag_fill), and only the RT state-row tiles of a wave are read from memory in the loop
+// (RT loads per 12 RT MFMAs).  Layer 2 fills the slice twice (W_ih, then W_hh after a barrier).
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
 __global__ __launch_bounds__(NT) void gru_cell_wlds_kernel(const CellArgs a, int kmax) {
     static_assert(PF >= 2 && (PF % 2) == 0, "the fragment double buffer follows the parity of the ring slot");
@@ -1360,47 +1159,23 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_kernel(const CellArgs a, int
     for (int m = 0; m < RT; ++m) arz[m][0] = arz[m][1] = anx[m] = anh[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     f32x4 fa[PF][RT];
     auto phase = [&](const float* A, long lda, const float* W, long ldw, int K, f32x4 (&accn)[RT], bool refill) {
-        const int nks = K >> 4, kq = K >> 2;
+        const int nks = K >> 4;
         unsigned oa[RT];
 #pragma unroll
         for (int m = 0; m < RT; ++m) oa[m] = (unsigned)(((long)min(m0 + 16 * m + li, a.B - 1) * lda + 4 * lg) * 4);
         const float* pa = A;
         auto load = [&](int set) {
 #pragma unroll
-            for (int m = 0; m < RT; ++m) fn_gld4_sb(fa[set][m], oa[m], pa);
+            for (int m = 0; m < RT; ++m) fn_gld4_s(fa[set][m], oa[m], pa);
             pa += 16;
         };
-        const int npro = min(PF, nks);
-#pragma unroll
-        for (int s = 0; s < PF; ++s)
-            if (s < npro) load(s);
+        fn_ring_request<PF>(nks, load);
         if (refill) __syncthreads();                 // every wave has left the previous phase's loop
-        // weight fragments: item (row r of 48 = gate r >> 4, unit r & 15; k quad c) -> step c >> 2, gate, lane group c & 3, slot (r & 15) rotated
-        const int total = 48 * kq, dq = NT / kq, dr = NT % kq;
-        int fr = threadIdx.x / kq, fc = threadIdx.x % kq;
-        for (int base = threadIdx.x; base < total; base += NT * 8) {
-            f32x4 v[8];
-            int rr[8], cc[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                rr[u] = fr;
-                cc[u] = fc;
-                const int r = min(fr, 47);
-                v[u] = *reinterpret_cast<const f32x4*>(W + (long)((r >> 4) * a.H + u0 + (r & 15)) * ldw + 4 * fc);
-                fc += dr;
-                fr += dq;
-                if (fc >= kq) { fc -= kq; ++fr; }
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int r = rr[u], c = cc[u];
-                if (r < 48) wl[(c >> 2) * 192 + (r >> 4) * 64 + (c & 3) * 16 + (((r & 15) + 4 * (c & 3) + (c >> 2)) & 15)] = v[u];
-            }
-        }
+        wfrag_fill<NT>(wl, K, [&](int r) { return W + (long)((r >> 4) * a.H + u0 + (r & 15)) * ldw; });
         __syncthreads();
         // weight fragments of step s + 1 are read while the MFMAs of step s run (bq[parity]); PF is even, so the parity of a step is its ring slot's
         f32x4 bq[2][3];
-        auto bread = [&](int buf, int s) {
+        auto bread = [&](int buf, int s) {               // (wfrag_read written out: through the helper <3, 2, true, true> took 192 registers for 190)
             const int sl = lg * 16 + ((li + 4 * lg + s) & 15);
             bq[buf][0] = wl[s * 192 + sl];
             bq[buf][1] = wl[s * 192 + 64 + sl];
@@ -1417,53 +1192,12 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_kernel(const CellArgs a, int
                     accn[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[u][m][j], bq[u & 1][2][j], accn[m], 0, 0, 0);
                 }
         };
+        auto keep = [&](int set) {
+#pragma unroll
+            for (int m = 0; m < RT; ++m) fn_keep(fa[set][m]);
+        };
         bread(0, 0);
-        const int nmain = nks / PF * PF;
-        int s = 0;
-        if (nmain > 0) {
-            for (; s + PF < nmain; s += PF) {
-#pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    fn_wait_vm<RT * (PF - 1)>();
-                    mma(u, s + u);
-                    load(u);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                if (u == 0) fn_wait_vm<RT * (PF - 1)>();
-                else if (u == 1 && PF > 1) fn_wait_vm<(PF > 1 ? RT * (PF - 2) : 0)>();
-                else if (u == 2 && PF > 2) fn_wait_vm<(PF > 2 ? RT * (PF - 3) : 0)>();
-                else fn_wait_vm<0>();
-                mma(u, s + u);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            s += PF;
-        } else {
-            fn_wait_vm<0>();                         // fewer steps than ring slots
-#pragma unroll
-            for (int u = 0; u < PF; ++u)
-                if (u < npro) mma(u, u);
-            s = npro;
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u)
-#pragma unroll
-            for (int m = 0; m < RT; ++m) fn_keep(fa[u][m]);
-        for (; s < nks; ++s) {                       // < PF leftover steps, unpipelined; ring slot = parity of the step (bq[parity] holds its fragments)
-            if (s & 1) {
-                load(1);
-                fn_wait_vm<0>();
-                mma(1, s);
-            } else {
-                load(0);
-                fn_wait_vm<0>();
-                mma(0, s);
-            }
-#pragma unroll
-            for (int m = 0; m < RT; ++m) { fn_keep(fa[0][m]); fn_keep(fa[1][m]); }
-        }
+        fn_ring_run<PF, RT, true, true>(nks, load, mma, keep);       // leftover steps in slot = parity of the step (bq[parity] holds its fragments)
     };
     // the token of every epilogue row now (the table-row loads of the epilogue then cost one memory latency, not two)
     int tok[RT];
@@ -1471,9 +1205,12 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_kernel(const CellArgs a, int
     for (int m = 0; m < RT; ++m) tok[m] = HAS_TAB ? a.token(min(m0 + 16 * m + (lane >> 2), a.B - 1)) : 0;
     if (a.x) phase(a.x, a.ldx, a.w_ih, a.ldw_ih, a.K1, anx, false);
     phase(a.h_prev, a.ldh, a.w_hh, a.ldw_hh, a.H, anh, a.x != nullptr);
-    CellEpiPre<RT> pre;
-    cell_epilogue_request<RT>(a, m0, u0, lane, pre);
-    cell_epilogue_items<RT, HAS_TAB, HAS_RB>(a, m0, u0, lane, tr + wave * 4 * 320, tok, arz, anx, anh, pre);
+    CellEpi<RT> epi;
+    auto tokf = [&](int m, int) { return tok[m]; };
+    cell_epilogue_request_bias<RT>(a, u0, lane, epi);
+    cell_epilogue_request_rows<RT, true, false, false>(a, m0, u0, lane, tokf, epi);
+    cell_epilogue_request_rows<RT, false, HAS_TAB, HAS_RB>(a, m0, u0, lane, tokf, epi);
+    cell_epilogue_finish<RT, HAS_TAB, HAS_RB>(a, m0, u0, lane, tr + wave * 4 * 320, arz, anx, anh, epi);
 }
 
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
@@ -1495,11 +1232,7 @@ template <int RT, int PF>
 int launch_cell_wlds(const CellArgs& a, hipStream_t st) {
     const int kmax = a.x ? (a.K1 > a.H ? a.K1 : a.H) : a.H;
     const size_t lds = (size_t)48 * kmax * 4 + 4 * 4 * 320 * 4;
-    const bool tab = a.gx_table != nullptr, rb = a.gx_rowbias != nullptr;
-    if (tab && rb) return launch_cell_wlds_inst<RT, PF, true, true>(a, kmax, lds, st);
-    if (tab) return launch_cell_wlds_inst<RT, PF, true, false>(a, kmax, lds, st);
-    if (rb) return launch_cell_wlds_inst<RT, PF, false, true>(a, kmax, lds, st);
-    return launch_cell_wlds_inst<RT, PF, false, false>(a, kmax, lds, st);
+    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_wlds_inst<RT, PF, decltype(TAB)::value, decltype(RB)::value>(a, kmax, lds, st); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1671,11 +1404,7 @@ int launch_cell_x6_inst(const CellArgs& a, hipStream_t st) {
 }
 
 int launch_cell_x6(const CellArgs& a, hipStream_t st) {
-    const bool tab = a.gx_table != nullptr, rb = a.gx_rowbias != nullptr;
-    if (tab && rb) return launch_cell_x6_inst<true, true>(a, st);
-    if (tab) return launch_cell_x6_inst<true, false>(a, st);
-    if (rb) return launch_cell_x6_inst<false, true>(a, st);
-    return launch_cell_x6_inst<false, false>(a, st);
+    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_x6_inst<decltype(TAB)::value, decltype(RB)::value>(a, st); });
 }
 
 FN_DEVINL void fn_wait_vm_n(int n) {                // n folds to a constant in fully unrolled loops
@@ -1712,6 +1441,8 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_ovl_kernel(const CellArgs a)
     // one lane offset for all items, the item's part of the address in a scalar base (no vector address arithmetic, no pointer registers)
     auto f_off = [&](long ldw) { return (unsigned)((((long)(u0 + wave) * ldw) + 4 * lane) * 4); };
     auto f_base = [&](const float* W, long ldw, int half, int j) { return W + ((long)(j >> 2) * a.H + 4 * (j & 3)) * ldw + 256 * half; };
+    // (wfrag_slot(r, c) and, in bread below, wfrag_read written out: through the helpers the 192- and 256-row instances took 2 - 10 more registers,
+    // <4, 2, true, false> its first AGPR copies - profiles/decode_cells_refactor.txt)
     auto fill_store = [&](int half) {
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
@@ -1727,7 +1458,7 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_ovl_kernel(const CellArgs a)
         const float* pa = A;
         auto load = [&](int set) {
 #pragma unroll
-            for (int m = 0; m < RT; ++m) fn_gld4_sb(fa[set][m], oa[m], pa);
+            for (int m = 0; m < RT; ++m) fn_gld4_s(fa[set][m], oa[m], pa);
             pa += 16;
         };
 #pragma unroll
@@ -1771,9 +1502,9 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_ovl_kernel(const CellArgs a)
                 }
             if (u + PF < NKS) load(u % PF);
             if (u < HALF) {
-                if (u < NF) fn_gld4_sb(fv[u], fo, f_base(W, ldw, 1, u));
+                if (u < NF) fn_gld4_s(fv[u], fo, f_base(W, ldw, 1, u));
             } else if (pre2 && u - HALF < NF) {
-                fn_gld4_sb(fv[u - HALF], fon, f_base(Wn, ldwn, 0, u - HALF));
+                fn_gld4_s(fv[u - HALF], fon, f_base(Wn, ldwn, 0, u - HALF));
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -1806,17 +1537,23 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_ovl_kernel(const CellArgs a)
     using T_ = std::integral_constant<bool, true>;
     using F_ = std::integral_constant<bool, false>;
     constexpr bool EARLY = RT <= 2;                  // (the 192- and 256-row forms have no registers left beside their rings: no AGPR copies next to asm loads)
-    CellEpiPre<RT> pre;
+    CellEpi<RT> epi;
+    auto tokf = [&](int m, int) { return tok[m]; };
+    auto request_state = [&]() {                     // biases and old-state rows
+        cell_epilogue_request_bias<RT>(a, u0, lane, epi);
+        cell_epilogue_request_rows<RT, true, false, false>(a, m0, u0, lane, tokf, epi);
+    };
     if (a.x) {
         phase(a.x, a.ldx, a.w_ih, a.ldw_ih, anx, T_{}, T_{}, a.w_hh, a.ldw_hh);
-        if (EARLY) cell_epilogue_request<RT>(a, m0, u0, lane, pre);
+        if (EARLY) request_state();
         phase(a.h_prev, a.ldh, a.w_hh, a.ldw_hh, anh, F_{}, F_{}, nullptr, 0);
     } else {
-        if (EARLY) cell_epilogue_request<RT>(a, m0, u0, lane, pre);
+        if (EARLY) request_state();
         phase(a.h_prev, a.ldh, a.w_hh, a.ldw_hh, anh, T_{}, F_{}, nullptr, 0);
     }
-    if (!EARLY) cell_epilogue_request<RT>(a, m0, u0, lane, pre);
-    cell_epilogue_items<RT, HAS_TAB, HAS_RB>(a, m0, u0, lane, tr + wave * 4 * 320, tok, arz, anx, anh, pre);
+    if (!EARLY) request_state();
+    cell_epilogue_request_rows<RT, false, HAS_TAB, HAS_RB>(a, m0, u0, lane, tokf, epi);
+    cell_epilogue_finish<RT, HAS_TAB, HAS_RB>(a, m0, u0, lane, tr + wave * 4 * 320, arz, anx, anh, epi);
 }
 
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
@@ -1833,11 +1570,7 @@ static bool cell_wlds_ovl_ok(const CellArgs& a) { return a.H == 512 && (!a.x || 
 
 template <int RT, int PF>
 int launch_cell_wlds_ovl(const CellArgs& a, hipStream_t st) {
-    const bool tab = a.gx_table != nullptr, rb = a.gx_rowbias != nullptr;
-    if (tab && rb) return launch_cell_wlds_ovl_inst<RT, PF, true, true>(a, st);
-    if (tab) return launch_cell_wlds_ovl_inst<RT, PF, true, false>(a, st);
-    if (rb) return launch_cell_wlds_ovl_inst<RT, PF, false, true>(a, st);
-    return launch_cell_wlds_ovl_inst<RT, PF, false, false>(a, st);
+    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_wlds_ovl_inst<RT, PF, decltype(TAB)::value, decltype(RB)::value>(a, st); });
 }
 
 template <int BM, int WM, int WN>

@@ -29,6 +29,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // loop must end with fn_wait_vm<0>() before the registers can be reused.
 FN_DEVINL void fn_gld4_asm(f32x4& dst, const float* p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory"); }
 FN_DEVINL void fn_gld1_asm(float& dst, const float* p) { asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(p) : "memory"); }
+// the same with a scalar base + a fixed 32-bit lane offset: no vector address arithmetic in a K loop that advances the base
+FN_DEVINL void fn_gld4_s(f32x4& dst, unsigned voff, const float* sbase) {
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
+}
 // A fake use: keeps an asm-loaded register allocated (not re-used for anything else) up to this point.  Every register a
 // fn_gld4_asm targets must reach a fn_keep() placed AFTER the wait that covers it, otherwise hipcc may recycle a
 // "dead" destination while the load is still in flight.
@@ -38,6 +42,7 @@ FN_DEVINL void fn_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
+#include "ring_core.h"       // the register ring built on these waits
 
 // wave-uniform by construction (depends on the wave id only); the compiler cannot see that
 FN_DEVINL const float* fn_uniform_ptr(const float* p) {
@@ -247,4 +252,18 @@ FN_DEVINL int fn_xcd_remap(int b, int n) {
     if (!FN_XCD_REMAP) return b;
     const int q = n >> 3, r = n & 7, x = b & 7, s = b >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + s;
+}
+
+// (row panel, unit tile) of a cell workgroup (gru_cell_direct_kernel; gru_cell_kernel has the same text inline), panels of bm rows: 4 x 8 super-tiles (row panels x unit tiles) in consecutive virtual ids = on one XCD
+FN_DEVINL void fn_supertile(int block, int nblocks, int rows, int bm, int nut, int& tm, int& tu) {
+    const int v = fn_xcd_remap(block, nblocks);
+    const int ntm = (rows + bm - 1) / bm;
+    if ((ntm % 4) == 0 && (nut % 8) == 0) {
+        const int sb = v >> 5, l = v & 31, sbu = nut >> 3;
+        tm = (sb / sbu) * 4 + (l >> 3);
+        tu = (sb % sbu) * 8 + (l & 7);
+    } else {
+        tm = v / nut;
+        tu = v % nut;
+    }
 }

@@ -150,6 +150,88 @@ def test_gru_cell_dense(ops, B, H, K1, mode, variant):
     close(out, ref, 2e-5, "gru_cell")
 
 
+# The K-loop tails and the four epilogue forms of the LDS-free and weight-slice cells at 70 rows (ragged against every row tile).  nks = K / 16 steps
+# of a K phase against a ring of PF slots: dense K1 = 16 .. 272 at H = 32 gives nks = 1, 2, 3, 5, 9, 17 (fewer steps than slots, exactly one ring,
+# ring + leftover, one steady pass, steady pass + odd leftover for PF up to 8); without a dense input the recurrent phase alone: H = 32, 96 = nks 2, 6.
+# H = 272 (17 steps) is no multiple of 32: fn_gru_cell_f32 refuses it by its contract, whatever the variant, and the test pins that answer; H = 288
+# (18 steps: two / four rings + two leftover steps for PF 8 / 4) is the nearest size the entry point takes.  The overlapped-fill cells (15-18) exist
+# for H = 512, K1 in {0, 512} only.
+CELL_TAIL_SHAPES = [(32, k1) for k1 in (16, 32, 48, 80, 144, 272)] + [(32, 0), (96, 0), (272, 0), (288, 0)]
+CELL_TAIL_VARIANTS = (4, 5, 6, 7, 10, 12, 14)               # direct PF 1 / 4 / 2 / 2, wlds PF 4 / 8 / 2
+CELL_OVL_SHAPES = [(512, 512), (512, 0)]
+CELL_OVL_VARIANTS = (15, 16, 17, 18)
+CELL_FORMS = ((False, False), (False, True), (True, True), (True, False))      # (token table, row constant): dense only, + row constant, table + row constant, table alone
+CELL_TAIL_ROWS = 70
+
+
+def _cell_runs_forced_family(variant, H, K1):
+    """fn_gru_cell_f32's eligibility rules for a forced variant on contiguous 16-byte aligned fp32 operands (what torch allocates): the LDS-free
+    cells 4-7 need H % 32 == 0 and K1 % 16 == 0; the weight-slice cells 9-14 also 48 max(K1, H) floats + four 16 x 20 tiles per wave within 160 KB of
+    LDS; the overlapped-fill cells 15-18 H == 512 and K1 in {0, 512}.  Anything else runs the staged default; H % 32 != 0 is refused (FN_E_SHAPE)."""
+    direct = H % 32 == 0 and K1 % 16 == 0
+    if 4 <= variant <= 7:
+        return direct
+    if 9 <= variant <= 14:
+        return direct and 48 * max(K1, H) * 4 + 4 * 4 * 320 * 4 <= 160 * 1024
+    if 15 <= variant <= 18:
+        return direct and H == 512 and K1 in (0, 512)
+    return False
+
+
+_cell_tail_cache = {}
+
+
+def _cell_tail_case(H, K1, tab, rb):
+    key = (H, K1, tab, rb)
+    if key not in _cell_tail_cache:
+        B, V = CELL_TAIL_ROWS, 50
+        gen = torch.Generator().manual_seed(1000 * H + K1)
+        rn = lambda *s: torch.randn(*s, generator=gen)
+        hp = rn(B, H) * 0.5
+        whh, bhh, bih = rn(3 * H, H) / H ** 0.5, rn(3 * H) * 0.1, rn(3 * H) * 0.1
+        kw = dict(b_ih=bih)
+        if K1:
+            kw.update(x=rn(B, K1), w_ih=rn(3 * H, K1) / K1 ** 0.5)
+        toks = torch.randint(0, V, (B, 7), generator=gen, dtype=torch.int32)
+        if tab:
+            kw.update(gx_table=rn(V, 3 * H) * 0.3, idx=toks[:, 3])
+        if rb:
+            kw.update(gx_rowbias=rn(B, 3 * H) * 0.3)
+        ref = torch.zeros(B, H)
+        FakeOps().gru_cell(hp, whh, bhh, ref, **kw)
+        dkw = {k: g(v) for k, v in kw.items() if k != "idx"}
+        if tab:
+            dkw["idx"] = g(toks)[:, 3]
+        _cell_tail_cache[key] = (g(hp), g(whh), g(bhh), dkw, ref)
+    return _cell_tail_cache[key]
+
+
+def test_cell_tail_cases_run_the_forced_kernels():
+    """more than half of the (shape, variant, form) cases below launch the kernel family their variant names (all of them, by the rules)"""
+    cases = [(v, H, K1) for H, K1 in CELL_TAIL_SHAPES for v in CELL_TAIL_VARIANTS] + [(v, H, K1) for H, K1 in CELL_OVL_SHAPES for v in CELL_OVL_VARIANTS]
+    forced = sum(_cell_runs_forced_family(*c) for c in cases)
+    assert len(cases) == 10 * 7 + 2 * 4 and forced == len(cases) - 7 and 2 * forced > len(cases), (forced, len(cases))      # all but the refused H = 272
+
+
+@pytest.mark.parametrize("variant,H,K1", [(v, H, K1) for H, K1 in CELL_TAIL_SHAPES for v in CELL_TAIL_VARIANTS]
+                         + [(v, H, K1) for H, K1 in CELL_OVL_SHAPES for v in CELL_OVL_VARIANTS])
+def test_gru_cell_ring_tails_and_epilogue_forms(ops, variant, H, K1):
+    """fn_gru_cell_f32, forced LDS-free (4-7), weight-slice (10, 12, 14) and overlapped-fill (15-18) cells at 70 rows: every K tail of the shared ring
+    (CELL_TAIL_SHAPES) in the four input forms - dense only, dense + row constant, token table + row constant, token table alone; the second and the
+    fourth are the HAS_TAB != HAS_RB instantiations - against tests/fake_ops.py at 2e-5, and a second launch bit for bit."""
+    for tab, rb in CELL_FORMS:
+        hp, whh, bhh, kw, ref = _cell_tail_case(H, K1, tab, rb)
+        out = torch.zeros(2, CELL_TAIL_ROWS, H, device=DEV)
+        if H % 32:
+            with pytest.raises(RuntimeError, match="fn_gru_cell_f32 failed.*sizes"):
+                ops.gru_cell(hp, whh, bhh, out[0], variant=variant, **kw)
+            continue
+        ops.gru_cell(hp, whh, bhh, out[0], variant=variant, **kw)
+        ops.gru_cell(hp, whh, bhh, out[1], variant=variant, **kw)
+        close(out[0], ref, 2e-5, "gru_cell variant %d H %d K1 %d table %d row constant %d" % (variant, H, K1, tab, rb))
+        assert torch.equal(out[0], out[1]), (variant, H, K1, tab, rb)
+
+
 @pytest.mark.parametrize("B,H,K1,mode", [(2048, 512, 512, "dense"), (1024, 512, 0, "table"), (768, 512, 0, "table0"), (128, 64, 32, "dense"), (256, 96, 64, "dense"),
                                          (1280, 512, 512, "dense_rb")])
 def test_gru_cell_bf16x6(ops, B, H, K1, mode):
@@ -1570,7 +1652,8 @@ def test_large_batch_decode_cells_match_per_token_kernels(H, Bi, steps):
     close(lp1[keep], lp0[keep], 2e-5)
 
 
-@pytest.mark.parametrize("B,V,K", [(2048, 342, 512), (77, 342, 512), (300, 50, 64), (33, 97, 48), (130, 342, 112), (70, 60, 1024)])
+@pytest.mark.parametrize("B,V,K", [(2048, 342, 512), (77, 342, 512), (300, 50, 64), (33, 97, 48), (130, 342, 112), (70, 60, 1024),
+                                   (70, 97, 16), (70, 97, 32), (70, 97, 80)])      # K / 16 = 1, 2, 5 steps: below, at and above the ring of the eight-wave kernel (two steps per K half at 5), one-ring kernel for K = 16, 80
 def test_out_argmax_packed_words(ops, B, V, K):
     """fn_out_argmax_f32 (output layer with the argmax in its epilogue: packed (logit, column) words by 64-bit atomic max) + fn_best_tokens
     against the fp64 logits: the winning column wherever the fp64 top-2 gap is above 1e-4, the packed key = the order-preserving image of a

@@ -419,6 +419,22 @@ def test_isa_wait_checker_finds_an_uncovered_asm_load(tmp_path):
     assert os.path.exists(os.path.join(csrc, "isa.checked")), "run __graft_entry__.build(): csrc/Makefile checks the compiled kernels (isa.checked)"
 
 
+def test_ring_driver_schedule_under_sanitizers(tmp_path):
+    """csrc/ring_core.h (the register ring of the LDS-free decode K loops) compiled for the host with recording stubs for the counted wait and the
+    scheduling barrier (csrc/host/ring_check.cpp, a stand-alone program, nothing preloaded): PF in {1, 2, 4, 8}, NL in {1, 4, 7}, 0 .. 3 PF + 2 steps,
+    both entry forms and the parity form, under the in-order retirement model of check_isa_waits.py - 0 findings."""
+    import subprocess
+    asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    if not os.path.isabs(asan) or not os.path.exists(asan):
+        pytest.skip("no AddressSanitizer runtime on this box (gcc -print-file-name=libasan.so)")
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "music-fader-nets_amd", "csrc", "host", "ring_check.cpp")
+    exe = str(tmp_path / "ring_check")
+    subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-Wall", "-Werror", src, "-o", exe], check=True, capture_output=True, timeout=300)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, (p.stdout[-2000:], p.stderr[-3000:])
+    assert "FINDING" not in p.stdout and p.stdout.strip().endswith("648 schedules, 0 findings"), p.stdout[-2000:]
+
+
 def test_fake_ops_do_not_read_an_output_they_overwrite():
     """beta == 0 means the output is write-only, as in the kernels (gemm.hip: `if (beta != 0.f)`): the engine hands over uninitialised
     buffers, and 0 x NaN is NaN.  (FakeOps.gru_dwhh once formed beta * dW: the gradient comparison above failed whenever the allocator
