@@ -747,8 +747,13 @@ int fn_latent_fwd(const float* pre, const float* eps, const float* mu_lk, const 
  * bakes the step-dependent beta into a kernel argument).  Fused loss gradient (trainer_gmm.py:150-194):
  *    L += w_lat * sum_b sum_k qy KLmean_k  + w_cls * sum_b mean_k(qy log qy)          (unsupervised)
  *    L += w_lat * sum_b KLmean_label       + w_clf * sum_b CE(softmax(qy), label)     (labels != NULL)
+ * The gradient is that of this formula AT THE GIVEN z and qy (the float32 arrays fn_latent_fwd wrote): the posterior is not
+ * recomputed from pre, and the softmax backward q_k (dq_k - sum_j q_j dq_j), dq_k = g_qy_k + dL/dq_k, uses qy as handed over.
+ * Near saturation this differs from the gradient of the posterior recomputed in float64 by up to 1e-5 of a tile maximum, because
+ * a float32 qy sums to 1 to one ulp only while dq carries KL means of about 1e3; a component with qy == 0 contributes 0 to
+ * the entropy gradient.  With labels w_cls is not read, without labels w_clf is not read.
  * outputs: dpre [B][2Z]; dmu_lk_rows [B][K][Z] per-row contributions to d mu_lookup (reduce with
- * fn_colsum_f32 over B). */
+ * fn_colsum_f32 over B; may be NULL). */
 int fn_latent_bwd(const float* pre, const float* eps, const float* mu_lk, const float* lv_lk, int B, int Z, int K,
                   const int32_t* labels, const float* z, const float* qy, const float* g_z, const float* g_mu,
                   const float* g_sigma, const float* g_ll, const float* g_qy, const float* w3, float* dpre,

@@ -281,22 +281,24 @@ class FakeOps:
         K = mu_lk.shape[0]
         mu, s = pre[:, :Z], torch.exp(pre[:, Z:])
         z = mu + s * eps
-        ll = torch.stack([(-0.5 * ((z - mu_lk[k]) ** 2 / torch.exp(lv_lk[k]) + lv_lk[k] + LOG_2PI)).sum(1) + math.log(1.0 / K)
-                          for k in range(K)], dim=1)
-        qy = torch.softmax(ll, dim=1)
+        # the log-likelihoods are ~1e3 while the posterior sees their differences only: summed and normalised in float64, as fn_latent_fwd does
+        zd, md, ld = z.double(), mu_lk.double(), lv_lk.double()
+        ll = torch.stack([(-0.5 * ((zd - md[k]) ** 2 / torch.exp(ld[k]) + ld[k] + LOG_2PI)).sum(1) + math.log(1.0 / K) for k in range(K)], dim=1)
+        logq = torch.log_softmax(ll, dim=1)
+        qy = torch.exp(logq).to(pre.dtype)
         sp = torch.exp(lv_lk)                              # [K][Z] used as STD
         vr = (s.unsqueeze(1) / sp) ** 2
         t1 = ((mu.unsqueeze(1) - mu_lk) / sp) ** 2
         klm = (0.5 * (vr + t1 - 1 - torch.log(vr))).mean(-1)      # [B][K]
-        return mu, s, z, ll, qy, klm
+        return mu, s, z, ll.to(pre.dtype), qy, klm, logq.to(pre.dtype)
 
     def latent_fwd(self, pre, eps, mu_lk, lv_lk, labels, sigma, z, ll, qy, y, terms):
-        mu, s, zz, l, q, klm = self._latent_math(pre, eps, mu_lk, lv_lk)
+        mu, s, zz, l, q, klm, lq = self._latent_math(pre, eps, mu_lk, lv_lk)
         sigma.copy_(s), z.copy_(zz), ll.copy_(l), qy.copy_(q)
         y.copy_(q.max(1)[1].to(torch.int32))
         terms.zero_()
         terms[:, 0] = (q * klm).sum(1)
-        terms[:, 1] = (q * torch.log_softmax(l, dim=1)).mean(1)
+        terms[:, 1] = (q * lq).mean(1)
         if labels is not None:
             lb = labels.long().view(-1, 1)
             terms[:, 2] = klm.gather(1, lb).view(-1)
@@ -316,15 +318,15 @@ class FakeOps:
         tot = torch.zeros(())
         rows = []
         for b in range(B):
-            mu, s, zz, l, q, klm = self._latent_math(pre_[b:b + 1], eps[b:b + 1], mlk[b], lv_lk)
-            rows.append((mu, s, zz, l, q, klm))
+            mu, s, zz, l, q, klm, lq = self._latent_math(pre_[b:b + 1], eps[b:b + 1], mlk[b], lv_lk)
+            rows.append((mu, s, zz, l, q, klm, lq))
         mu = torch.cat([r[0] for r in rows]); s = torch.cat([r[1] for r in rows]); zz = torch.cat([r[2] for r in rows])
-        l = torch.cat([r[3] for r in rows]); q = torch.cat([r[4] for r in rows]); klm = torch.cat([r[5] for r in rows])
+        l = torch.cat([r[3] for r in rows]); q = torch.cat([r[4] for r in rows]); klm = torch.cat([r[5] for r in rows]); lq = torch.cat([r[6] for r in rows])
         for g, t in ((g_z, zz), (g_mu, mu), (g_sigma, s), (g_ll, l), (g_qy, q)):
             if g is not None:
                 tot = tot + (g * t).sum()
         if labels is None:
-            tot = tot + w_lat * (q * klm).sum() + w_cls * (q * torch.log_softmax(l, dim=1)).mean(1).sum()
+            tot = tot + w_lat * (q * klm).sum() + w_cls * (q * lq).mean(1).sum()
         else:
             lb = labels.long().view(-1, 1)
             tot = tot + w_lat * klm.gather(1, lb).sum() + w_clf * (-torch.log_softmax(q, dim=1).gather(1, lb)).sum()

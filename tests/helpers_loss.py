@@ -1,7 +1,8 @@
 """Shared code of tests/test_loss_reference.py (CPU) and tests/test_gpu_loss.py (MI355X): the loss-head kernels of csrc/loss.hip - fn_vocab_logsoftmax,
 fn_vocab_logsoftmax_bwd, fn_vocab_argmax, fn_time_logsoftmax (both kernels), fn_time_logsoftmax_bwd, fn_masked_prob, fn_pairwise_reg, fn_adv_head and
 fn_onehot_to_index - against float64.  No GPU import: every driver takes the backend (`ops`: HipOps on the GPU, FakeOps or StepOps on the CPU) and the
-device as arguments.  fn_vocab_sample (tests/test_gpu_sampling.py) and the latent block are not covered here.
+device as arguments.  fn_vocab_sample has tests/test_gpu_sampling.py; the latent block (fn_latent_fwd, fn_latent_bwd) has tests/helpers_latent.py,
+tests/test_latent_reference.py and tests/test_gpu_latent.py, built on this module's layout.
 
 References.  Every *_math function is the documented operation in plain torch on the CPU, in float64 on the float32 inputs (the reference) and, the same
 lines, in float32 (the restatement).  StepOps wraps the float32 lines in the signatures of FakeOps / HipOps, so that the restatement - and a planted
