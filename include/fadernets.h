@@ -722,6 +722,48 @@ int fn_notes_from_tokens(const int32_t* tokens, int tok_ld, int rows, int steps,
 int fn_tokens_from_notes(const FnNote* notes, int n_total, const FnNoteSpan* spans, int rows, const FnNoteParams* params_dev, int32_t* tokens,
                          int tok_ld, int steps, int32_t* n_tokens, int32_t* n_kept, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reconstruction report (report.py, epochs.evaluation_phase): what the reference's evaluation_phase() computes behind its loss terms
+ * (trainer_gmm.py:470-610) - the accuracies.  The reference's: `torch.argmax(a, dim=-1)` (:546) and the per-sample loop of acc() with its
+ * np.trim_zeros cut (:549-565).  OURS: the negative log-likelihood and the rank of the target per token, which re-ranking decoded hypotheses
+ * and top-k accuracy need and the reference does not report.  Both entry points are additive: fn_version() stays 6.
+ *
+ * fn_token_score (replaces trainer_gmm.py:546 `torch.argmax(a, dim=-1)` on a materialised (B, T, V) tensor): row (b, t) starts at
+ * x + b*stride_b + t*stride_t (strides in floats) and has V valid floats, 1 <= V <= FN_SAMPLE_MAX_V; nothing behind them is read, every logit
+ * is read once and nothing of width V is written.  One signature serves the train forward's time-major logits [T*B][ld] (stride_t = B*ld,
+ * stride_b = ld), a decode's logp (Bi, steps, V) and the attribute decoders' logp_bt [B][Tr][Cc] (V = Cc).  target [B][tgt_ld] or NULL; the
+ * outputs pred, nll, rank [B][out_ld], each optional.  Per row, with tg = target[b][t] clamped to [0, V) as fn_token_sort clamps:
+ *   pred[b][t] = the first-index argmax of the row, by comparisons only: fn_vocab_argmax's token on the same floats;
+ *   nll[b][t]  = lse - x[tg] in the arithmetic of fn_vocab_logsoftmax: mx = max x; s = sum expf(x - mx), lane l of 64 adding its e = l, l + 64,
+ *                ... ascending from 0.0f, then s[l] += s[l ^ o] for o = 32 .. 1; lse = mx + logf(s);
+ *   rank[b][t] = #{j : x[j] > x[tg] or (x[j] == x[tg] and j < tg)}: an exact integer, 0 = the target is the argmax.
+ * A -inf logit is legal; a target whose logit is -inf has nll = +inf.  A row of only -inf, or a row that holds a NaN, gives unspecified
+ * values (every access stays in bounds).  One wavefront per row, 4 rows per workgroup, the row in registers.
+ * x NULL, pred, nll and rank all NULL, nll or rank without target: FN_E_NULL; B, T < 1, V outside [1, FN_SAMPLE_MAX_V], out_ld < T,
+ * tgt_ld < T with a target: FN_E_SHAPE; both before any launch.
+ *
+ * fn_match_rows (replaces the loop of acc(), trainer_gmm.py:549-565): pred [rows][pred_ld], target [rows][tgt_ld], T columns used.
+ *   trim != 0  the reference's quirk, kept exactly: lead = the number of leading zeros of the target row, len = (last non-zero) + 1 - lead
+ *              (np.trim_zeros trims both ends), and the comparison is pred[j] == target[lead + j] for j < len - the reference cuts `a` from
+ *              its start (:556) but `b` from its first non-zero (:555).
+ *   trim == 0  lead = 0, len = T.
+ *   correct = #{j < len : pred[j] == target[lead + j]};  acc = (double)correct / len, one fp64 division;
+ *   correct_topk = #{j < len : rank[lead + j] < topk}   (rank [rows][aux_ld]; correct_topk NULL iff rank NULL; topk >= 1);
+ *   nll_sum = the fp64 sum of the fp32 nll[lead + j], j < len (nll [rows][aux_ld]; nll_sum NULL iff nll NULL), in this order: lane l of 64 adds
+ *             j = l, l + 64, ... ascending from 0.0, then s[l] += s[l ^ o] for o = 32, 16, 8, 4, 2, 1;
+ *   status = 0, or FN_MATCH_EMPTY for an all-zero target row under trim: len = 0, lead = T, acc = 0, nll_sum = 0, counts 0 (the reference
+ *            divides by zero there).
+ * One wavefront per row, no LDS, no cap on T beyond int32.
+ * pred, target, lead, len, correct, acc or status NULL, rank without correct_topk or the reverse, nll without nll_sum or the reverse:
+ * FN_E_NULL; rows, T < 1, pred_ld or tgt_ld < T, aux_ld < T with nll or rank, topk < 1 with rank: FN_E_SHAPE; both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_MATCH_EMPTY 1
+int fn_token_score(const float* x, int64_t stride_b, int64_t stride_t, int B, int T, int V, const int32_t* target, int tgt_ld, int32_t* pred,
+                   float* nll, int32_t* rank, int out_ld, void* stream);
+int fn_match_rows(const int32_t* pred, int pred_ld, const int32_t* target, int tgt_ld, int rows, int T, int trim, const float* nll,
+                  const int32_t* rank, int aux_ld, int topk, int32_t* lead, int32_t* len, int32_t* correct, int32_t* correct_topk, double* acc,
+                  double* nll_sum, int32_t* status, void* stream);
+
 /* TIME-axis log_softmax of the sub-decoders (gmm_model.py:110,115; the reference's dim=1 quirk).
  * logits [Tr][B][Cc] time-major.  logp_bt [B][Tr][Cc].  target [B][Tr] or NULL.
  * nll_bc [B][Cc] (sum over t with target==c of -logp) ; dlogits [Tr][B][Cc] = grad_scale * dNLLsum/dlogits. */

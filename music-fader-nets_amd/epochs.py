@@ -1,7 +1,7 @@
 """Epoch drivers: the schedule, bookkeeping and log lines of the reference's ``training_phase`` functions - the GM-VAE trainer's
 (trainer_gmm.py:306-467, ``training_phase`` below, on top of GMVAETrainer) and those of the five ``model_config_v2.json`` trainers
 (``training_phase_v2``: trainer.py:191-271, trainer_singlevae.py:184-255, trainer_cvae.py:156-223, trainer_fader.py:164-236,
-trainer_glsr.py:304-379).
+trainer_glsr.py:304-379) - and the GM-VAE trainer's ``evaluation_phase`` (trainer_gmm.py:470-610, on report.reconstruction_report).
 
 Per epoch: supervised (VGMIDI-style) batches ``(d, r, n, c, arousal, valence, r_density, n_density)`` are trained with
 ``is_supervised=True, y_label=arousal`` and evaluated (``evaluate`` is called with ``step - 1``, still in train mode, as the reference
@@ -79,6 +79,55 @@ def training_phase(trainer, step, n_epochs, vgm_train_dl, vgm_val_dl, train_dl, 
         torch.save(cpu_state_dict(model), stamped)
     log("Model saved as {}!".format(save_path))
     return step
+
+
+def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True):
+    """``run(dl)`` of the reference's ``evaluation_phase()`` (trainer_gmm.py:479-601) over every loader of `loaders`, on
+    report.reconstruction_report: a batch of eight fields ``(d, r, n, c, arousal, valence, r_density, n_density)`` is a supervised one (the
+    reference's ``is_vgmidi``), a batch of six an unsupervised one.  Per loader the reference's lines
+
+        CE: <CE_X>  <CE_R>  <CE_N>            (means over the batches)
+        Regularized: <l_r>  <l_n>             (means over the batches)
+        Acc: <x>  <r>  <n>  <a_r>  <a_n>      (sums divided by the number of samples, ``data_len``)
+
+    go to `log`.  The ``Adversarial:`` line is left out: upstream reads an undefined name there (and unpacks a 6-tuple as 8 before it, so
+    nobody has seen its output).  One deliberate difference: upstream divides the SUM of per-batch ``accuracy_score`` MEANS by ``data_len``
+    for the two posterior-class accuracies - a number that shrinks with the batch size; here they are per-sample means like the other three.
+    ``step`` is the reference's module-level step (it sets the KL weight inside the loss only).
+    -> one dict per loader: CE_X, CE_R, CE_N, l_r, l_n, kld_latent, kld_class, loss (means over the batches), acc_x, acc_r, acc_n, acc_y_r,
+    acc_y_n, topk_x (per-sample means), nll_per_token, n_tokens, n_samples, n_empty, n_batches."""
+    from .report import reconstruction_report
+    if trainer.dist is not None and trainer.dist.world > 1:
+        raise NotImplementedError("evaluation_phase: multi-rank reporting is not implemented - run it in a single process")
+    results = []
+    for dl in loaders:
+        tot = dict.fromkeys(("loss", "CE_X", "CE_R", "CE_N", "l_r", "l_n", "kld_latent", "kld_class", "acc_x", "acc_r", "acc_n", "acc_y_r", "acc_y_n",
+                             "topk_x", "nll_x", "n_tokens", "n_samples", "n_empty"), 0.0)
+        nb = 0
+        for x in dl:
+            if len(x) == 8:
+                d, r, n, c, a, _v, rd, nd = x
+            else:
+                (d, r, n, c, rd, nd), a = x, None
+            rep = reconstruction_report(trainer, (d, r, n, c, rd, nd), step=step, y_label=a, teacher_forced=teacher_forced)
+            for k, v in zip(("loss", "CE_X", "CE_R", "CE_N", "l_r", "l_n", "kld_latent", "kld_class"), rep["tuple8"]):
+                tot[k] += float(v)
+            for k in ("acc_x", "acc_r", "acc_n", "acc_y_r", "acc_y_n", "topk_x", "nll_x", "n_tokens", "n_samples", "n_empty"):
+                tot[k] += rep[k] or 0
+            nb += 1
+        if nb == 0:
+            raise RuntimeError("evaluation_phase: a loader yielded no batch")
+        ns = tot["n_samples"]
+        res = {k: tot[k] / nb for k in ("loss", "CE_X", "CE_R", "CE_N", "l_r", "l_n", "kld_latent", "kld_class")}
+        res.update({k: tot[k] / ns for k in ("acc_x", "acc_r", "acc_n", "acc_y_r", "acc_y_n")})
+        res.update(topk_x=tot["topk_x"] / ns if teacher_forced else None,
+                   nll_per_token=tot["nll_x"] / tot["n_tokens"] if teacher_forced and tot["n_tokens"] else None,
+                   n_tokens=int(tot["n_tokens"]), n_samples=int(ns), n_empty=int(tot["n_empty"]), n_batches=nb)
+        log("CE: {:.4}  {:.4}  {:.4}".format(res["CE_X"], res["CE_R"], res["CE_N"]))
+        log("Regularized: {:.4}  {:.4}".format(res["l_r"], res["l_n"]))
+        log("Acc: {:.4}  {:.4}  {:.4}  {:.4}  {:.4}".format(res["acc_x"], res["acc_r"], res["acc_n"], res["acc_y_r"], res["acc_y_n"]))
+        results.append(res)
+    return results
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

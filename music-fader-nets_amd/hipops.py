@@ -748,6 +748,51 @@ class HipOps:
         _lib.check(self.lib.fn_sweep_scores(_p(r), _p(n), _p(status), r.shape[0], r.shape[1], _p(values), int(which), float(r_std), float(n_std), _p(scores),
                                             _p(n_used), self.stream()), "fn_sweep_scores")
 
+    def token_score(self, x, stride_b, stride_t, B, T, V, target=None, pred=None, nll=None, rank=None):
+        """fn_token_score: row (b, t) = the V floats at x.data_ptr() + 4 (b stride_b + t stride_t), which must lie inside x's storage; target int32
+        (B, >= T) and the outputs pred, rank int32 / nll fp32 (B, >= T), each optional, with contiguous rows; the outputs share one row stride"""
+        _chk(x, name="x"), _chk(target, torch.int32, "target"), _chk(pred, torch.int32, "pred"), _chk(nll, name="nll"), _chk(rank, torch.int32, "rank")
+        B, T, V, stride_b, stride_t = int(B), int(T), int(V), int(stride_b), int(stride_t)
+        room = x.untyped_storage().nbytes() // 4 - x.storage_offset()
+        if min(B, T, V) < 1 or min(stride_b, stride_t) < 0 or (B - 1) * stride_b + (T - 1) * stride_t + V > room:
+            raise RuntimeError("token_score: rows of %d floats at strides (%d, %d) for B = %d, T = %d do not fit the %d floats behind x" % (V, stride_b, stride_t, B, T, room))
+        lds = set()
+        for t, nm in ((target, "target"), (pred, "pred"), (nll, "nll"), (rank, "rank")):
+            if t is None:
+                continue
+            if t.dim() != 2 or t.shape[0] != B or t.shape[1] < T or (t.shape[1] > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) < T):
+                raise RuntimeError("token_score: %s (%d, >= %d) with contiguous rows, got shape %s strides %s" % (nm, B, T, tuple(t.shape), t.stride()))
+            if nm != "target":
+                lds.add(t.stride(0) if B > 1 else max(t.shape[1], t.stride(0)))
+        if len(lds) != 1:
+            raise RuntimeError("token_score: at least one of pred, nll, rank, and one row stride for all of them (got %s)" % sorted(lds))
+        tgt_ld = 0 if target is None else (target.stride(0) if B > 1 else max(target.shape[1], target.stride(0)))
+        _lib.check(self.lib.fn_token_score(_p(x), stride_b, stride_t, B, T, V, _p(target), tgt_ld, _p(pred), _p(nll), _p(rank), lds.pop(), self.stream()),
+                   "fn_token_score")
+
+    def match_rows(self, pred, target, T, trim, lead, len_, correct, acc, status, nll=None, rank=None, topk=1, correct_topk=None, nll_sum=None):
+        """fn_match_rows: pred, target int32 (rows, >= T) with contiguous rows; nll fp32 / rank int32 (rows, >= T) sharing one row stride, or None;
+        lead, len_, correct, status, correct_topk int32 [rows], acc, nll_sum fp64 [rows]"""
+        rows, T = pred.shape[0], int(T)
+        ld = {}
+        for t, d, nm in ((pred, torch.int32, "pred"), (target, torch.int32, "target"), (nll, torch.float32, "nll"), (rank, torch.int32, "rank")):
+            _chk(t, d, nm)
+            if t is None:
+                continue
+            if t.dim() != 2 or t.shape[0] != rows or t.shape[1] < T or T < 1 or (t.shape[1] > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < T):
+                raise RuntimeError("match_rows: %s (%d, >= %d) with contiguous rows, got shape %s strides %s" % (nm, rows, T, tuple(t.shape), t.stride()))
+            ld[nm] = t.stride(0) if rows > 1 else max(t.shape[1], t.stride(0))
+        if nll is not None and rank is not None and ld["nll"] != ld["rank"]:
+            raise RuntimeError("match_rows: nll and rank share one row stride, got %d and %d" % (ld["nll"], ld["rank"]))
+        for t, d, nm in ((lead, torch.int32, "lead"), (len_, torch.int32, "len"), (correct, torch.int32, "correct"), (status, torch.int32, "status"),
+                         (correct_topk, torch.int32, "correct_topk"), (acc, torch.float64, "acc"), (nll_sum, torch.float64, "nll_sum")):
+            _dense(t, d, nm)
+            if t is not None and t.numel() != rows:
+                raise RuntimeError("match_rows: %s for %d rows" % (nm, rows))
+        _lib.check(self.lib.fn_match_rows(_p(pred), ld["pred"], _p(target), ld["target"], rows, T, 1 if trim else 0, _p(nll), _p(rank),
+                                          ld.get("nll", ld.get("rank", 0)), int(topk), _p(lead), _p(len_), _p(correct), _p(correct_topk), _p(acc),
+                                          _p(nll_sum), _p(status), self.stream()), "fn_match_rows")
+
     def time_logsoftmax(self, logits, logp_bt=None, target=None, nll_bc=None, grad_scale=0.0, dlogits=None):
         _dense(logits, name="logits"), _dense(logp_bt, name="logp_bt"), _dense(target, torch.int32, "target")
         _dense(nll_bc, name="nll_bc"), _dense(dlogits, name="dlogits")

@@ -166,17 +166,23 @@ def main(argv=None):
                          "bf16 pieces, six partial products on the bf16 MFMA, fp32 accumulation (as accurate as the fp32 chains against float64). "
                          "Default: the package default (arith.default())")
     ap.add_argument("--bf16x6", action="store_true", help="same as --arith bf16x6")
+    ap.add_argument("--evaluate", action="store_true",
+                    help="after training, the reference's evaluation_phase() over the four loaders: CE / Regularized / Acc lines (--model gmm, one process)")
     opts = ap.parse_args(argv)
 
     import importlib
     pkg = importlib.import_module(__package__)
     from . import parallel
-    from .epochs import training_phase, training_phase_v2
+    from .epochs import evaluation_phase, training_phase, training_phase_v2
     args = read_config(opts.config, opts.model)
+    if opts.evaluate and opts.model != "gmm":
+        raise SystemExit("train: --evaluate is the GM-VAE trainer's evaluation_phase (--model gmm)")
     if not torch.cuda.is_available():
         raise SystemExit("train: needs an MI355X - the HIP path has no CPU fallback")
     ctx, local = parallel.init_from_env()
     rank, world = (0, 1) if ctx is None else (ctx.rank, ctx.world)
+    if opts.evaluate and world > 1:
+        raise SystemExit("train: --evaluate is single-process (evaluation_phase does not reduce its sums over ranks)")
     if opts.model == "glsr" and world > 1:
         raise SystemExit("train: --model glsr is single-process (the reference's rhythm-density walk reads sample 0 of the batch for every row)")
     dev = torch.device("cuda", local)
@@ -218,6 +224,9 @@ def main(argv=None):
         say()
         step = training_phase(trainer, 0, n_epochs, dls["vgm_train"], dls["vgm_val"], dls["train"], dls["val"], save_path,
                               name=args["name"], log=say, save=rank == 0)    # every rank runs the schedule, rank 0 writes the checkpoints
+        if opts.evaluate:                                               # trainer_gmm.py:603-614
+            say("Evaluate")
+            evaluation_phase(trainer, [dls[k] for k in ("train", "val", "vgm_train", "vgm_val")], log=say, step=step)
     else:
         say("Train / Validation / Test")                                # trainer.py:74-75
         say(sizes["train"], sizes["val"], sizes["test"])

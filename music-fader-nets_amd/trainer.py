@@ -236,7 +236,10 @@ class GMVAETrainer:
         """device partial sums -> the reference's 8 numbers (ONE D2H copy; the reference does 8 .item() calls, :257)."""
         if self.dist is not None:
             self.dist.all_reduce_sum(self.stats)
-        s = self.stats.tolist()
+        return self._terms8(self.stats.tolist(), beta0, Bg, supervised)
+
+    def _terms8(self, s, beta0, Bg, supervised):
+        """the host copy `s` of the partial sums -> the reference's 8 numbers"""
         # the host is synchronised here anyway: a weight-stationary scan whose workgroups gave up waiting (bounded spins) has left
         # garbage behind - fail loudly instead of returning it
         check = getattr(self.model.engine().ops, "gru_sync_error", None)
