@@ -702,6 +702,36 @@ int fn_sweep_scores(const float* r, const float* n, const int32_t* status, int S
  *   One wavefront per row; static LDS 8.5 KB (1024 event keys of tick:23 | kind:1 | pitch:7 | k:10 in 64 bits, 512 bins).
  *   NULL spans / params_dev / tokens / n_tokens / n_kept / status, or NULL notes with n_total > 0: FN_E_NULL; rows < 1, steps outside
  *   [1, FN_ATTR_MAX_STEPS], tok_ld < steps, n_total < 0: FN_E_SHAPE; both before any launch.
+ *
+ * fn_notes_stitch (transfer.py): S windows of V pieces back into V note lists - the step from decoded windows to a piece.  OURS; the
+ * reference stops at one window.  dec [S*V] rows of FnNote at a stride of dec_rs notes, row = j*V + v, dec_ld slots of a row in use,
+ * with dec_n and dec_end [S*V] (n_notes and t_end of fn_notes_from_tokens); src [n_total] FnNote and spans [S] FnNoteSpan as the
+ * tokeniser takes them; mode [S*V] int32 -> out [V][out_ld] FnNote, win_first [V][S + 1], out_n, status [V].  Everything but the
+ * sizes is read from DEVICE memory.  Per window j of piece v, with spans[j] = (first, count, t_lo, t_hi), all arithmetic in 64 bits:
+ *   1. W = t_hi - t_lo clamped to [0, FN_NOTES_MAX_TICK].
+ *   2. mode 0, the source passes through: the notes are src[first + k], 0 <= k < count; a k with first + k outside [0, n_total) is no
+ *      note; count is NOT capped at FN_NOTES_MAX.  A note is kept iff t_lo <= t0 < t_lo + W, and is written unchanged: absolute
+ *      times, t1 not cut.
+ *   3. mode 1, decoded and clipped: the notes are dec[row][k], k < dec_n[row] clamped to [0, dec_ld].  A note is kept iff
+ *      0 <= t0 < W, and is written as (t_lo + t0, t_lo + min(t1, W), pitch, vel).
+ *   4. mode 2, decoded and fitted: when dec_end[row] > W, first t0 <- floor(t0 * W / dec_end) and t1 <- max(t0 + 1, floor(t1 * W /
+ *      dec_end)) (floor towards minus infinity; the products reach 2^53), then clause 3; otherwise mode 2 is clause 3.
+ *   5. Any other mode: the window holds nothing.
+ *   6. In every mode a note whose written t1 <= t0 is dropped, so is one with pitch outside [0, 128) and one whose written times
+ *      leave int32; vel is clamped to [1, 127].
+ *   7. out[v] holds the kept notes of window 0, then of window 1, ...; inside a window the input order.  Nothing is sorted: the result
+ *      ascends by t0 when the spans are ascending and disjoint and the windows' notes ascend, which is the caller's affair.
+ *   8. win_first[v][j] is the number of kept notes in front of window j, win_first[v][S] the total: true counts, not clamped to out_ld.
+ *      out_n[v] = min(total, out_ld); the first out_n notes of the order are written, entries [out_n, out_ld) are zeroed, nothing is
+ *      written behind out_ld.  status FN_NOTES_OVERFLOW if total > out_ld, else FN_NOTES_EMPTY if total == 0, else 0.
+ *   Three launches, ordered by their boundaries alone (no workgroup waits for another): one wavefront per (window, piece) counts its
+ *   kept notes with a ballot into win_first; one wavefront per piece turns the counts into offsets, 256 windows a pass; one wavefront
+ *   per (window, piece) repeats the walk and writes every kept note at offset + the lanes' prefix popcount as one 16-byte store,
+ *   and zeroes its share of the tail.  No LDS.
+ *   NULL dec / dec_n / dec_end / spans / mode / out / win_first / out_n / status, or NULL src with n_total > 0: FN_E_NULL; S < 1, V < 1,
+ *   dec_ld < 1, dec_rs < dec_ld, out_ld < 1, n_total < 0: FN_E_SHAPE; dec, src or out not 16-byte aligned: FN_E_ALIGN; S >
+ *   FN_STITCH_MAX_S, V > FN_STITCH_MAX_V, out_ld > FN_STITCH_MAX_OUT, or S * max(n_total, dec_ld) >= 2^31 (a count could leave
+ *   int32): FN_E_UNSUPPORTED; all before any launch.
  * ------------------------------------------------------------------------------------------ */
 #define FN_NOTES_MAX 512
 #define FN_NOTES_MAX_TICK (1 << 22)
@@ -721,6 +751,12 @@ int fn_notes_from_tokens(const int32_t* tokens, int tok_ld, int rows, int steps,
                          int32_t* n_notes, int32_t* t_end, int32_t* status, void* stream);
 int fn_tokens_from_notes(const FnNote* notes, int n_total, const FnNoteSpan* spans, int rows, const FnNoteParams* params_dev, int32_t* tokens,
                          int tok_ld, int steps, int32_t* n_tokens, int32_t* n_kept, int32_t* status, void* stream);
+#define FN_STITCH_MAX_S (1 << 16)
+#define FN_STITCH_MAX_V 64
+#define FN_STITCH_MAX_OUT (1 << 24)
+int fn_notes_stitch(const FnNote* dec, int dec_rs, int dec_ld, const int32_t* dec_n, const int32_t* dec_end, const FnNote* src, int n_total,
+                    const FnNoteSpan* spans, int S, int V, const int32_t* mode, FnNote* out, int out_ld, int32_t* win_first, int32_t* out_n,
+                    int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Reconstruction report (report.py, epochs.evaluation_phase): what the reference's evaluation_phase() computes behind its loss terms

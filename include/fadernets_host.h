@@ -69,7 +69,11 @@ int fn_constrain_apply_host(float* logits, int rows, int V, int ld, int step, co
 int fn_constrain_advance_host(int32_t* tok_io, int tok_ld, int rows, int V, const FnConstrainParams* params, const float* logits, int ld,
                               const int32_t* fallback, int fb_ld, const uint32_t* held_in, uint32_t* held_out, int32_t* fixed,
                               void* stream);                                                              /* fn_constrain_advance */
-size_t fn_frag_floats_host(int rows, int K);                                                             /* fn_frag_floats */
+/* windows -> pieces */
+int fn_notes_stitch_host(const FnNote* dec, int dec_rs, int dec_ld, const int32_t* dec_n, const int32_t* dec_end, const FnNote* src, int n_total,
+                         const FnNoteSpan* spans, int S, int V, const int32_t* mode, FnNote* out, int out_ld, int32_t* win_first, int32_t* out_n,
+                         int32_t* status, void* stream);                                                 /* fn_notes_stitch */
+size_t fn_frag_floats_host(int rows, int K);                                                            /* fn_frag_floats */
 size_t fn_gru_gates_floats_host(int B, int H);                                                           /* fn_gru_gates_floats */
 
 #ifdef __cplusplus

@@ -42,6 +42,7 @@ FN_ATTR_MAX_STEPS, FN_ATTR_MAX_CELLS, FN_ATTR_MAX_SAMPLES = 1024, 2048, 4096
 FN_ATTR_EMPTY, FN_ATTR_OVERFLOW = 1, 2
 FN_NOTES_MAX, FN_NOTES_MAX_TICK = 512, 1 << 22
 FN_NOTES_EMPTY, FN_NOTES_OVERFLOW = 1, 2
+FN_STITCH_MAX_S, FN_STITCH_MAX_V, FN_STITCH_MAX_OUT = 1 << 16, 64, 1 << 24
 FN_MATCH_EMPTY = 1
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
@@ -191,6 +192,7 @@ SIGNATURES = {
     "fn_sweep_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp]),
     "fn_notes_from_tokens": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "fn_tokens_from_notes": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "fn_notes_stitch": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "fn_token_score": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]),
     "fn_match_rows": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),

@@ -10,6 +10,7 @@
 #include "../../../include/fadernets_host.h"
 #include "sample_host.h"
 #include "constrain_host.h"
+#include "notes_host.h"
 
 namespace {
 
@@ -573,6 +574,12 @@ int fn_constrain_apply_host(float* logits, int rows, int V, int ld, int step, co
 int fn_constrain_advance_host(int32_t* tok_io, int tok_ld, int rows, int V, const FnConstrainParams* params, const float* logits, int ld,
                               const int32_t* fallback, int fb_ld, const uint32_t* held_in, uint32_t* held_out, int32_t* fixed, void*) {
     return fn_constrain_host::constrain_advance(tok_io, tok_ld, rows, V, params, logits, ld, fallback, fb_ld, held_in, held_out, fixed);
+}
+
+int fn_notes_stitch_host(const FnNote* dec, int dec_rs, int dec_ld, const int32_t* dec_n, const int32_t* dec_end, const FnNote* src, int n_total,
+                         const FnNoteSpan* spans, int S, int V, const int32_t* mode, FnNote* out, int out_ld, int32_t* win_first, int32_t* out_n,
+                         int32_t* status, void*) {
+    return fn_notes_host::notes_stitch(dec, dec_rs, dec_ld, dec_n, dec_end, src, n_total, spans, S, V, mode, out, out_ld, win_first, out_n, status);
 }
 
 size_t fn_decode_ws_bytes_host(int B, int H, int) { return (size_t)4 * B * H * sizeof(float) + 16; }

@@ -1,5 +1,5 @@
-// notes_host.h - fn_notes_from_tokens / fn_tokens_from_notes in plain C++ (include/fadernets.h has the definition these follow clause by clause, not
-// the kernels).  No dependencies: the stand-alone notes_check.cpp includes it.  Integers only.
+// notes_host.h - fn_notes_from_tokens / fn_tokens_from_notes / fn_notes_stitch in plain C++ (include/fadernets.h has the definition these follow clause
+// by clause, not the kernels).  No dependencies: the stand-alone notes_check.cpp and stitch_check.cpp include it.  Integers only.
 #ifndef FADERNETS_NOTES_HOST_H
 #define FADERNETS_NOTES_HOST_H
 
@@ -122,6 +122,57 @@ inline int tokens_from_notes(const FnNote* notes, int n_total, const FnNoteSpan*
         for (int i = 0; i < steps; ++i) row[i] = i < (int)stream.size() ? stream[(size_t)i] : c.pad;          // 7
         n_tokens[r] = (int32_t)length, n_kept[r] = kept;
         status[r] = length > steps ? FN_NOTES_OVERFLOW : kept == 0 ? FN_NOTES_EMPTY : 0;                      // 8
+    }
+    return FN_OK;
+}
+
+// floor(a / b) for b > 0
+inline int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+inline int notes_stitch(const FnNote* dec, int dec_rs, int dec_ld, const int32_t* dec_n, const int32_t* dec_end, const FnNote* src, int n_total,
+                        const FnNoteSpan* spans, int S, int V, const int32_t* mode, FnNote* out, int out_ld, int32_t* win_first, int32_t* out_n,
+                        int32_t* status) {
+    if (!dec || !dec_n || !dec_end || !spans || !mode || !out || !win_first || !out_n || !status || (!src && n_total > 0)) return FN_E_NULL;
+    if (S < 1 || V < 1 || dec_ld < 1 || dec_rs < dec_ld || out_ld < 1 || n_total < 0) return FN_E_SHAPE;
+    if (((uintptr_t)dec | (uintptr_t)src | (uintptr_t)out) & 15u) return FN_E_ALIGN;
+    if (S > FN_STITCH_MAX_S || V > FN_STITCH_MAX_V || out_ld > FN_STITCH_MAX_OUT || (int64_t)S * std::max(n_total, dec_ld) > INT32_MAX)
+        return FN_E_UNSUPPORTED;
+    for (int v = 0; v < V; ++v) {
+        std::vector<FnNote> piece;
+        int32_t* first_of = win_first + (int64_t)v * (S + 1);
+        for (int j = 0; j < S; ++j) {
+            first_of[j] = (int32_t)piece.size();                                                              // 8
+            const FnNoteSpan sp = spans[j];
+            const int64_t row = (int64_t)j * V + v, t_lo = sp.t_lo;
+            const int64_t W = std::min<int64_t>(std::max<int64_t>((int64_t)sp.t_hi - t_lo, 0), FN_NOTES_MAX_TICK);   // 1
+            auto put = [&](int64_t t0, int64_t t1, int pitch, int vel) {                                      // 6
+                if (t1 <= t0 || pitch < 0 || pitch >= 128 || t0 < INT32_MIN || t0 > INT32_MAX || t1 < INT32_MIN || t1 > INT32_MAX) return;
+                piece.push_back(FnNote{(int32_t)t0, (int32_t)t1, pitch, clampi(vel, 1, 127)});
+            };
+            if (mode[row] == 0) {                                                                             // 2
+                for (int64_t k = std::max<int64_t>(0, -(int64_t)sp.first); k < sp.count; ++k) {          // the k before are in front of the array
+                    const int64_t at = (int64_t)sp.first + k;
+                    if (at >= n_total) break;
+                    const FnNote q = src[at];
+                    if (q.t0 >= t_lo && q.t0 < t_lo + W) put(q.t0, q.t1, q.pitch, q.vel);
+                }
+            } else if (mode[row] == 1 || mode[row] == 2) {                                                    // 3, 4
+                const int n = clampi(dec_n[row], 0, dec_ld);
+                const int64_t end = dec_end[row];
+                for (int k = 0; k < n; ++k) {
+                    const FnNote q = dec[row * dec_rs + k];
+                    int64_t t0 = q.t0, t1 = q.t1;
+                    if (mode[row] == 2 && end > W) t0 = floor_div(t0 * W, end), t1 = std::max(t0 + 1, floor_div(t1 * W, end));
+                    if (t0 >= 0 && t0 < W) put(t_lo + t0, t_lo + std::min(t1, W), q.pitch, q.vel);
+                }
+            }                                                                                                 // 5: nothing
+        }
+        const int64_t total = (int64_t)piece.size();
+        first_of[S] = (int32_t)total;
+        FnNote* row_out = out + (int64_t)v * out_ld;
+        for (int64_t i = 0; i < out_ld; ++i) row_out[i] = i < total ? piece[(size_t)i] : FnNote{0, 0, 0, 0};
+        out_n[v] = (int32_t)std::min<int64_t>(total, out_ld);
+        status[v] = total > out_ld ? FN_NOTES_OVERFLOW : total == 0 ? FN_NOTES_EMPTY : 0;
     }
     return FN_OK;
 }

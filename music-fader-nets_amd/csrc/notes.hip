@@ -1,5 +1,6 @@
 // notes.hip - event tokens <-> timed notes (notes.py, midi.py): fn_notes_from_tokens publishes the notes that event_raster_kernel (attributes.hip)
-// keeps in registers, with velocity; fn_tokens_from_notes is the tokeniser.  include/fadernets.h has the definition.
+// keeps in registers, with velocity; fn_tokens_from_notes is the tokeniser; fn_notes_stitch joins decoded windows into pieces (transfer.py).
+// include/fadernets.h has the definitions.
 // Plain HIP: no inline assembly, no atomics, nothing between workgroups; one wavefront per row, every lane reaches every barrier.
 #include "common.h"
 
@@ -250,6 +251,118 @@ __global__ __launch_bounds__(64) void tokens_from_notes_kernel(const FnNote* __r
     if (lane == 0) n_tokens[r] = (int32_t)total, n_kept[r] = kept, status[r] = total > (uint32_t)steps ? FN_NOTES_OVERFLOW : kept == 0 ? FN_NOTES_EMPTY : 0;
 }
 
+// floor(a / b) for b > 0
+__device__ __forceinline__ long floor_div(long a, long b) {
+    const long q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// One window of one piece as fn_notes_stitch walks it: where its notes come from, how many there are, and what clauses 1 to 6 make of note k.
+// Everything that steers an address is clamped here: `n` notes starting at `base`, all inside src [n_total] or inside the dec_ld slots of the row.
+struct StitchWindow {
+    const FnNote* base;
+    long t_lo, W, end;          // end: dec_end where mode 2 fits the times, 0 where it does not
+    int n, mode;
+};
+
+__device__ __forceinline__ StitchWindow stitch_window(const FnNote* __restrict__ dec, int dec_rs, int dec_ld, const int32_t* __restrict__ dec_n,
+                                                      const int32_t* __restrict__ dec_end, const FnNote* __restrict__ src, int n_total,
+                                                      const FnNoteSpan* __restrict__ spans, const int32_t* __restrict__ mode, long j, long row) {
+    const FnNoteSpan sp = spans[j];
+    StitchWindow w;
+    w.t_lo = sp.t_lo, w.W = min(max((long)sp.t_hi - (long)sp.t_lo, 0l), (long)FN_NOTES_MAX_TICK);
+    w.mode = mode[row], w.end = 0, w.n = 0, w.base = src;
+    if (w.mode == 0) {
+        const long lo = max(0l, -(long)sp.first), hi = min((long)sp.count, (long)n_total - (long)sp.first);          // the k with first + k in [0, n_total)
+        if (hi > lo) w.n = (int)(hi - lo), w.base = src + ((long)sp.first + lo);
+    } else if (w.mode == 1 || w.mode == 2) {
+        w.n = min(max(dec_n[row], 0), dec_ld), w.base = dec + row * dec_rs;
+        const long e = dec_end[row];
+        if (w.mode == 2 && e > w.W) w.end = e;
+    }
+    return w;
+}
+
+// note k < w.n of the window -> is it kept, and as what
+__device__ __forceinline__ bool stitch_note(const StitchWindow& w, long k, int4& q) {
+    q = *reinterpret_cast<const int4*>(w.base + k);          // (t0, t1, pitch, vel)
+    long t0 = q.x, t1 = q.y;
+    if (w.mode == 0) {
+        if (!(t0 >= w.t_lo && t0 < w.t_lo + w.W)) return false;
+    } else {
+        if (w.end > 0) t0 = floor_div(t0 * w.W, w.end), t1 = max(t0 + 1, floor_div(t1 * w.W, w.end));
+        if (!(t0 >= 0 && t0 < w.W)) return false;
+        t0 += w.t_lo, t1 = w.t_lo + min(t1, w.W);
+    }
+    if (t1 <= t0 || q.z < 0 || q.z >= 128 || t0 < INT32_MIN || t1 > INT32_MAX) return false;          // t0 < t1: the two bounds cover both times
+    q.x = (int)t0, q.y = (int)t1, q.w = min(max(q.w, 1), 127);
+    return true;
+}
+
+// One wavefront per (window j, piece v), 64 notes of the window at a time.  WRITE false: the count of kept notes goes to win_first[v][j].
+// WRITE true (after stitch_scan_kernel): the kept notes go to out[v] from win_first[v][j] on, in input order - a lane's place is the number of kept
+// notes in the lanes below it - and the window zeroes its share of [total, out_ld): element total + 64 * j + lane and every 64 * S-th behind it.
+template <bool WRITE>
+__global__ __launch_bounds__(64) void stitch_walk_kernel(const FnNote* __restrict__ dec, int dec_rs, int dec_ld, const int32_t* __restrict__ dec_n,
+                                                         const int32_t* __restrict__ dec_end, const FnNote* __restrict__ src, int n_total,
+                                                         const FnNoteSpan* __restrict__ spans, int S, int V, const int32_t* __restrict__ mode,
+                                                         FnNote* __restrict__ out, int out_ld, int32_t* __restrict__ win_first) {
+    const int lane = threadIdx.x;
+    const long j = blockIdx.x, v = blockIdx.y;
+    const StitchWindow w = stitch_window(dec, dec_rs, dec_ld, dec_n, dec_end, src, n_total, spans, mode, j, j * V + v);
+    int32_t* counts = win_first + v * ((long)S + 1);
+    FnNote* piece = out + v * (long)out_ld;
+    long at = WRITE ? counts[j] : 0;                    // < 2^31: the entry point refuses sizes at which a count could leave int32
+    for (long base = 0; base < w.n; base += 64) {          // long: n reaches 2^31 - 1 when S is 1
+        const long k = base + lane;
+        int4 q = make_int4(0, 0, 0, 0);
+        const bool keep = k < w.n && stitch_note(w, k, q);
+        const unsigned long long m = __ballot(keep);
+        if (WRITE && keep) {
+            const long pos = at + __popcll(m & ((1ull << lane) - 1ull));
+            if (pos < out_ld) *reinterpret_cast<int4*>(piece + pos) = q;
+        }
+        at += __popcll(m);
+    }
+    if (WRITE) {
+        for (long i = (long)counts[S] + 64 * j + lane; i < out_ld; i += 64l * S) *reinterpret_cast<int4*>(piece + i) = make_int4(0, 0, 0, 0);
+    } else if (lane == 0) {
+        counts[j] = (int32_t)at;
+    }
+}
+
+constexpr int STITCH_SCAN_PASS = 256;                   // windows per pass of stitch_scan_kernel: 4 per lane
+
+// One wavefront per piece: win_first[v][0 .. S) from counts to the counts in front (an exclusive scan, in place: a lane reads and writes its own four
+// entries of a pass), win_first[v][S] the total; out_n and status of the piece.
+__global__ __launch_bounds__(64) void stitch_scan_kernel(int32_t* __restrict__ win_first, int S, int out_ld, int32_t* __restrict__ out_n,
+                                                         int32_t* __restrict__ status) {
+    const int lane = threadIdx.x;
+    const long v = blockIdx.x;
+    int32_t* row = win_first + v * ((long)S + 1);
+    int carry = 0;
+    for (int base = 0; base < S; base += STITCH_SCAN_PASS) {
+        const int i0 = base + 4 * lane;
+        int c[4], sum = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c[q] = i0 + q < S ? row[i0 + q] : 0, sum += c[q];
+        int x = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        int before = carry + x - sum;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (i0 + q < S) row[i0 + q] = before;
+            before += c[q];
+        }
+        carry += __shfl(x, 63, 64);
+    }
+    if (lane == 0) row[S] = carry, out_n[v] = min(carry, out_ld), status[v] = carry > out_ld ? FN_NOTES_OVERFLOW : carry == 0 ? FN_NOTES_EMPTY : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -273,6 +386,26 @@ int fn_tokens_from_notes(const FnNote* notes, int n_total, const FnNoteSpan* spa
     if (rows < 1 || steps < 1 || steps > FN_ATTR_MAX_STEPS || tok_ld < steps || n_total < 0) return FN_E_SHAPE;
     hipLaunchKernelGGL(tokens_from_notes_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, notes, n_total, spans, params_dev, tokens,
                        tok_ld, steps, n_tokens, n_kept, status);
+    FN_CHECK_LAUNCH();
+    return FN_OK;
+}
+
+int fn_notes_stitch(const FnNote* dec, int dec_rs, int dec_ld, const int32_t* dec_n, const int32_t* dec_end, const FnNote* src, int n_total,
+                    const FnNoteSpan* spans, int S, int V, const int32_t* mode, FnNote* out, int out_ld, int32_t* win_first, int32_t* out_n,
+                    int32_t* status, void* stream) {
+    if (!dec || !dec_n || !dec_end || !spans || !mode || !out || !win_first || !out_n || !status || (!src && n_total > 0)) return FN_E_NULL;
+    if (S < 1 || V < 1 || dec_ld < 1 || dec_rs < dec_ld || out_ld < 1 || n_total < 0) return FN_E_SHAPE;
+    if (((uintptr_t)dec | (uintptr_t)src | (uintptr_t)out) & 15u) return FN_E_ALIGN;
+    if (S > FN_STITCH_MAX_S || V > FN_STITCH_MAX_V || out_ld > FN_STITCH_MAX_OUT || (int64_t)S * (n_total > dec_ld ? n_total : dec_ld) > INT32_MAX)
+        return FN_E_UNSUPPORTED;
+    const dim3 grid((unsigned)S, (unsigned)V);
+    hipLaunchKernelGGL(stitch_walk_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, dec, dec_rs, dec_ld, dec_n, dec_end, src, n_total, spans, S, V,
+                       mode, out, out_ld, win_first);
+    FN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(stitch_scan_kernel, dim3((unsigned)V), dim3(64), 0, (hipStream_t)stream, win_first, S, out_ld, out_n, status);
+    FN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(stitch_walk_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, dec, dec_rs, dec_ld, dec_n, dec_end, src, n_total, spans, S, V,
+                       mode, out, out_ld, win_first);
     FN_CHECK_LAUNCH();
     return FN_OK;
 }

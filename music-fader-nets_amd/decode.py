@@ -552,6 +552,61 @@ def clean_output(out):
     return recon
 
 
+def _check_beam(steps, prompt, sample, beam):
+    if beam is not None:
+        if sample is not None or prompt is not None:
+            raise ValueError("beam goes with neither sample nor prompt")
+        unknown = set(beam) - {"width", "eos", "length_penalty"}
+        if unknown:
+            raise ValueError("beam: keys among width, eos, length_penalty; got %s" % sorted(unknown, key=str))
+        _beam_args(steps, beam.get("width", 4), beam.get("eos"), beam.get("length_penalty", 0.0))
+
+
+def _decode_rows(model, z, steps, prompt=None, sample=None, beam=None, constraints=None):
+    """the decode fader_sweep's keywords select, over the rows of z -> tokens (rows, steps) int32"""
+    rows = z.shape[0]
+    pr = None if prompt is None else (prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))).reshape(1, -1)
+    if beam is not None:
+        return beam_decode(model, z, steps, constraints=constraints, **beam)[0][:, 0].contiguous()
+    if sample is not None:
+        unknown = set(sample) - {"temperature", "top_k", "top_p", "seed", "offset"}
+        if unknown:
+            raise ValueError("sample: keys among temperature, top_k, top_p, seed, offset; got %s" % sorted(unknown, key=str))
+        return sample_decode(model, z, steps, want_logp=False, prompt=None if pr is None else pr.expand(rows, pr.shape[1]), constraints=constraints,
+                             **sample)[1]
+    if prompt is None:
+        return greedy_decode(model, z, steps, want_logp=False, constraints=constraints)[1]
+    return continue_from(model, z, pr.expand(rows, pr.shape[1]), steps, want_logp=False, constraints=constraints)[1]
+
+
+def fader_latents(model, dis_r, dis_n, amounts, eps=None, which="r", mode="set"):
+    """The latent arithmetic of fader_sweep for an (n, V) matrix of amounts - one per (sample, value) pair, on the posteriors' device:
+      mode="set":   z_which[i, v, 0] = amounts[i, v];   mode="shift": z_which[i, v] += amounts[i, v] * (mu_lookup[1] - mu_lookup[0])
+    eps as fader_sweep takes it; None = drawn here (r first, then n).
+    -> (zr, zn (n, V, Z) fresh tensors, z0 (n,) or (n, V): the value of z_which[:, 0] before the change; which="both": z_r's)"""
+    n, Z = dis_r.mean.shape
+    V = amounts.shape[1]
+    dev = dis_r.mean.device
+    if eps is None:
+        eps = (torch.randn(n, Z), torch.randn(n, Z))      # repar() of test_class.py:53-56 draws r first, then n
+    er, en = (e.to(dev).float() for e in eps)
+    per_value = er.dim() == 3
+    if not per_value:
+        er, en = er.unsqueeze(1).expand(n, V, Z), en.unsqueeze(1).expand(n, V, Z)
+    zr = dis_r.mean.unsqueeze(1) + dis_r.stddev.unsqueeze(1) * er          # (n, V, Z), fresh tensors
+    zn = dis_n.mean.unsqueeze(1) + dis_n.stddev.unsqueeze(1) * en
+    z0 = (zn if which == "n" else zr)[:, :, 0].clone()
+    if not per_value:
+        z0 = z0[:, 0]
+    if mode == "set":
+        (zr if which == "r" else zn)[:, :, 0] = amounts
+    else:
+        for tgt, lk, on in ((zr, model.mu_r_lookup, which in ("r", "both")), (zn, model.mu_n_lookup, which in ("n", "both"))):
+            if on:
+                tgt += amounts.unsqueeze(2) * (lk.weight.data[1] - lk.weight.data[0]).view(1, 1, Z)
+    return zr, zn, z0
+
+
 @torch.no_grad()
 def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="set", prompt=None, sample=None, beam=None, constraints=None):
     """Batched RhythmEvaluator.shift / NoteEvaluator.shift (test_class.py:233-254, :282-303) and the notebook's
@@ -569,53 +624,17 @@ def fader_sweep(model, x, chroma, values, steps=100, which="r", eps=None, mode="
     Returns (tokens (n, V, steps) int32, z0 (n,) or (n, V): the value of z_which[:, 0] before the change; which="both": z_r's)."""
     if which not in ("r", "n", "both") or mode not in ("set", "shift") or (which == "both" and mode == "set"):
         raise ValueError("which in {r, n, both}, mode in {set, shift}; 'both' only with mode='shift'")
-    if beam is not None:
-        if sample is not None or prompt is not None:
-            raise ValueError("beam goes with neither sample nor prompt")
-        unknown = set(beam) - {"width", "eos", "length_penalty"}
-        if unknown:
-            raise ValueError("beam: keys among width, eos, length_penalty; got %s" % sorted(unknown, key=str))
-        _beam_args(steps, beam.get("width", 4), beam.get("eos"), beam.get("length_penalty", 0.0))
+    _check_beam(steps, prompt, sample, beam)
     was_training = model.training
     model.eval()
     try:
         dis_r, dis_n = model.encode(x)
-        n, Z = dis_r.mean.shape
-        V = len(values)
+        n, V = dis_r.mean.shape[0], len(values)
         dev = dis_r.mean.device
-        if eps is None:
-            eps = (torch.randn(n, Z), torch.randn(n, Z))      # repar() of test_class.py:53-56 draws r first, then n
-        er, en = (e.to(dev).float() for e in eps)
-        per_value = er.dim() == 3
-        if not per_value:
-            er, en = er.unsqueeze(1).expand(n, V, Z), en.unsqueeze(1).expand(n, V, Z)
-        zr = dis_r.mean.unsqueeze(1) + dis_r.stddev.unsqueeze(1) * er          # (n, V, Z), fresh tensors
-        zn = dis_n.mean.unsqueeze(1) + dis_n.stddev.unsqueeze(1) * en
-        z0 = (zn if which == "n" else zr)[:, :, 0].clone()
-        if not per_value:
-            z0 = z0[:, 0]
         vals = torch.as_tensor(values, dtype=torch.float32, device=dev)
-        if mode == "set":
-            (zr if which == "r" else zn)[:, :, 0] = vals
-        else:
-            for tgt, lk, on in ((zr, model.mu_r_lookup, which in ("r", "both")), (zn, model.mu_n_lookup, which in ("n", "both"))):
-                if on:
-                    tgt += vals.view(1, V, 1) * (lk.weight.data[1] - lk.weight.data[0]).view(1, 1, Z)
+        zr, zn, z0 = fader_latents(model, dis_r, dis_n, vals.view(1, V).expand(n, V), eps, which, mode)
         c = chroma.float().to(dev).unsqueeze(1).expand(n, V, chroma.shape[-1])
         z = torch.cat([zr, zn, c], dim=2).reshape(n * V, -1)
-        pr = None if prompt is None else (prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))).reshape(1, -1)
-        if beam is not None:
-            tok = beam_decode(model, z, steps, constraints=constraints, **beam)[0][:, 0].contiguous()
-        elif sample is not None:
-            unknown = set(sample) - {"temperature", "top_k", "top_p", "seed", "offset"}
-            if unknown:
-                raise ValueError("sample: keys among temperature, top_k, top_p, seed, offset; got %s" % sorted(unknown, key=str))
-            tok = sample_decode(model, z, steps, want_logp=False, prompt=None if pr is None else pr.expand(n * V, pr.shape[1]), constraints=constraints,
-                                **sample)[1]
-        elif prompt is None:
-            tok = greedy_decode(model, z, steps, want_logp=False, constraints=constraints)[1]
-        else:
-            tok = continue_from(model, z, pr.expand(n * V, pr.shape[1]), steps, want_logp=False, constraints=constraints)[1]
-        return tok.view(n, V, steps), z0
+        return _decode_rows(model, z, steps, prompt, sample, beam, constraints).view(n, V, steps), z0
     finally:
         model.train(was_training)

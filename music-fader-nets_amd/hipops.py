@@ -738,6 +738,28 @@ class HipOps:
         _lib.check(self.lib.fn_tokens_from_notes(_p(notes) if notes.shape[0] else None, notes.shape[0], _p(spans), rows, _p(params), _p(tokens), ld, int(steps),
                                                  _p(n_tokens), _p(n_kept), _p(status), self.stream()), "fn_tokens_from_notes")
 
+    def notes_stitch(self, dec, dec_ld, dec_n, dec_end, src, spans, mode, out, win_first, out_n, status):
+        """fn_notes_stitch: dec int32 [S*V][>= dec_ld][4] (any row stride that is a multiple of 4 words; row = j*V + v), dec_n, dec_end, mode contiguous
+        int32 [S*V]; src contiguous int32 [n_total][4], spans contiguous int32 [S][4]; out contiguous int32 [V][out_ld][4], win_first [V][S + 1], out_n and
+        status [V] are written"""
+        _chk(dec, torch.int32, "dec"), _dense(src, torch.int32, "src"), _dense(spans, torch.int32, "spans"), _dense(out, torch.int32, "out")
+        if spans.dim() != 2 or spans.shape[1] != 4 or src.dim() != 2 or src.shape[1] != 4 or out.dim() != 3 or out.shape[2] != 4:
+            raise RuntimeError("notes_stitch: spans (S, 4), src (n_total, 4) and out (V, out_ld, 4), got %s, %s and %s" % (
+                tuple(spans.shape), tuple(src.shape), tuple(out.shape)))
+        S, V = spans.shape[0], out.shape[0]
+        rows = S * V
+        if dec.dim() != 3 or dec.shape[0] != rows or dec.shape[2] != 4 or dec.shape[1] < dec_ld or dec.stride(2) != 1 or dec.stride(1) != 4 or (
+                rows > 1 and (dec.stride(0) % 4 or dec.stride(0) < 4 * dec.shape[1])):
+            raise RuntimeError("notes_stitch: dec (%d, >= %d, 4) with contiguous rows, got shape %s strides %s" % (rows, dec_ld, tuple(dec.shape), dec.stride()))
+        rs = dec.stride(0) // 4 if rows > 1 else dec.shape[1]
+        for t, nm, n in ((dec_n, "dec_n", rows), (dec_end, "dec_end", rows), (mode, "mode", rows), (win_first, "win_first", V * (S + 1)), (out_n, "out_n", V),
+                         (status, "status", V)):
+            _dense(t, torch.int32, nm)
+            if t is None or t.numel() != n:
+                raise RuntimeError("notes_stitch: %s of %d words" % (nm, n))
+        _lib.check(self.lib.fn_notes_stitch(_p(dec), rs, int(dec_ld), _p(dec_n), _p(dec_end), _p(src) if src.shape[0] else None, src.shape[0], _p(spans), S, V,
+                                            _p(mode), _p(out), out.shape[1], _p(win_first), _p(out_n), _p(status), self.stream()), "fn_notes_stitch")
+
     def sweep_scores(self, r, n, status, values, which, r_std, n_std, scores, n_used):
         """fn_sweep_scores: r, n fp32 and status int32 contiguous [S][Vn]; values fp64 [Vn]; scores fp64 [4]; n_used int32 [1]"""
         _dense(r, name="r"), _dense(n, name="n"), _dense(status, torch.int32, "status"), _dense(values, torch.float64, "values")

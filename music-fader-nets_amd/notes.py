@@ -135,6 +135,57 @@ def notes_to_tokens(notes, spans=None, steps=100, add_eos=True, eos=1, pad=0, vo
     return (tokens, *out)
 
 
+Piece = collections.namedtuple("Piece", ["notes", "n_notes", "win_first", "status"])
+Piece.__doc__ = """notes (V, out_ld, 4) int32 rows of (t0, t1, pitch, vel) in absolute ticks, the windows in order, zeros behind n_notes; n_notes (V,) int32;
+win_first (V, S + 1) int32: the notes in front of window j, the total at S (true counts); status (V,) int32 (0, EMPTY, OVERFLOW)."""
+STITCH_MAX_S, STITCH_MAX_V, STITCH_MAX_OUT = _lib.FN_STITCH_MAX_S, _lib.FN_STITCH_MAX_V, _lib.FN_STITCH_MAX_OUT
+PASS, CLIP, FIT = 0, 1, 2          # the modes of fn_notes_stitch
+
+
+def stitch_notes(dec, src_notes, spans, mode, out_ld=None, ops=None):
+    """Decoded windows back into pieces (fn_notes_stitch; include/fadernets.h has the clauses): window j of piece v is placed at its span's start, cut
+    to its span's length and joined to the windows before it, in one call and without a copy to the host.
+
+    dec        Notes of an (S, V, steps) token tensor, as tokens_to_notes returns them: notes (S, V, dec_ld, 4), n_notes, t_end (S, V) int32.
+    src_notes  (n_total, 4) int32, the piece the windows were cut from; spans (S, 4) int32 rows of (first, count, t_lo, t_hi), as midi_segments returns
+               them (count is not capped).
+    mode       (S, V) int32 on the device: PASS (0) the span's source notes that start in the window, unchanged; CLIP (1) the decoded notes that start
+               in [0, W), W = t_hi - t_lo at most 2^22, ends cut at W, moved to t_lo; FIT (2) as CLIP after the decoded times were scaled by W / t_end
+               where t_end > W; anything else: the window holds nothing.
+    out_ld     the note slots of a piece; None: n_total + S * dec_ld, which cannot overflow.
+
+    -> Piece(notes (V, out_ld, 4), n_notes (V,), win_first (V, S + 1), status (V,)) on the device.  A note that ends up with t1 <= t0, a pitch
+    outside [0, 128) or a time outside int32 is dropped, velocities are clamped to [1, 127]: midi_bytes takes every stitched piece.
+    ValueError for anything that is not as described, before anything is launched."""
+    if not isinstance(dec, Notes) or not all(torch.is_tensor(t) and t.dtype == torch.int32 for t in dec) or dec.notes.dim() != 4 or dec.notes.shape[3] != 4 \
+            or dec.notes.numel() == 0 or any(tuple(t.shape) != tuple(dec.notes.shape[:2]) for t in dec[1:]):
+        raise ValueError("dec: Notes of an (S, V, steps) token tensor - notes (S, V, dec_ld, 4), n_notes, t_end, status (S, V), int32 - got %s" % (
+            ", ".join(_what(t) for t in dec) if isinstance(dec, Notes) else type(dec).__name__))
+    S, V, dec_ld = dec.notes.shape[:3]
+    dev = dec.notes.device
+    if S > STITCH_MAX_S or V > STITCH_MAX_V:
+        raise ValueError("dec: at most %d windows of %d pieces, got %d of %d" % (STITCH_MAX_S, STITCH_MAX_V, S, V))
+    if not torch.is_tensor(src_notes) or src_notes.dtype != torch.int32 or src_notes.dim() != 2 or src_notes.shape[1] != 4 or src_notes.device != dev:
+        raise ValueError("src_notes: an int32 tensor (n_total, 4) beside dec, got %s" % _what(src_notes))
+    n_total = src_notes.shape[0]
+    if S * max(n_total, dec_ld) >= 2**31:
+        raise ValueError("src_notes: S * max(n_total, dec_ld) below 2^31 (a count could leave int32), got %d * %d" % (S, max(n_total, dec_ld)))
+    if not torch.is_tensor(spans) or spans.dtype != torch.int32 or tuple(spans.shape) != (S, 4) or spans.device != dev:
+        raise ValueError("spans: an int32 tensor (%d, 4) beside dec, got %s" % (S, _what(spans)))
+    if not torch.is_tensor(mode) or mode.dtype != torch.int32 or tuple(mode.shape) != (S, V) or mode.device != dev:
+        raise ValueError("mode: an int32 tensor (%d, %d) beside dec, got %s" % (S, V, _what(mode)))
+    out_ld = n_total + S * dec_ld if out_ld is None else _int("out_ld", out_ld, 1, STITCH_MAX_OUT + 1)
+    if out_ld > STITCH_MAX_OUT:
+        raise ValueError("out_ld: at most %d note slots, got n_total + S * dec_ld = %d" % (STITCH_MAX_OUT, out_ld))
+    rows = dec.notes.reshape(S * V, dec_ld, 4).contiguous()
+    out = torch.empty(V, out_ld, 4, dtype=torch.int32, device=dev)
+    win_first = torch.empty(V, S + 1, dtype=torch.int32, device=dev)
+    out_n, status = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(2))
+    _ops_of(rows, ops).notes_stitch(rows, dec_ld, dec.n_notes.reshape(-1).contiguous(), dec.t_end.reshape(-1).contiguous(), src_notes.contiguous(),
+                                    spans.contiguous(), mode.reshape(-1).contiguous(), out, win_first, out_n, status)
+    return Piece(out, out_n, win_first, status)
+
+
 KK_MAJOR = (6.35, 2.23, 3.48, 2.33, 4.38, 4.09, 2.52, 5.19, 2.39, 3.66, 2.29, 2.88)          # Krumhansl & Kessler (1982), probe-tone ratings
 KK_MINOR = (6.33, 2.68, 3.52, 5.38, 2.60, 3.53, 2.54, 4.75, 3.98, 2.69, 3.34, 3.17)
 
