@@ -2,7 +2,7 @@
 // (fn_event_attributes) and the consistency / restrictiveness / monotonicity of a fader sweep (fn_sweep_scores).  include/fadernets.h has the
 // definition and says which part is the reference's (the piano-roll fill, the attributes, the scores) and which is ours (tokens -> timed notes).
 // Plain HIP: no inline assembly, no hand-counted waits, no atomics, nothing between workgroups.
-#include "common.h"
+#include "events.h"
 
 namespace {
 
@@ -18,12 +18,6 @@ __device__ __forceinline__ AttrView attr_view(const FnAttrParams* __restrict__ p
     c.np = min(max(p->n_pitch, 0), 128), c.ns = min(max(p->n_shift, 0), 4096);
     c.num = (uint32_t)min(max(p->ticks_num, 1), 32768), c.den = (uint32_t)min(max(p->ticks_den, 1), 256), c.bc = (uint32_t)min(max(p->beat_cells, 1), 64);
     return c;
-}
-
-// offset of token e in the range of n tokens that starts at lo, or -1 (64-bit difference: lo is whatever the memory held)
-__device__ __forceinline__ int attr_in_range(int e, int lo, int n) {
-    const long d = (long)e - (long)lo;
-    return (d >= 0 && d < n) ? (int)d : -1;
 }
 
 // the fill of one kept note into the lane's own bit column (bit c of word w = cell 32 w + c; the words of a column are 128 apart)
@@ -42,45 +36,23 @@ __device__ __forceinline__ void attr_fill(uint32_t* col, const AttrView& c, uint
     }
 }
 
-// One walk over the row's stored events by every lane (the same LDS word for all: a broadcast); lane l follows pitches l and l + 64 and keeps their
-// open t0 in two registers.  FILL = false: only the largest t1 of a kept note (the first, cheap walk that gives n_cells); FILL = true: the notes go
-// into the lane's bit columns as they close.
+// One fn_note_walk over the row.  FILL = false: only the largest t1 of a kept note (the first, cheap walk that gives n_cells); FILL = true: the notes
+// go into the lane's bit columns as they close.
 template <bool FILL>
 __device__ __forceinline__ uint32_t attr_walk(const uint32_t* ev, int len, uint32_t t_end, int lane, const AttrView& c, uint32_t* bits, int nc) {
-    int open0 = -1, open1 = -1;
     uint32_t t_last = 0;
-    for (int i = 0; i < len; ++i) {
-        const uint32_t w = ev[i];
-        const int code = (int)(w & 511u);
-        if (code == 0) continue;
-        const bool is_on = code <= 128;
-        const int p = is_on ? code - 1 : code - 129;
-        if ((p & 63) != lane) continue;
-        const uint32_t t = w >> 9;
-        const int open = (p >> 6) ? open1 : open0;
-        if (open >= 0 && t > (uint32_t)open) {
-            t_last = max(t_last, t);
-            if (FILL) attr_fill(bits + (p >> 6) * 64 + lane, c, (uint32_t)open, t, nc);
-        }
-        const int now = is_on ? (int)t : -1;
-        if (p >> 6) open1 = now; else open0 = now;
-    }
-    if (open0 >= 0 && t_end > (uint32_t)open0) {
-        t_last = max(t_last, t_end);
-        if (FILL) attr_fill(bits + lane, c, (uint32_t)open0, t_end, nc);
-    }
-    if (open1 >= 0 && t_end > (uint32_t)open1) {
-        t_last = max(t_last, t_end);
-        if (FILL) attr_fill(bits + 64 + lane, c, (uint32_t)open1, t_end, nc);
-    }
+    fn_note_walk(ev, len, t_end, lane, [&](int p, uint32_t t0, uint32_t t1, int) {
+        t_last = max(t_last, t1);
+        if (FILL) attr_fill(bits + (p >> 6) * 64 + lane, c, t0, t1, nc);
+    });
     return t_last;
 }
 
 extern __shared__ __attribute__((aligned(16))) char attr_smem[];
 
-// One wavefront per row, one row per 64-thread workgroup.  LDS: ev[steps] (tick << 9 | code; code 0 = skipped, 1 + p = note-on, 129 + p = note-off;
-// the tick is the clock AFTER the token) and bits[ceil(cells_ld / 32)][128], a bit column per pitch over the cells.  n_cells is needed by the fill's
-// guards, so phase 2 walks the events twice: a first walk that only finds t_last, then the walk that fills (the notes are not kept in between).
+// One wavefront per row, one row per 64-thread workgroup.  LDS: ev[steps] (fn_event_scan's words: tick << 9 | code) and
+// bits[ceil(cells_ld / 32)][128], a bit column per pitch over the cells.  n_cells is needed by the fill's guards, so phase 2 walks the events
+// twice: a first walk that only finds t_last, then the walk that fills (the notes are not kept in between).
 // Every lane reaches every barrier: no return before the end, and every ballot / shuffle sits in wave-uniform control flow.
 __global__ __launch_bounds__(64) void event_raster_kernel(const int32_t* __restrict__ tokens, int tok_ld, int steps, const FnAttrParams* __restrict__ params,
                                                           int32_t* __restrict__ n_cells, int32_t* __restrict__ status, float* __restrict__ r_density,
@@ -95,39 +67,13 @@ __global__ __launch_bounds__(64) void event_raster_kernel(const int32_t* __restr
     const int32_t* row = tokens + r * tok_ld;
 
     // phase 1: the row's end, the clock of every token, the events into LDS
-    int len = steps;
-    uint32_t carry = 0;
-    bool found = false;
-    for (int base = 0; base < steps && !found; base += 64) {
-        const int i = base + lane;
-        const int e = i < steps ? row[i] : 0;
-        const unsigned long long m = __ballot(i < steps && c.eos >= 0 && e == c.eos);
-        if (m != 0ull) found = true, len = base + __ffsll((long long)m) - 1;
-        const bool live = i < len;                      // len <= steps
-        uint32_t amount = 0, code = 0;
-        if (live && (c.vocab <= 0 || (e >= 0 && e < c.vocab))) {
-            int p;
-            if ((p = attr_in_range(e, c.on_lo, c.np)) >= 0) code = 1u + (uint32_t)p;
-            else if ((p = attr_in_range(e, c.off_lo, c.np)) >= 0) code = 129u + (uint32_t)p;
-            else if ((p = attr_in_range(e, c.shift_lo, c.ns)) >= 0) amount = (uint32_t)p + 1u;
-        }
-        uint32_t x = amount;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (live) ev[i] = ((carry + x) << 9) | code;
-        carry += __shfl(x, 63, 64);
-    }
-    const uint32_t t_end = carry;
+    uint32_t t_end;
+    const int len = fn_event_scan<false>(row, steps, lane, c, ev, nullptr, t_end);
     for (int k = lane; k < words * 128; k += 64) bits[k] = 0u;          // lane l zeroes the columns of pitches l and l + 64: its own
     __syncthreads();
 
     // phase 2: t_last, n_cells, then the fill
-    uint32_t t_last = attr_walk<false>(ev, len, t_end, lane, c, nullptr, 0);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t_last = max(t_last, (uint32_t)__shfl_xor(t_last, o, 64));
+    const uint32_t t_last = fn_wave_max_u32(attr_walk<false>(ev, len, t_end, lane, c, nullptr, 0));
     const uint32_t nc_u = t_last > 0u ? c.bc * ((t_last * c.den) / (c.num * c.bc) + 1u) : 0u;          // < 2^31
     const int nc = (int)nc_u;
     const bool fits = nc > 0 && nc <= cells_ld;

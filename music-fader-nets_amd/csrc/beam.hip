@@ -6,28 +6,13 @@
 
 namespace {
 
-// pack(s, i) of fn_out_argmax_f32 over n = W * V columns: order-preserving key of s in the high half, n - 1 - i in the low half
-__device__ __forceinline__ unsigned long long beam_pack(float s, int i, int n) {
-    const uint32_t b = __float_as_uint(s);
-    const uint32_t key = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-    return ((unsigned long long)key << 32) | (uint32_t)(n - 1 - i);
-}
-
+// the score back from the high half of a word of fn_pack_best (common.h; here over n = W * V columns)
 __device__ __forceinline__ float beam_unkey(uint32_t key) {
     return __uint_as_float(key ^ ((key >> 31) ? 0x80000000u : 0xffffffffu));
 }
 
-__device__ __forceinline__ unsigned long long beam_wave_max(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long ov = __shfl_xor(v, o, 64);
-        v = ov > v ? ov : v;
-    }
-    return v;
-}
-
-// One workgroup of W wavefronts per sequence, wavefront w on beam row w: lane l holds e = l, l + 64, ... in NE registers, computes the row's lse as
-// vocab_argmax_kernel does, packs its V candidates and leaves the row's own top W words (only they can reach the sequence's top W) in LDS by W rounds
+// One workgroup of W wavefronts per sequence, wavefront w on beam row w: lane l holds e = l, l + 64, ... in NE registers, takes the row's lse from
+// fn_row_head, packs its V candidates and leaves the row's own top W words (only they can reach the sequence's top W) in LDS by W rounds
 // of wave-max with removal; a non-live row leaves W empty words (0: below every real candidate, whose key is at least key(-inf)), a finished row its
 // one candidate.  After the barrier thread t < W * W ranks word t by counting the larger ones (the words of real candidates are distinct) and the
 // threads of rank < W store the slabs.  (The row loop strides by the number of wavefronts, whatever the launch gives it.)
@@ -43,23 +28,7 @@ __global__ __launch_bounds__(64 * FN_BEAM_MAX_W) void beam_step_kernel(const flo
     for (int w = wv; w < W; w += nwv) {
         const long r = (long)b * W + w;
         const float* x = logits + r * ld;
-        // max, lse, lp: the instruction sequence of vocab_argmax_kernel
-        float mx = -INFINITY;
-        int am = 0x7fffffff;
-        for (int e = lane; e < V; e += 64) {
-            const float v = x[e];
-            if (v > mx) { mx = v; am = e; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(mx, o, 64);
-            const int oa = __shfl_xor(am, o, 64);
-            if (ov > mx || (ov == mx && oa < am)) { mx = ov; am = oa; }
-        }
-        float s = 0.f;
-        for (int e = lane; e < V; e += 64) s += expf(x[e] - mx);
-        s = fn_wave_sum(s);
-        const float lse = mx + logf(s);
+        const float lse = fn_row_head(x, V, lane).lse;          // lp = x[e] - lse, as vocab_argmax_kernel forms it
         if (logp_out)
             for (int e = lane; e < V; e += 64) logp_out[r * logp_ld + e] = x[e] - lse;
         const bool live = step > 0 || w == 0;
@@ -69,14 +38,14 @@ __global__ __launch_bounds__(64 * FN_BEAM_MAX_W) void beam_step_kernel(const flo
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
             const int e = lane + 64 * k;
-            wd[k] = (live && !finished && e < V) ? beam_pack(sp + (x[e] - lse), w * V + e, n) : 0ull;
+            wd[k] = (live && !finished && e < V) ? fn_pack_best(sp + (x[e] - lse), w * V + e, n) : 0ull;
         }
-        if (finished && lane == 0) wd[0] = beam_pack(sp, w * V + eos, n);
+        if (finished && lane == 0) wd[0] = fn_pack_best(sp, w * V + eos, n);
         for (int j = 0; j < W; ++j) {
             unsigned long long m = wd[0];
 #pragma unroll
             for (int k = 1; k < NE; ++k) m = wd[k] > m ? wd[k] : m;
-            m = beam_wave_max(m);
+            m = fn_wave_max_u64(m);
             // the low halves differ from candidate to candidate: exactly one register of one lane holds m (or m is the empty word)
 #pragma unroll
             for (int k = 0; k < NE; ++k) wd[k] = wd[k] == m ? 0ull : wd[k];

@@ -70,3 +70,86 @@ __device__ __forceinline__ double fn_wave_sum_f64(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ int fn_wave_sum_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t fn_wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned long long fn_wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long ov = __shfl_xor(v, o, 64);
+        v = ov > v ? ov : v;
+    }
+    return v;
+}
+
+// inclusive scan over the 64 lanes: the sum of x over the lanes up to and including `lane` (the caller's own lane index)
+template <class T>
+__device__ __forceinline__ T fn_wave_scan_add(T x, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    return x;
+}
+// carry-forward scan: the last non-zero v at or before the lane, 0 where there is none
+__device__ __forceinline__ uint32_t fn_wave_scan_last(uint32_t v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(v, o, 64);
+        if (lane >= o && v == 0u) v = y;
+    }
+    return v;
+}
+
+// (max, first index holding it) of the lanes' (mx, am) pairs, the same in every lane: torch.max semantics.  Not fn_wave_max: that one is fmaxf, which
+// skips a NaN where `>` keeps what it has.  The butterfly runs on copies: with the caller's variables in the loop the compiler allocates registers
+// and places waits differently from the kernels that had this loop inline (measured on vocab_sample_kernel: 101 -> 111 us per launch).
+__device__ __forceinline__ void fn_wave_argmax(float& mx_io, int& am_io) {
+    float mx = mx_io;
+    int am = am_io;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(mx, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        if (ov > mx || (ov == mx && oa < am)) { mx = ov; am = oa; }
+    }
+    mx_io = mx, am_io = am;
+}
+
+// The head of one row of E logits read lane-strided by one wavefront (lane l: e = l, l + 64, ...): max, first-index argmax (0x7fffffff for a row
+// without a value above -inf) and log-sum-exp, the same in every lane.  The heads that promise bit-equal log-probs (fn_vocab_argmax, fn_vocab_sample,
+// fn_beam_step) all take them from here: x[e] - lse.
+struct FnRowHead {
+    float mx, lse;
+    int am;
+};
+__device__ __forceinline__ FnRowHead fn_row_head(const float* __restrict__ x, int E, int lane) {
+    FnRowHead h;
+    h.mx = -INFINITY, h.am = 0x7fffffff;
+    for (int e = lane; e < E; e += 64) {
+        const float v = x[e];
+        if (v > h.mx) { h.mx = v; h.am = e; }
+    }
+    fn_wave_argmax(h.mx, h.am);
+    float s = 0.f;
+    for (int e = lane; e < E; e += 64) s += expf(x[e] - h.mx);
+    s = fn_wave_sum(s);
+    h.lse = h.mx + logf(s);
+    return h;
+}
+
+// pack(x, v) over V columns: order-preserving key of x in the high half, V - 1 - v in the low half, so the 64-bit maximum is the largest x and, among
+// equals, the lowest column (fn_out_argmax_f32, fn_beam_step)
+__device__ __forceinline__ unsigned long long fn_pack_best(float x, int v, int V) {
+    const uint32_t b = __float_as_uint(x);
+    const uint32_t key = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+    return ((unsigned long long)key << 32) | (uint32_t)(V - 1 - v);
+}

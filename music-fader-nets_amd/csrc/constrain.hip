@@ -2,7 +2,7 @@
 // fn_beam_step (fn_constrain_apply) and the fix-up + sounding-pitch update behind them (fn_constrain_advance).  include/fadernets.h has the
 // definition; there is no reference counterpart (gmm_model.py:73-80,119-149 feeds back its argmax).
 // Plain HIP: no inline assembly, no hand-counted waits, no LDS, no barriers, no atomics, no spins across workgroups.
-#include "common.h"
+#include "events.h"
 
 namespace {
 
@@ -18,12 +18,6 @@ __device__ __forceinline__ ConstrainView constrain_view(const FnConstrainParams*
     c.n = min(max(p->n_pitch, 0), FN_CONSTRAIN_MAX_PITCH);
     c.max_poly = p->max_poly, c.eos = p->eos, c.min_len = p->min_len, c.flags = p->flags;
     return c;
-}
-
-// pitch of token e in the range that starts at lo, or -1 (64-bit difference: lo is whatever the memory held)
-__device__ __forceinline__ int constrain_pitch(int e, int lo, int n) {
-    const long p = (long)e - (long)lo;
-    return (p >= 0 && p < n) ? (int)p : -1;
 }
 
 __device__ __forceinline__ bool constrain_bit(uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3, int p) {
@@ -54,9 +48,9 @@ __global__ __launch_bounds__(256) void constrain_apply_kernel(float* __restrict_
     auto in_g = [&](int e) -> bool {
         if (ban_eos && e == c.eos) return true;
         if (!grammar) return false;
-        int p = constrain_pitch(e, c.on_lo, c.n);
+        int p = fn_token_offset(e, c.on_lo, c.n);
         if (p >= 0) return constrain_bit(h0, h1, h2, h3, p) ? no_reonset : full;
-        p = constrain_pitch(e, c.off_lo, c.n);
+        p = fn_token_offset(e, c.off_lo, c.n);
         return p >= 0 && off_needs_on && !constrain_bit(h0, h1, h2, h3, p);
     };
 
@@ -93,11 +87,11 @@ __global__ __launch_bounds__(256) void constrain_advance_kernel(int* tok_io, int
     if (!held_in) return;
     uint32_t h[4] = {held_in[r * 4 + 0], held_in[r * 4 + 1], held_in[r * 4 + 2], held_in[r * 4 + 3]};
     if (tok >= 0 && tok < V) {
-        int p = constrain_pitch(tok, c.on_lo, c.n);
+        int p = fn_token_offset(tok, c.on_lo, c.n);
         if (p >= 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) h[k] |= (k == (p >> 5)) ? (1u << (p & 31)) : 0u;
-        } else if ((p = constrain_pitch(tok, c.off_lo, c.n)) >= 0) {
+        } else if ((p = fn_token_offset(tok, c.off_lo, c.n)) >= 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) h[k] &= (k == (p >> 5)) ? ~(1u << (p & 31)) : 0xffffffffu;
         }

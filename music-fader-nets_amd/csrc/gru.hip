@@ -809,12 +809,7 @@ FN_DEVINL void cell_epilogue_finish(const CellArgs& a, int m0, int u0, int lane,
 }
 
 // Packed-argmax epilogue of the output kernels: lane (li, lg) holds the logits of rows m0 + 4 lg + i, columns n0 + 16 q + li - the best
-// packed word of its three columns per row, a 16-lane butterfly over li, one 64-bit atomic max per row and wave.
-FN_DEVINL unsigned long long fn_pack_best(float x, int v, int V) {
-    const unsigned b = __float_as_uint(x);
-    const unsigned key = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-    return ((unsigned long long)key << 32) | (unsigned)(V - 1 - v);
-}
+// packed word (fn_pack_best, common.h) of its three columns per row, a 16-lane butterfly over li, one 64-bit atomic max per row and wave.
 FN_DEVINL void out_argmax_bias(const float* __restrict__ bias, int n0, int lane, int V, float (&bv)[3]) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) bv[q] = bias[min(n0 + 16 * q + (lane & 15), V - 1)];

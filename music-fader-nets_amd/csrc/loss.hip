@@ -61,25 +61,10 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float* __restri
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
     const float* x = logits + (long)b * ld;
-    float mx = -INFINITY;
-    int am = 0x7fffffff;
-    for (int e = lane; e < E; e += 64) {
-        const float v = x[e];
-        if (v > mx) { mx = v; am = e; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mx, o, 64);
-        const int oa = __shfl_xor(am, o, 64);
-        if (ov > mx || (ov == mx && oa < am)) { mx = ov; am = oa; }
-    }
-    float s = 0.f;
-    for (int e = lane; e < E; e += 64) s += expf(x[e] - mx);
-    s = fn_wave_sum(s);
-    const float lse = mx + logf(s);
+    const FnRowHead h = fn_row_head(x, E, lane);
     if (logp_out)
-        for (int e = lane; e < E; e += 64) logp_out[(long)b * logp_ld + e] = x[e] - lse;
-    if (lane == 0) tok_out[(long)b * tok_ld] = am;
+        for (int e = lane; e < E; e += 64) logp_out[(long)b * logp_ld + e] = x[e] - h.lse;
+    if (lane == 0) tok_out[(long)b * tok_ld] = h.am;
 }
 
 // seeded temperature / top-k / top-p draw (fn_vocab_sample, include/fadernets.h has the definition; no reference counterpart: the reference's
@@ -97,12 +82,6 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-__device__ __forceinline__ int fn_wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int NE>      // entries per lane: V <= 64 NE
 __global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restrict__ logits, int B, int E, int ld,
                                                            const FnSampleParams* __restrict__ params, int step, float* __restrict__ logp_out,
@@ -115,27 +94,13 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restri
     const int br = live ? b : B - 1;
     float* sf = reinterpret_cast<float*>(fn_sample_lds) + (size_t)wv * E;             // lp, then the sorted weights, then their prefix sums
     int* si = reinterpret_cast<int*>(fn_sample_lds) + (size_t)4 * E + (size_t)wv * E;  // the sorted indices
-    // 1. max, first-index argmax, lse, lp: the instruction sequence of vocab_argmax_kernel
+    // 1. max, first-index argmax, lse, lp: fn_row_head, as vocab_argmax_kernel takes them
     const float* x = logits + (long)br * ld;
-    float mx = -INFINITY;
-    int am = 0x7fffffff;
-    for (int e = lane; e < E; e += 64) {
-        const float v = x[e];
-        if (v > mx) { mx = v; am = e; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mx, o, 64);
-        const int oa = __shfl_xor(am, o, 64);
-        if (ov > mx || (ov == mx && oa < am)) { mx = ov; am = oa; }
-    }
-    float s = 0.f;
-    for (int e = lane; e < E; e += 64) s += expf(x[e] - mx);
-    s = fn_wave_sum(s);
-    const float lse = mx + logf(s);
+    const FnRowHead h = fn_row_head(x, E, lane);
+    const float lse = h.lse;
     if (logp_out && live)
         for (int e = lane; e < E; e += 64) logp_out[(long)b * logp_ld + e] = x[e] - lse;
-    if (own_out && live && lane == 0) own_out[(long)b * own_ld] = am;
+    if (own_out && live && lane == 0) own_out[(long)b * own_ld] = h.am;
     float lp[NE];
 #pragma unroll
     for (int k = 0; k < NE; ++k) {
@@ -143,7 +108,7 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restri
         lp[k] = e < E ? x[e] - lse : -INFINITY;
         if (e < E) sf[e] = lp[k];
     }
-    const float lp_max = mx - lse;
+    const float lp_max = h.mx - lse;
     // the parameters come from memory: clamped, as the host twin clamps them
     const FnSampleParams pr = *params;
     const int top_k = min(max(pr.top_k, 0), E);
@@ -184,12 +149,7 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restri
         if (k < per) run += j < E ? sf[j] : 0.f;
         c[k] = run;
     }
-    float tot = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float up = __shfl_up(tot, o, 64);
-        if (lane >= o) tot += up;
-    }
+    const float tot = fn_wave_scan_add(run, lane);
     float before = __shfl_up(tot, 1, 64);
     if (lane == 0) before = 0.f;
 #pragma unroll

@@ -2,7 +2,7 @@
 // keeps in registers, with velocity; fn_tokens_from_notes is the tokeniser; fn_notes_stitch joins decoded windows into pieces (transfer.py).
 // include/fadernets.h has the definitions.
 // Plain HIP: no inline assembly, no atomics, nothing between workgroups; one wavefront per row, every lane reaches every barrier.
-#include "common.h"
+#include "events.h"
 
 namespace {
 
@@ -17,12 +17,6 @@ __device__ __forceinline__ NoteView note_view(const FnNoteParams* __restrict__ p
     c.vstep = c.nv > 0 ? (127 + c.nv - 1) / c.nv : 1;
     c.def_vel = min(max(p->default_vel, 1), 127), c.pad = p->pad, c.add_eos = p->add_eos;
     return c;
-}
-
-// offset of token e in the range of n tokens that starts at lo, or -1 (64-bit difference: lo is whatever the memory held)
-__device__ __forceinline__ int note_in_range(int e, int lo, int n) {
-    const long d = (long)e - (long)lo;
-    return (d >= 0 && d < n) ? (int)d : -1;
 }
 
 // Ascending bitonic sort of n 64-bit keys in LDS by one wavefront; n a power of two (1: nothing to do).  Pair t of a pass is (lo, lo + stride) with
@@ -52,10 +46,9 @@ extern __shared__ __attribute__((aligned(16))) char note_smem[];
 constexpr unsigned long long NOTE_NO_KEY = ~0ull;
 
 // LDS: key[P] (t0 << 17 | pitch << 10 | index of the note-on token; NOTE_NO_KEY where the token opens no kept note), P = the power of two >= steps;
-// ev[steps] (tick << 9 | code, as event_raster_kernel has it); t1[steps] by note-on token; vel[steps], the velocity current at every token.
-// Phase 1 is event_raster_kernel's (the ballot for the eos, the shuffle scan of the clock) with a second, carry-forward scan for the velocity.
-// Phase 2: every lane walks all events (the same LDS word for all: a broadcast) and follows pitches l and l + 64; a note that closes goes to the slot
-// of its note-on token, which no other note has.  Phase 3: sort the keys; rank j of the order is note j.
+// ev[steps] and vel[steps], the velocity current at every token (phase 1: fn_event_scan with the velocity track, as event_raster_kernel runs it
+// without); t1[steps] by note-on token.  Phase 2: fn_note_walk; a note that closes goes to the slot of its note-on token, which no other note has.
+// Phase 3: sort the keys; rank j of the order is note j.
 __global__ __launch_bounds__(64) void notes_from_tokens_kernel(const int32_t* __restrict__ tokens, int tok_ld, int steps, const FnNoteParams* __restrict__ params,
                                                                FnNote* __restrict__ notes, int notes_ld, int32_t* __restrict__ n_notes,
                                                                int32_t* __restrict__ t_end_out, int32_t* __restrict__ status) {
@@ -70,71 +63,18 @@ __global__ __launch_bounds__(64) void notes_from_tokens_kernel(const int32_t* __
     const int32_t* row = tokens + r * tok_ld;
 
     // phase 1
-    int len = steps;
-    uint32_t carry = 0, vcarry = (uint32_t)c.def_vel;
-    bool found = false;
-    for (int base = 0; base < steps && !found; base += 64) {
-        const int i = base + lane;
-        const int e = i < steps ? row[i] : 0;
-        const unsigned long long m = __ballot(i < steps && c.eos >= 0 && e == c.eos);
-        if (m != 0ull) found = true, len = base + __ffsll((long long)m) - 1;
-        const bool live = i < len;                      // len <= steps
-        uint32_t amount = 0, code = 0, v = 0;
-        if (live && (c.vocab <= 0 || (e >= 0 && e < c.vocab))) {
-            int p;
-            if ((p = note_in_range(e, c.on_lo, c.np)) >= 0) code = 1u + (uint32_t)p;
-            else if ((p = note_in_range(e, c.off_lo, c.np)) >= 0) code = 129u + (uint32_t)p;
-            else if ((p = note_in_range(e, c.shift_lo, c.ns)) >= 0) amount = (uint32_t)p + 1u;
-            else if ((p = note_in_range(e, c.vel_lo, c.nv)) >= 0) v = (uint32_t)min(1 + p * c.vstep, 127);
-        }
-        uint32_t x = amount;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {              // the last non-zero value at or before the lane
-            const uint32_t y = __shfl_up(v, o, 64);
-            if (lane >= o && v == 0u) v = y;
-        }
-        if (v == 0u) v = vcarry;
-        if (live) ev[i] = ((carry + x) << 9) | code, vel[i] = (uint8_t)v;
-        carry += __shfl(x, 63, 64);
-        vcarry = __shfl(v, 63, 64);
-    }
-    const uint32_t t_end = carry;
+    uint32_t t_end;
+    const int len = fn_event_scan<true>(row, steps, lane, c, ev, vel, t_end);
     for (int k = lane; k < P; k += 64) key[k] = NOTE_NO_KEY;
     __syncthreads();
 
     // phase 2
-    int open0 = -1, open1 = -1, at0 = 0, at1 = 0, mine = 0;
-    for (int i = 0; i < len; ++i) {
-        const uint32_t w = ev[i];
-        const int code = (int)(w & 511u);
-        if (code == 0) continue;
-        const bool is_on = code <= 128;
-        const int p = is_on ? code - 1 : code - 129;
-        if ((p & 63) != lane) continue;
-        const uint32_t t = w >> 9;
-        const int open = (p >> 6) ? open1 : open0, at = (p >> 6) ? at1 : at0;
-        if (open >= 0 && t > (uint32_t)open) {
-            key[at] = ((unsigned long long)(uint32_t)open << 17) | ((unsigned long long)p << 10) | (unsigned long long)at;
-            t1s[at] = t, ++mine;
-        }
-        const int now = is_on ? (int)t : -1;
-        if (p >> 6) open1 = now, at1 = i; else open0 = now, at0 = i;
-    }
-    if (open0 >= 0 && t_end > (uint32_t)open0) {
-        key[at0] = ((unsigned long long)(uint32_t)open0 << 17) | ((unsigned long long)lane << 10) | (unsigned long long)at0;
-        t1s[at0] = t_end, ++mine;
-    }
-    if (open1 >= 0 && t_end > (uint32_t)open1) {
-        key[at1] = ((unsigned long long)(uint32_t)open1 << 17) | ((unsigned long long)(lane + 64) << 10) | (unsigned long long)at1;
-        t1s[at1] = t_end, ++mine;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    int mine = 0;
+    fn_note_walk(ev, len, t_end, lane, [&](int p, uint32_t t0, uint32_t t1, int at) {
+        key[at] = ((unsigned long long)t0 << 17) | ((unsigned long long)p << 10) | (unsigned long long)at;
+        t1s[at] = t1, ++mine;
+    });
+    mine = fn_wave_sum_i32(mine);
     const int n = mine;                                 // <= len
 
     // phase 3
@@ -187,8 +127,7 @@ __global__ __launch_bounds__(64) void tokens_from_notes_kernel(const FnNote* __r
         }
         key[2 * k] = on, key[2 * k + 1] = off;          // 2k + 1 < P
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o, 64);
+    kept = fn_wave_sum_i32(kept);
 
     // phase 2
     lds_bitonic_sort(key, P, lane);
@@ -208,24 +147,14 @@ __global__ __launch_bounds__(64) void tokens_from_notes_kernel(const FnNote* __r
         const uint32_t g = tick - before;
         const uint32_t full = ns ? g / ns : 0u, rest = ns ? g % ns : 0u;
         const uint32_t b = (is_on && c.nv > 0) ? 1u + (uint32_t)bin[k & 1023ull] : 0u;
-        uint32_t last = b;                              // the last non-zero b at or before the lane ...
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(last, o, 64);
-            if (lane >= o && last == 0u) last = y;
-        }
+        uint32_t last = fn_wave_scan_last(b, lane);     // the last non-zero b at or before the lane ...
         if (last == 0u) last = prev_bin;
         uint32_t seen = __shfl_up(last, 1, 64);         // ... and before it
         if (lane == 0) seen = prev_bin;
         prev_bin = __shfl(last, 63, 64);
         const bool vel_tok = b != 0u && b != seen;
         const uint32_t cnt = live ? full + (rest ? 1u : 0u) + (vel_tok ? 1u : 0u) + 1u : 0u;
-        uint32_t x = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
+        const uint32_t x = fn_wave_scan_add(cnt, lane);
         const uint32_t start = total + x - cnt;         // < 2^23: the gaps of a row sum to at most FN_NOTES_MAX_TICK
         total += __shfl(x, 63, 64);
         if (live) {
@@ -346,12 +275,7 @@ __global__ __launch_bounds__(64) void stitch_scan_kernel(int32_t* __restrict__ w
         int c[4], sum = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) c[q] = i0 + q < S ? row[i0 + q] : 0, sum += c[q];
-        int x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
+        const int x = fn_wave_scan_add(sum, lane);
         int before = carry + x - sum;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

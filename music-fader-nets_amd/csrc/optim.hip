@@ -27,8 +27,7 @@ __global__ __launch_bounds__(1024) void sumsq_final_kernel(const float* __restri
     __shared__ double red[16];
     double s = 0.0;
     for (int i = threadIdx.x; i < nb; i += 1024) s += (double)partial[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = fn_wave_sum_f64(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -7,16 +7,10 @@
 
 namespace {
 
-__device__ __forceinline__ int report_wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One wavefront per row (row = b T + t, the order of the outputs), 4 rows per workgroup, lane l holds e = l, l + 64, ... in NE registers (V <= 64 NE):
-// the geometry of vocab_sample_kernel.  max / first-index argmax / expf sum / logf are the instruction sequence of vocab_argmax_kernel, so pred is its
-// token and nll the value of vocab_logsoftmax_kernel on the same floats.  x[tg] is picked up in the load loop by the lane that owns it and broadcast:
-// the register array is never indexed by a runtime value.
+// the geometry of vocab_sample_kernel.  The row stays in registers, so this is fn_row_head (common.h) written over v[]: the same per-lane order, the
+// same fn_wave_argmax butterfly, expf sum and logf, so pred is vocab_argmax_kernel's token and nll the value of vocab_logsoftmax_kernel on the same
+// floats.  x[tg] is picked up in the load loop by the lane that owns it and broadcast: the register array is never indexed by a runtime value.
 template <int NE>
 __global__ __launch_bounds__(256) void token_score_kernel(const float* __restrict__ x, long stride_b, long stride_t, int B, int T, int V,
                                                           const int32_t* __restrict__ target, int tgt_ld, int32_t* __restrict__ pred,
@@ -37,12 +31,7 @@ __global__ __launch_bounds__(256) void token_score_kernel(const float* __restric
         if (e < V && v[k] > mx) { mx = v[k]; am = e; }
         if (e == tg) xt = v[k];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mx, o, 64);
-        const int oa = __shfl_xor(am, o, 64);
-        if (ov > mx || (ov == mx && oa < am)) { mx = ov; am = oa; }
-    }
+    fn_wave_argmax(mx, am);
     if (pred && lane == 0) pred[b * out_ld + t] = am;
     if (!target) return;                                   // wave-uniform
     xt = __shfl(xt, tg & 63, 64);
@@ -57,7 +46,7 @@ __global__ __launch_bounds__(256) void token_score_kernel(const float* __restric
         }
     }
     s = fn_wave_sum(s);
-    cnt = report_wave_sum_i32(cnt);
+    cnt = fn_wave_sum_i32(cnt);
     if (lane == 0) {
         if (nll) nll[b * out_ld + t] = (mx + logf(s)) - xt;
         if (rank) rank[b * out_ld + t] = cnt;
@@ -96,8 +85,8 @@ __global__ __launch_bounds__(256) void match_rows_kernel(const int32_t* __restri
         if (rank) ok_k += rank[r * aux_ld + lead + j] < topk ? 1 : 0;
         if (nll) sum += (double)nll[r * aux_ld + lead + j];
     }
-    ok = report_wave_sum_i32(ok);
-    if (rank) ok_k = report_wave_sum_i32(ok_k);
+    ok = fn_wave_sum_i32(ok);
+    if (rank) ok_k = fn_wave_sum_i32(ok_k);
     if (nll) sum = fn_wave_sum_f64(sum);
     if (lane == 0) {
         lead_out[r] = lead, len_out[r] = len, correct[r] = ok;

@@ -12,11 +12,26 @@ from .constrain import Constraints, constraint_buffers, constraint_stats, load_c
 from .engine import E_VOCAB, LOGIT_LD
 
 
+def _is_int(v):
+    """an int that is no bool"""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_finite(v):
+    """a finite real number that is no bool"""
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and bool(np.isfinite(v))
+
+
+def _check_steps(steps, bools=True):
+    """bools: True counts as the int it is (beam_decode refuses it)"""
+    if not (isinstance(steps, (int, np.integer)) if bools else _is_int(steps)) or steps < 1:
+        raise ValueError("steps: a positive int, got %r" % (steps,))
+
+
 def _force_mask(force, steps):
     """force as greedy_decode takes it - a bool per step, or an int P = the first P steps - as a list of `steps` bools; ValueError otherwise"""
-    if not isinstance(steps, (int, np.integer)) or steps < 1:
-        raise ValueError("steps: a positive int, got %r" % (steps,))
-    if isinstance(force, (int, np.integer)) and not isinstance(force, (bool, np.bool_)):
+    _check_steps(steps)
+    if _is_int(force):
         if not 0 <= int(force) <= steps:
             raise ValueError("force = P forces the first P steps: 0 <= P <= %d, got %d" % (steps, int(force)))
         return [i < int(force) for i in range(steps)]
@@ -31,8 +46,7 @@ def _forced_args(z, steps, forced, force):
     before anything is launched"""
     if forced is None or force is None:
         raise ValueError("forced and force go together: the tokens and the per-step mask that selects them")
-    if not isinstance(steps, (int, np.integer)) or steps < 1:
-        raise ValueError("steps: a positive int, got %r" % (steps,))
+    _check_steps(steps)
     if not torch.is_tensor(forced):
         forced = torch.as_tensor(np.asarray(forced))
     if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool:
@@ -72,6 +86,82 @@ def _constraints_arg(constraints, Bi, eos=None, beam=False):
     return constraints
 
 
+def _reset_constraints(con):
+    """a decode starts: zeroes the counters and the sounding-pitch words of the buffers of constraint_buffers -> the words, or None where there are none"""
+    if con is None:
+        return None
+    con["stuck"].zero_(), con["fixed"].zero_()
+    if con["held"] is not None:
+        con["held"].zero_()
+    return con["held"]
+
+
+def _prompt_arg(z, steps, prompt):
+    """validated (the prompt (Bi, P <= steps) widened to (Bi, steps) CPU tokens, zeros behind it; P)"""
+    prompt = prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))
+    if prompt.dim() != 2 or prompt.shape[0] != z.shape[0] or prompt.shape[1] > steps:
+        raise ValueError("prompt: (%d, <= %d) tokens, got %s" % (z.shape[0], steps, tuple(prompt.shape)))
+    P = prompt.shape[1]
+    full = torch.zeros(z.shape[0], steps, dtype=prompt.dtype)
+    full[:, :P] = prompt.cpu()
+    return full, P
+
+
+def _init_state(eng, rows, prefix):
+    """the two GEMMs in front of every decode, from the latent rows (z, or z repeated per beam) into the engine's buffers prefix + "h0g" / "rbg":
+    (the global decoder's initial state, layer 1's per-row input bias)"""
+    P, H = eng.p, eng.H
+    h0g = eng.buf(prefix + "h0g", (rows.shape[0], H))
+    eng.ops.gemm(rows, P["linear_init_global.weight"], h0g, bias=P["linear_init_global.bias"])
+    rbg = eng.buf(prefix + "rbg", (rows.shape[0], 3 * H))
+    eng.ops.gemm(rows, P["grucell_g.weight_ih"][:, E_VOCAB:], rbg)
+    return h0g, rbg
+
+
+def _arith_key(eng):
+    """the cells' / GEMMs' arithmetic switches that select launches: a part of every graph key (a new switch goes here, once)"""
+    ops = eng.ops
+    return (bool(getattr(ops, "dw_x6", False) and getattr(ops, "cell_x6", False)), getattr(ops, "cell_x6_rows", None),
+            bool(getattr(ops, "x6_per_tile", False)), bool(getattr(ops, "nt_x6", True)))
+
+
+def _token_buffers(z, steps, want_logp, forced=None, params=None, con=None):
+    """every tensor a captured greedy / sampling decode reads or writes, at its final size: copies of the inputs (zs, fs, ps, cb) and the results"""
+    return dict(zs=z.clone(), fs=None if forced is None else forced.clone(), ps=None if params is None else params.to(z.device),
+                cb=None if con is None else constraint_buffers(con, z.shape[0], z.device),
+                tokens=torch.zeros(z.shape[0], steps, dtype=torch.int32, device=z.device),
+                logp=torch.empty(z.shape[0], steps, E_VOCAB, device=z.device) if want_logp else None)
+
+
+def _graph_replay(eng, cache, key, build, body, bounded, inputs, con=None, repeat=1):
+    """One hipGraph per key in `cache`, captured at the key's first use and replayed on the given inputs -> (clones of the result buffers, cb).
+    build() -> dict of the static buffers at their final sizes, "cb" among them (the buffers of constraint_buffers, or None); body(bufs, warm): the
+    launches on them - first the warm-up (warm=True: a short run that allocates every scratch buffer at its FINAL size, nothing is allocated inside the
+    capture), then the capture.  Every entry keeps its static buffers, so of the keys with bounded(key) at most MAX_MASKED_GRAPHS stay: the oldest
+    goes.  inputs: buffer name -> this call's value, copied in before the replay together with the constraints' setting (con, repeat)."""
+    ent = cache.get(key)
+    if ent is None:
+        bufs = build()
+        body(bufs, True)
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        getattr(eng.ops, "begin_capture", lambda: None)()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            body(bufs, False)
+        ent = cache[key] = (g, bufs)
+        old = [k for k in cache if bounded(k)]
+        if len(old) > MAX_MASKED_GRAPHS:
+            del cache[old[0]]
+    g, bufs = ent
+    for name, v in inputs.items():
+        if bufs[name] is not None:
+            bufs[name].copy_(v)
+    if bufs["cb"] is not None:
+        load_constraints(bufs["cb"], con, inputs["zs"].shape[0], repeat)
+    g.replay()
+    return {k: (None if v is None else v.clone()) for k, v in bufs.items() if k not in inputs and k != "cb"}, bufs["cb"]
+
+
 @torch.no_grad()
 def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, force=None, constraints=None):
     """z (Bi, 2Z+24) -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32).
@@ -98,8 +188,8 @@ def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, 
     if forced is not None or force is not None:
         forced, mask = _forced_args(z, steps, forced, force)
     con = _constraints_arg(constraints, z.shape[0])
-    if con is not None and (not isinstance(steps, (int, np.integer)) or steps < 1):
-        raise ValueError("steps: a positive int, got %r" % (steps,))
+    if con is not None:
+        _check_steps(steps)
     if con is None and _single_launch_ok(eng, z):
         res = _decode_single_launch(eng, z, steps, want_logp, forced, mask)
         if res is not None:
@@ -112,38 +202,15 @@ def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, 
         cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
         logp, tokens = _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask, con=cb)
         return (logp, tokens, constraint_stats(cb)) if con is not None and con.want_stats else (logp, tokens)
-    cache = eng.__dict__.setdefault("_decode_graphs", {})
     # the captured launches depend on the path taken, on the cells' / GEMMs' arithmetic switches, on the form of the constraints and - the per-token
-    # paths pick every step's token pointer on the host - on the mask
-    key = (z.shape[0], steps, bool(want_logp), z.shape[0] >= eng.cell_decode_rows, bool(getattr(eng, "fused_argmax", True)),
-           bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)),
-           getattr(eng.ops, "cell_x6_rows", None), bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)),
+    # paths pick every step's token pointer on the host - on the mask; the unmasked graphs are bounded by the shapes in use
+    key = (z.shape[0], steps, bool(want_logp), z.shape[0] >= eng.cell_decode_rows, bool(getattr(eng, "fused_argmax", True)), *_arith_key(eng),
            None if con is None else con.key(), mask)
-    ent = cache.get(key)
-    if ent is None:
-        zs = z.clone()
-        fs = None if mask is None else forced.clone()
-        cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
-        tokens = torch.zeros(z.shape[0], steps, dtype=torch.int32, device=z.device)
-        logp = torch.empty(z.shape[0], steps, E_VOCAB, device=z.device) if want_logp else None
-        _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask, con=cb)      # warm-up: allocates every buffer at its FINAL size (nothing is allocated inside the capture)
-        g = torch.cuda.CUDAGraph()
-        torch.cuda.synchronize()
-        getattr(eng.ops, "begin_capture", lambda: None)()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask, con=cb)
-        ent = cache[key] = (g, zs, logp, tokens, fs, cb)
-        masked = [k for k in cache if k[-1] is not None]
-        if len(masked) > MAX_MASKED_GRAPHS:           # each entry keeps its own static logp / tokens buffers: the oldest masked graph goes
-            del cache[masked[0]]
-    g, zs, logp, tokens, fs, cb = ent
-    zs.copy_(z)
-    if fs is not None:
-        fs.copy_(forced)
-    if cb is not None:
-        load_constraints(cb, con, z.shape[0])
-    g.replay()
-    logp, tokens = (None if logp is None else logp.clone()), tokens.clone()
+    out, cb = _graph_replay(eng, eng.__dict__.setdefault("_decode_graphs", {}), key, lambda: _token_buffers(z, steps, want_logp, forced, con=con),
+                            lambda b, warm: _decode_body(eng, b["zs"], min(steps, 2) if warm else steps, want_logp, b["logp"], b["tokens"],
+                                                         alloc_steps=steps, forced=b["fs"], mask=mask, con=b["cb"]),
+                            lambda k: k[-1] is not None, dict(zs=z, fs=forced), con)
+    logp, tokens = out["logp"], out["tokens"]
     return (logp, tokens, constraint_stats(cb)) if con is not None and con.want_stats else (logp, tokens)
 
 
@@ -151,14 +218,9 @@ def continue_from(model, z, prompt, steps, want_logp=True, constraints=None):
     """Prompted continuation: prompt (Bi, P) tokens, 0 <= P <= steps -> (log-probs (Bi, steps, 342) or None, tokens (Bi, steps) int32) where
     tokens[:, :P] is the prompt and the rest is what the model wrote after it (the stream that was fed back); the log-probs are
     the model's own at every step, i.e. logp[:, i] scores tokens[:, i] given the start token and tokens[:, :i].  constraints: as greedy_decode."""
-    prompt = prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))
-    if prompt.dim() != 2 or prompt.shape[0] != z.shape[0] or prompt.shape[1] > steps:
-        raise ValueError("prompt: (%d, <= %d) tokens, got %s" % (z.shape[0], steps, tuple(prompt.shape)))
-    P = prompt.shape[1]
+    forced, P = _prompt_arg(z, steps, prompt)
     if P == 0:
         return greedy_decode(model, z, steps, want_logp, constraints=constraints)
-    forced = torch.zeros(z.shape[0], steps, dtype=prompt.dtype)
-    forced[:, :P] = prompt.cpu()
     res = greedy_decode(model, z, steps, want_logp, forced=forced, force=P, constraints=constraints)
     res[1][:, :P] = forced[:, :P].to(device=res[1].device, dtype=res[1].dtype)
     return res
@@ -167,27 +229,21 @@ def continue_from(model, z, prompt, steps, want_logp=True, constraints=None):
 def _sample_args(z, steps, temperature, top_k, top_p, seed, offset, prompt):
     """validated (the 32 bytes of FnSampleParams as a CPU uint8 tensor, prompt int32 (Bi, steps) on z's device or None, its prefix mask or None, P);
     ValueError before anything is launched"""
-    if not isinstance(steps, (int, np.integer)) or steps < 1:
-        raise ValueError("steps: a positive int, got %r" % (steps,))
+    _check_steps(steps)
     for name, v in (("temperature", temperature), ("top_p", top_p)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        if not _is_finite(v):
             raise ValueError("%s: a finite number, got %r" % (name, v))
     if not temperature > 0:
         raise ValueError("temperature > 0, got %r" % (temperature,))
     if not 0 < top_p <= 1:
         raise ValueError("0 < top_p <= 1, got %r" % (top_p,))
     for name, v, hi in (("top_k", top_k, 1 << 31), ("seed", seed, 1 << 64), ("offset", offset, 1 << 64)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < hi:
+        if not _is_int(v) or not 0 <= int(v) < hi:
             raise ValueError("%s: an int in [0, 2^%d), got %r" % (name, hi.bit_length() - 1, v))
     P, forced, mask = 0, None, None
     if prompt is not None:
-        prompt = prompt if torch.is_tensor(prompt) else torch.as_tensor(np.asarray(prompt))
-        if prompt.dim() != 2 or prompt.shape[0] != z.shape[0] or prompt.shape[1] > steps:
-            raise ValueError("prompt: (%d, <= %d) tokens, got %s" % (z.shape[0], steps, tuple(prompt.shape)))
-        P = prompt.shape[1]
+        full, P = _prompt_arg(z, steps, prompt)
         if P:
-            full = torch.zeros(z.shape[0], steps, dtype=prompt.dtype)
-            full[:, :P] = prompt.cpu()
             forced, mask = _forced_args(z, steps, full, P)
     with np.errstate(over="ignore"):
         inv_t = np.float32(1.0) / np.float32(temperature)          # the kernel clamps what fp32 cannot hold
@@ -229,36 +285,12 @@ def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, 
         cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
         logp, tokens = _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask, sample=params.to(z.device), con=cb)
     else:
-        cache = eng.__dict__.setdefault("_sample_graphs", {})
-        key = (z.shape[0], steps, bool(want_logp), P, z.shape[0] >= eng.cell_decode_rows, None if con is None else con.key(),
-               bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)), getattr(eng.ops, "cell_x6_rows", None),
-               bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)))
-        ent = cache.get(key)
-        if ent is None:
-            zs, ps = z.clone(), params.to(z.device)
-            fs = None if forced is None else forced.clone()
-            cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
-            tokens = torch.zeros(z.shape[0], steps, dtype=torch.int32, device=z.device)
-            logp = torch.empty(z.shape[0], steps, E_VOCAB, device=z.device) if want_logp else None
-            _decode_body(eng, zs, min(steps, 2), want_logp, logp, tokens, alloc_steps=steps, forced=fs, mask=mask, sample=ps, con=cb)   # warm-up, as greedy_decode
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            getattr(eng.ops, "begin_capture", lambda: None)()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                _decode_body(eng, zs, steps, want_logp, logp, tokens, forced=fs, mask=mask, sample=ps, con=cb)
-            ent = cache[key] = (g, zs, ps, fs, logp, tokens, cb)
-            prompted = [k for k in cache if k[3]]
-            if len(prompted) > MAX_MASKED_GRAPHS:         # as greedy_decode bounds its masked graphs: every prompt length owns static logp / tokens buffers
-                del cache[prompted[0]]
-        g, zs, ps, fs, logp, tokens, cb = ent
-        zs.copy_(z)
-        ps.copy_(params)
-        if fs is not None:
-            fs.copy_(forced)
-        if cb is not None:
-            load_constraints(cb, con, z.shape[0])
-        g.replay()
-        logp, tokens = (None if logp is None else logp.clone()), tokens.clone()
+        key = (z.shape[0], steps, bool(want_logp), P, z.shape[0] >= eng.cell_decode_rows, None if con is None else con.key(), *_arith_key(eng))
+        out, cb = _graph_replay(eng, eng.__dict__.setdefault("_sample_graphs", {}), key, lambda: _token_buffers(z, steps, want_logp, forced, params, con),
+                                lambda b, warm: _decode_body(eng, b["zs"], min(steps, 2) if warm else steps, want_logp, b["logp"], b["tokens"],
+                                                             alloc_steps=steps, forced=b["fs"], mask=mask, sample=b["ps"], con=b["cb"]),
+                                lambda k: k[3], dict(zs=z, ps=params, fs=forced), con)          # bounded: the graphs with a prompt, as greedy_decode's masked ones
+        logp, tokens = out["logp"], out["tokens"]
     if P:
         tokens[:, :P] = forced[:, :P]
     return (logp, tokens, constraint_stats(cb)) if con is not None and con.want_stats else (logp, tokens)
@@ -266,23 +298,21 @@ def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, 
 
 def _beam_args(steps, width, eos, length_penalty):
     """validated (W, eos as the kernels take it: -1 = none, length_penalty as a float); ValueError before anything is launched"""
-    if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)) or steps < 1:
-        raise ValueError("steps: a positive int, got %r" % (steps,))
-    if isinstance(width, (bool, np.bool_)) or not isinstance(width, (int, np.integer)) or not 1 <= int(width) <= BEAM_MAX_WIDTH:
+    _check_steps(steps, bools=False)
+    if not _is_int(width) or not 1 <= int(width) <= BEAM_MAX_WIDTH:
         raise ValueError("width: an int in [1, %d], got %r" % (BEAM_MAX_WIDTH, width))
-    if eos is not None and (isinstance(eos, (bool, np.bool_)) or not isinstance(eos, (int, np.integer)) or not 0 <= int(eos) < E_VOCAB):
+    if eos is not None and (not _is_int(eos) or not 0 <= int(eos) < E_VOCAB):
         raise ValueError("eos: None or a token in [0, %d), got %r" % (E_VOCAB, eos))
-    if (isinstance(length_penalty, (bool, np.bool_)) or not isinstance(length_penalty, (int, float, np.integer, np.floating))
-            or not np.isfinite(length_penalty)):
+    if not _is_finite(length_penalty):
         raise ValueError("length_penalty: a finite number, got %r" % (length_penalty,))
     return int(width), -1 if eos is None else int(eos), float(length_penalty)
 
 
-def _beam_buffers(z, W, steps, keep_logp):
-    """every tensor the beam loop writes, at its final size (nothing is allocated inside a capture)"""
+def _beam_buffers(z, W, steps, keep_logp, con=None):
+    """every tensor the beam loop writes, at its final size (nothing is allocated inside a capture); cb: the constraints' buffers, or None"""
     Bi, dev = z.shape[0], z.device
     i32 = dict(dtype=torch.int32, device=dev)
-    return dict(zs=z.clone(), score=torch.zeros(steps, Bi, W, device=dev), parent=torch.zeros(steps, Bi, W, **i32), token=torch.zeros(steps, Bi, W, **i32),
+    return dict(zs=z.clone(), cb=None if con is None else constraint_buffers(con, Bi, dev, repeat=W, gather=True), score=torch.zeros(steps, Bi, W, device=dev), parent=torch.zeros(steps, Bi, W, **i32), token=torch.zeros(steps, Bi, W, **i32),
                 rows=torch.empty(steps, Bi * W, E_VOCAB, device=dev) if keep_logp else None,
                 tokens=torch.zeros(Bi, W, steps, **i32), beam=torch.zeros(Bi, W, steps, **i32), cum=torch.zeros(Bi, W, steps, device=dev),
                 lens=torch.zeros(Bi, W, **i32), final=torch.zeros(Bi, W, device=dev))
@@ -300,20 +330,12 @@ def _beam_body(eng, bufs, W, steps, eos, run_steps=None, con=None):
     R = z.shape[0] * W
     zr = eng.buf("beam_z", (R, z.shape[1]))
     zr.view(z.shape[0], W, z.shape[1]).copy_(z.unsqueeze(1).expand(z.shape[0], W, z.shape[1]))
-    h0g = eng.buf("beam_h0g", (R, H))
-    ops.gemm(zr, P["linear_init_global.weight"], h0g, bias=P["linear_init_global.bias"])
-    rbg = eng.buf("beam_rbg", (R, 3 * H))
-    ops.gemm(zr, P["grucell_g.weight_ih"][:, E_VOCAB:], rbg)
+    h0g, rbg = _init_state(eng, zr, "beam_")
     cur0, cur1, nxt0, nxt1 = (eng.buf("beam_" + n, (R, H)) for n in ("cur0", "cur1", "nxt0", "nxt1"))
     logits = eng.buf("beam_logits", (R, LOGIT_LD))
     score, parent, token, rows = bufs["score"], bufs["parent"], bufs["token"], bufs["rows"]
     n = steps if run_steps is None else min(steps, run_steps)
-    held = None
-    if con is not None:
-        held = con["held"]
-        con["stuck"].zero_(), con["fixed"].zero_()
-        if held is not None:
-            held.zero_()
+    held = _reset_constraints(con)
     for i in range(n):
         ops.gru_cell(h0g if i == 0 else nxt0, P["grucell_g.weight_hh"], P["grucell_g.bias_hh"], cur0, b_ih=P["grucell_g.bias_ih"], gx_table=eng.tab["g"],
                      start_token=E_VOCAB - 1, gx_rowbias=rbg, idx=token[i - 1].view(-1) if i > 0 else None)
@@ -362,36 +384,17 @@ def beam_decode(model, z, steps, width=4, eos=None, length_penalty=0.0, want_log
     eng = model.engine()
     z = z.float().contiguous()
     keep = bool(want_logp or trace)
-    cb = None
     if use_graph is None:
         use_graph = z.is_cuda
     if not use_graph:
-        bufs = _beam_buffers(z, W, steps, keep)
-        cb = None if con is None else constraint_buffers(con, z.shape[0], z.device, repeat=W, gather=True)
+        bufs = _beam_buffers(z, W, steps, keep, con)
+        cb = bufs["cb"]
         _beam_body(eng, bufs, W, steps, eos_k, con=cb)
     else:
-        cache = eng.__dict__.setdefault("_beam_graphs", {})
-        key = (z.shape[0], W, steps, eos_k, keep, None if con is None else con.key(), bool(getattr(eng.ops, "dw_x6", False) and getattr(eng.ops, "cell_x6", False)),
-               getattr(eng.ops, "cell_x6_rows", None), bool(getattr(eng.ops, "x6_per_tile", False)), bool(getattr(eng.ops, "nt_x6", True)))
-        ent = cache.get(key)
-        if ent is None:
-            bufs = _beam_buffers(z, W, steps, keep)
-            cb = None if con is None else constraint_buffers(con, z.shape[0], z.device, repeat=W, gather=True)
-            _beam_body(eng, bufs, W, steps, eos_k, run_steps=2, con=cb)          # warm-up: every scratch buffer exists at its final size before the capture
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            getattr(eng.ops, "begin_capture", lambda: None)()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                _beam_body(eng, bufs, W, steps, eos_k, con=cb)
-            ent = cache[key] = (g, bufs, cb)
-            if len(cache) > MAX_MASKED_GRAPHS:        # every entry owns static slabs (and log-prob rows): the oldest goes
-                del cache[next(iter(cache))]
-        g, bufs, cb = ent
-        bufs["zs"].copy_(z)
-        if cb is not None:
-            load_constraints(cb, con, z.shape[0], repeat=W)
-        g.replay()
-        bufs = {k: (None if v is None else v.clone()) for k, v in bufs.items()}
+        key = (z.shape[0], W, steps, eos_k, keep, None if con is None else con.key(), *_arith_key(eng))
+        bufs, cb = _graph_replay(eng, eng.__dict__.setdefault("_beam_graphs", {}), key, lambda: _beam_buffers(z, W, steps, keep, con),
+                                 lambda b, warm: _beam_body(eng, b, W, steps, eos_k, run_steps=2 if warm else None, con=b["cb"]),
+                                 lambda k: True, dict(zs=z), con, repeat=W)          # bounded: all of them, every entry owns static slabs (and log-prob rows)
     tokens, scores, lens, beam = bufs["tokens"], bufs["final"], bufs["lens"], bufs["beam"]
     Bi = z.shape[0]
     order = torch.arange(W, device=z.device).view(1, W).expand(Bi, W)
@@ -422,10 +425,7 @@ def _decode_single_launch(eng, z, steps, want_logp, forced=None, mask=None):
     timed out waiting for a hand-over: the caller then takes the per-token path."""
     ops, P, H = eng.ops, eng.p, eng.H
     Bi = z.shape[0]
-    h0g = eng.buf("dec_h0g", (Bi, H))
-    ops.gemm(z, P["linear_init_global.weight"], h0g, bias=P["linear_init_global.bias"])
-    rbg = eng.buf("dec_rbg", (Bi, 3 * H))
-    ops.gemm(z, P["grucell_g.weight_ih"][:, E_VOCAB:], rbg)
+    h0g, rbg = _init_state(eng, z, "dec_")
     tokens = torch.zeros(Bi, steps, dtype=torch.int32, device=z.device)
     logp = torch.empty(Bi, steps, E_VOCAB, device=z.device) if want_logp else None
     # forced feedback (fn_decode_forced): the mask travels as device bytes, the kernel reads it step by step
@@ -457,10 +457,7 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
         logp = torch.empty(Bi, steps, E_VOCAB, device=dev)
     hx0 = [eng.buf("dec_hx0_a", (1, Bi, H)), eng.buf("dec_hx0_b", (1, Bi, H))]
     hx1 = [eng.buf("dec_hx1_a", (1, Bi, H)), eng.buf("dec_hx1_b", (1, Bi, H))]
-    h0g = eng.buf("dec_h0g", (Bi, H))
-    ops.gemm(z, P["linear_init_global.weight"], h0g, bias=P["linear_init_global.bias"])
-    rbg = eng.buf("dec_rbg", (Bi, 3 * H))
-    ops.gemm(z, P["grucell_g.weight_ih"][:, E_VOCAB:], rbg)
+    h0g, rbg = _init_state(eng, z, "dec_")
     gx2 = eng.buf("dec_gx2", (1, Bi, 3 * H))
     logits = eng.buf("dec_logits", (Bi, LOGIT_LD))
     # every cell also leaves its new state in the MFMA operand layout, which the next cell call takes as h0_frag: no packing launches
@@ -468,12 +465,7 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
     hf0 = [eng.buf("dec_hf0_a", (nf,)), eng.buf("dec_hf0_b", (nf,))]
     hf1 = [eng.buf("dec_hf1_a", (nf,)), eng.buf("dec_hf1_b", (nf,))]
 
-    held = None
-    if con is not None:
-        held = con["held"]
-        con["stuck"].zero_(), con["fixed"].zero_()
-        if held is not None:
-            held.zero_()
+    held = _reset_constraints(con)
 
     def head(i):
         if con is not None:
