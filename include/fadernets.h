@@ -759,6 +759,76 @@ int fn_notes_stitch(const FnNote* dec, int dec_rs, int dec_ld, const int32_t* de
                     int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Latent-side work in front of a decode (latent.py): a draw from the mixture prior and a mix of two pieces' latents.  OURS; the reference has
+ * the prior's tables (gmm_model.py:151-183) and the class posterior (approx_qy_x, :194-218) but neither samples the one nor interpolates.  The
+ * text below is the specification.  Both entry points are additive: fn_version() stays 6.
+ *
+ * fn_latent_draw: z ~ N(mu_lk[k], (tau * exp(lv_lk[k] / 2))^2) for `rows` rows, up to FN_DRAW_MAX_JOBS jobs in ONE launch (jobs is a HOST array,
+ * read by value; the 32 bytes of params_dev are read from DEVICE memory, so a captured graph serves any seed).  The usual two jobs write z_r into
+ * columns [0, Z) and z_n into columns [Z, 2Z) of the decode's own (rows, 2Z+24) rows: a job writes z[b*z_ld + j] for j in [0, Z) and touches no
+ * other column.  For job s, row b, column j, with q = j / 4:
+ *   1. w[0..3] = Philox4x32-10(counter = (b, (stream_id << 16) | q, offset_lo, offset_hi), key = (seed_lo, seed_hi)), the rounds of fn_vocab_sample
+ *      (counter 0, key 0: 6627e8d5 e169c58d bc57ac4c 9b00dbd8).
+ *   2. Box-Muller, two pairs per quad.  For h = 0, 1: ua = ((w[2h] >> 8) + 1) * 2^-24 in (0, 1], ub = (w[2h+1] >> 8) * 2^-24 in [0, 1),
+ *      r = sqrtf(-2 logf(ua)), n[4q+2h] = r * cospif(2 ub), n[4q+2h+1] = r * sinpif(2 ub) - cos / sin of pi x, as 2 ub is exact in fp32.  A last
+ *      quad with fewer than 4 columns drops the rest.  |n| <= sqrt(48 ln 2) = 5.77.
+ *   3. The component: k = min(comp[b], K - 1) where comp is given and comp[b] >= 0; otherwise drawn uniformly from the row's own counter
+ *      (b, (stream_id << 16) | 0xFFFF, offset_lo, offset_hi): k = ((w'[0] >> 8) * K) >> 24 in 64-bit integers, which is floor(u * K) for
+ *      u = (w'[0] >> 8) * 2^-24 without a rounding.  comp_out[b] = k when given.
+ *   4. eps = n[j];  z[b*z_ld + j] = mu_lk[k][j] + (tau * expf(0.5f * lv_lk[k][j])) * eps;  eps_out[b*Z + j] = eps when given.
+ * tau comes from memory and is clamped to [0, FLT_MAX], NaN -> 1; tau = 0 gives the component mean itself.  A row's numbers depend on (b, j,
+ * stream_id, seed, offset) only - not on rows, n_jobs or the launch geometry.  One thread per (row, quad); no LDS.
+ *   NULL jobs, params_dev, or a job's mu_lk, lv_lk or z: FN_E_NULL (answered first);  n_jobs outside [1, FN_DRAW_MAX_JOBS]: FN_E_COUNT;  rows < 1,
+ *   Z < 1, z_ld < Z, a K < 1, a stream_id outside [0, 65535): FN_E_SHAPE;  Z > FN_DRAW_MAX_Z, a K > FN_DRAW_MAX_K, rows * ceil(Z / 4) >= 2^31:
+ *   FN_E_UNSUPPORTED;  a pointer that is not 4-byte aligned: FN_E_ALIGN;  in this order, all before any launch.
+ *
+ * fn_latent_mix: out row i*P + p (row stride out_ld >= D) is the mix of a[i] and b[i] (row stride ab_ld >= D) at tt = t[p], or t[i*P + p] with
+ * t_per_pair != 0; a, b, t in DEVICE memory, segs a HOST array read by value.  tt is any finite value (outside [0, 1]: extrapolation).  The
+ * segments are disjoint slices [off, off + len) of [0, D), each slice of each pair mixed on its own; columns in no segment are written as a's,
+ * columns [D, out_ld) are not touched.  out must not overlap a or b.  Per segment mode:
+ *   FN_MIX_LERP   out = fmaf(tt, b, (1.0f - tt) * a)
+ *   FN_MIX_STEP   out = tt < 0.5f ? a : b                                (the chroma columns: halfway between two keys is not a key)
+ *   FN_MIX_SLERP  saa = sum a^2, sbb = sum b^2, sab = sum ab over the slice in fp32; na = sqrtf(saa), nb = sqrtf(sbb);
+ *                 c = clamp((float)((double)sab / sqrt((double)saa * (double)sbb)), -1, 1) - the cosine sab / (na * nb) with product, root and quotient
+ *                 in fp64 and ONE rounding, so that a == b gives c = 1 and a == -b gives c = -1 exactly (the fp32 product na * nb exceeds saa by an
+ *                 ulp for about every fourth vector, and the angle of a vector with itself would come out as 4.9e-4);  w = acosf(c), s = sinf(w);
+ *                 na == 0, nb == 0, s < FN_MIX_MIN_SIN or s NaN: the slice of this pair is mixed as FN_MIX_LERP; otherwise
+ *                 wa = sinf((1.0f - tt) * w) / s, wb = sinf(tt * w) / s, out = fmaf(wb, b, wa * a)   (the raw vectors, as MusicVAE-style models do)
+ * omega_out[i*n_segs + g], when given: w of segment g; 0 where the segment is not FN_MIX_SLERP, -1 where the fallback was taken.  In every mode
+ * tt == 0 returns a's values and tt == 1 b's exactly (sinf(w) / s is s / s).  The sums are fp32, lane-strided and reduced by an xor butterfly
+ * inside one wavefront; one wavefront owns a pair and loops over its P points; no atomics, no LDS, no hand-over between workgroups.
+ *   NULL a, b, t, segs or out: FN_E_NULL;  n_segs outside [1, FN_MIX_MAX_SEGS]: FN_E_COUNT;  pairs, D or P < 1, ab_ld or out_ld < D, a segment
+ *   with len < 1, one that leaves [0, D), overlaps another or has an unknown mode: FN_E_SHAPE;  pairs * P >= 2^31: FN_E_UNSUPPORTED;  a, b, t, out
+ *   or omega_out not 4-byte aligned: FN_E_ALIGN;  in this order, all before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_DRAW_MAX_JOBS 4
+#define FN_DRAW_MAX_Z 4096
+#define FN_DRAW_MAX_K 1024
+typedef struct FnDrawParams {      /* 32 bytes, read from DEVICE memory like FnSampleParams */
+    uint32_t seed_lo, seed_hi;     /* the Philox key: a 64-bit seed                                                  */
+    uint32_t offset_lo, offset_hi; /* counter words 2, 3: a 64-bit offset                                            */
+    float tau;                     /* scale of the component's sigma; NaN -> 1, clamped to [0, FLT_MAX]              */
+    int32_t reserved[3];           /* 0                                                                              */
+} FnDrawParams;
+typedef struct FnDrawJob {         /* host memory, by value, like FnBeamGatherJob */
+    const float *mu_lk, *lv_lk;    /* [K][Z]                                                                         */
+    const int32_t* comp;           /* [rows] or NULL                                                                 */
+    float* z;                      /* row stride z_ld (>= Z)                                                         */
+    float* eps_out;                /* [rows][Z] or NULL                                                              */
+    int32_t* comp_out;             /* [rows] or NULL                                                                 */
+    int32_t K, stream_id;          /* stream_id in [0, 65535)                                                        */
+} FnDrawJob;
+int fn_latent_draw(const FnDrawJob* jobs, int n_jobs, int rows, int Z, int64_t z_ld, const FnDrawParams* params_dev, void* stream);
+#define FN_MIX_LERP 0
+#define FN_MIX_SLERP 1
+#define FN_MIX_STEP 2
+#define FN_MIX_MAX_SEGS 4
+#define FN_MIX_MIN_SIN 1e-4f
+typedef struct FnMixSeg { int32_t off, len, mode, reserved; } FnMixSeg;   /* host memory, by value */
+int fn_latent_mix(const float* a, const float* b, int64_t ab_ld, int pairs, int D, const float* t, int P, int t_per_pair,
+                  const FnMixSeg* segs, int n_segs, float* out, int64_t out_ld, float* omega_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Reconstruction report (report.py, epochs.evaluation_phase): what the reference's evaluation_phase() computes behind its loss terms
  * (trainer_gmm.py:470-610) - the accuracies.  The reference's: `torch.argmax(a, dim=-1)` (:546) and the per-sample loop of acc() with its
  * np.trim_zeros cut (:549-565).  OURS: the negative log-likelihood and the rank of the target per token, which re-ranking decoded hypotheses

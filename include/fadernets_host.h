@@ -73,6 +73,10 @@ int fn_constrain_advance_host(int32_t* tok_io, int tok_ld, int rows, int V, cons
 int fn_notes_stitch_host(const FnNote* dec, int dec_rs, int dec_ld, const int32_t* dec_n, const int32_t* dec_end, const FnNote* src, int n_total,
                          const FnNoteSpan* spans, int S, int V, const int32_t* mode, FnNote* out, int out_ld, int32_t* win_first, int32_t* out_n,
                          int32_t* status, void* stream);                                                 /* fn_notes_stitch */
+/* prior draw, latent mix */
+int fn_latent_draw_host(const FnDrawJob* jobs, int n_jobs, int rows, int Z, int64_t z_ld, const FnDrawParams* params, void* stream);   /* fn_latent_draw */
+int fn_latent_mix_host(const float* a, const float* b, int64_t ab_ld, int pairs, int D, const float* t, int P, int t_per_pair,
+                       const FnMixSeg* segs, int n_segs, float* out, int64_t out_ld, float* omega_out, void* stream);                 /* fn_latent_mix */
 size_t fn_frag_floats_host(int rows, int K);                                                            /* fn_frag_floats */
 size_t fn_gru_gates_floats_host(int B, int H);                                                           /* fn_gru_gates_floats */
 

@@ -43,6 +43,9 @@ FN_ATTR_EMPTY, FN_ATTR_OVERFLOW = 1, 2
 FN_NOTES_MAX, FN_NOTES_MAX_TICK = 512, 1 << 22
 FN_NOTES_EMPTY, FN_NOTES_OVERFLOW = 1, 2
 FN_STITCH_MAX_S, FN_STITCH_MAX_V, FN_STITCH_MAX_OUT = 1 << 16, 64, 1 << 24
+FN_DRAW_MAX_JOBS, FN_DRAW_MAX_Z, FN_DRAW_MAX_K = 4, 4096, 1024
+FN_MIX_LERP, FN_MIX_SLERP, FN_MIX_STEP = 0, 1, 2
+FN_MIX_MAX_SEGS, FN_MIX_MIN_SIN = 4, 1e-4
 FN_MATCH_EMPTY = 1
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
@@ -136,6 +139,19 @@ class FnNoteParams(C.Structure):
                 ("add_eos", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class FnDrawParams(C.Structure):
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("offset_lo", C.c_uint32), ("offset_hi", C.c_uint32), ("tau", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class FnDrawJob(C.Structure):
+    _fields_ = [("mu_lk", vp), ("lv_lk", vp), ("comp", vp), ("z", vp), ("eps_out", vp), ("comp_out", vp), ("K", C.c_int32), ("stream_id", C.c_int32)]
+
+
+class FnMixSeg(C.Structure):
+    _fields_ = [("off", C.c_int32), ("len", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/fadernets.h
 SIGNATURES = {
     "fn_version": (C.c_int, []),
@@ -193,6 +209,8 @@ SIGNATURES = {
     "fn_notes_from_tokens": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "fn_tokens_from_notes": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "fn_notes_stitch": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "fn_latent_draw": (C.c_int, [C.POINTER(FnDrawJob), C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
+    "fn_latent_mix": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FnMixSeg), C.c_int, vp, C.c_int64, vp, vp]),
     "fn_token_score": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]),
     "fn_match_rows": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),

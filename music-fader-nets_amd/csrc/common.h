@@ -146,6 +146,19 @@ __device__ __forceinline__ FnRowHead fn_row_head(const float* __restrict__ x, in
     return h;
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four words.  The draws of fn_vocab_sample and fn_latent_draw both come from here;
+// host/sample_host.h has the same rounds in plain C++.
+__device__ __forceinline__ void fn_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // pack(x, v) over V columns: order-preserving key of x in the high half, V - 1 - v in the low half, so the 64-bit maximum is the largest x and, among
 // equals, the lowest column (fn_out_argmax_f32, fn_beam_step)
 __device__ __forceinline__ unsigned long long fn_pack_best(float x, int v, int V) {

@@ -11,6 +11,7 @@
 #include "sample_host.h"
 #include "constrain_host.h"
 #include "notes_host.h"
+#include "latent_ops_host.h"
 
 namespace {
 
@@ -580,6 +581,15 @@ int fn_notes_stitch_host(const FnNote* dec, int dec_rs, int dec_ld, const int32_
                          const FnNoteSpan* spans, int S, int V, const int32_t* mode, FnNote* out, int out_ld, int32_t* win_first, int32_t* out_n,
                          int32_t* status, void*) {
     return fn_notes_host::notes_stitch(dec, dec_rs, dec_ld, dec_n, dec_end, src, n_total, spans, S, V, mode, out, out_ld, win_first, out_n, status);
+}
+
+int fn_latent_draw_host(const FnDrawJob* jobs, int n_jobs, int rows, int Z, int64_t z_ld, const FnDrawParams* params, void*) {
+    return fn_latent_host::latent_draw(jobs, n_jobs, rows, Z, z_ld, params);
+}
+
+int fn_latent_mix_host(const float* a, const float* b, int64_t ab_ld, int pairs, int D, const float* t, int P, int t_per_pair, const FnMixSeg* segs,
+                       int n_segs, float* out, int64_t out_ld, float* omega_out, void*) {
+    return fn_latent_host::latent_mix(a, b, ab_ld, pairs, D, t, P, t_per_pair, segs, n_segs, out, out_ld, omega_out);
 }
 
 size_t fn_decode_ws_bytes_host(int B, int H, int) { return (size_t)4 * B * H * sizeof(float) + 16; }

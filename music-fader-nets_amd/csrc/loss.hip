@@ -71,17 +71,6 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float* __restri
 // _sampling is the argmax above).  Geometry of vocab_argmax_kernel: one wavefront per row, 4 rows per workgroup, lane l holds e = l, l+64, ...
 // LDS per wavefront: V floats + V indices.  The wavefronts of a workgroup are independent but walk the same barriers, so a wavefront past
 // the last row works on row B-1 again and stores nothing.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 template <int NE>      // entries per lane: V <= 64 NE
 __global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restrict__ logits, int B, int E, int ld,
                                                            const FnSampleParams* __restrict__ params, int step, float* __restrict__ logp_out,
@@ -175,7 +164,7 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restri
     }
     // 6. the draw: u in [0, 1) from Philox4x32-10 on (row, step, offset), keyed by the seed; j = #{j < m : not c[j] > u c[m-1]}
     uint32_t r4[4];
-    philox4x32_10((uint32_t)b, (uint32_t)step, pr.offset_lo, pr.offset_hi, pr.seed_lo, pr.seed_hi, r4);
+    fn_philox4x32_10((uint32_t)b, (uint32_t)step, pr.offset_lo, pr.offset_hi, pr.seed_lo, pr.seed_hi, r4);
     const float u = (float)(r4[0] >> 8) * 0x1p-24f;
     const float t = u * sf[m - 1];
     int notabove = 0;

@@ -760,6 +760,48 @@ class HipOps:
         _lib.check(self.lib.fn_notes_stitch(_p(dec), rs, int(dec_ld), _p(dec_n), _p(dec_end), _p(src) if src.shape[0] else None, src.shape[0], _p(spans), S, V,
                                             _p(mode), _p(out), out.shape[1], _p(win_first), _p(out_n), _p(status), self.stream()), "fn_notes_stitch")
 
+    def latent_draw(self, jobs, params):
+        """fn_latent_draw: jobs = up to 4 dicts of mu_lk, lv_lk (contiguous fp32 [K][Z]), z (a 2-D fp32 view [rows][Z] with unit inner stride; all jobs
+        share its row stride), stream_id and optionally comp, comp_out (contiguous int32 [rows]) and eps_out (contiguous fp32 [rows][Z]); params: the
+        32 bytes of FnDrawParams on the device"""
+        _dense(params, torch.uint8, "params")
+        if params.numel() != C.sizeof(_lib.FnDrawParams) or not 1 <= len(jobs) <= _lib.FN_DRAW_MAX_JOBS:
+            raise RuntimeError("latent_draw: 1..%d jobs and %d parameter bytes, got %d and %d" % (
+                _lib.FN_DRAW_MAX_JOBS, C.sizeof(_lib.FnDrawParams), len(jobs), params.numel()))
+        arr = (_lib.FnDrawJob * len(jobs))()
+        pz, rows, Z, z_ld = _mat(jobs[0]["z"], "z")
+        for j, d in zip(arr, jobs):
+            pz, r, zc, ld = _mat(d["z"], "z")
+            mu, lv, comp, eps_out, comp_out = d["mu_lk"], d["lv_lk"], d.get("comp"), d.get("eps_out"), d.get("comp_out")
+            _dense(mu, name="mu_lk"), _dense(lv, name="lv_lk"), _dense(comp, torch.int32, "comp"), _dense(eps_out, name="eps_out")
+            _dense(comp_out, torch.int32, "comp_out")
+            if (r, zc, ld) != (rows, Z, z_ld) or mu.dim() != 2 or mu.shape[1] != Z or lv.shape != mu.shape or any(
+                    t is not None and t.numel() != n for t, n in ((comp, rows), (comp_out, rows), (eps_out, rows * Z))):
+                raise RuntimeError("latent_draw: every job writes (%d, %d) at a row stride of %d from [K][%d] tables; comp, comp_out of %d, eps_out of %d "
+                                   "entries" % (rows, Z, z_ld, Z, rows, rows * Z))
+            j.mu_lk, j.lv_lk, j.comp, j.z, j.eps_out, j.comp_out, j.K, j.stream_id = (
+                mu.data_ptr(), lv.data_ptr(), None if comp is None else comp.data_ptr(), d["z"].data_ptr(), None if eps_out is None else eps_out.data_ptr(),
+                None if comp_out is None else comp_out.data_ptr(), mu.shape[0], int(d["stream_id"]))
+        _lib.check(self.lib.fn_latent_draw(arr, len(jobs), rows, Z, z_ld, _p(params), self.stream()), "fn_latent_draw")
+
+    def latent_mix(self, a, b, t, segs, out, omega_out=None, per_pair=False):
+        """fn_latent_mix: a, b 2-D fp32 views [pairs][D] sharing a row stride; t contiguous fp32 [P], or [pairs][P] with per_pair; segs: up to 4
+        (off, len, mode); out a 2-D fp32 view [pairs*P][D]; omega_out contiguous fp32 [pairs][len(segs)] or None"""
+        pa, pairs, D, ld = _mat(a, "a")
+        pb, rb, cb, ldb = _mat(b, "b")
+        po, ro, co, ldo = _mat(out, "out")
+        _dense(t, name="t"), _dense(omega_out, name="omega_out")
+        P = t.numel() // pairs if per_pair else t.numel()
+        if (rb, cb, ldb) != (pairs, D, ld) or P < 1 or t.numel() != (pairs * P if per_pair else P) or (ro, co) != (pairs * P, D) or not (
+                1 <= len(segs) <= _lib.FN_MIX_MAX_SEGS) or (omega_out is not None and omega_out.numel() != pairs * len(segs)):
+            raise RuntimeError("latent_mix: a%s b%s (strides %d, %d) t%s out%s for %d segments" % (
+                tuple(a.shape), tuple(b.shape), ld, ldb, tuple(t.shape), tuple(out.shape), len(segs)))
+        arr = (_lib.FnMixSeg * len(segs))()
+        for s, (off, n, mode) in zip(arr, segs):
+            s.off, s.len, s.mode, s.reserved = int(off), int(n), int(mode), 0
+        _lib.check(self.lib.fn_latent_mix(pa, pb, ld, pairs, D, _p(t), P, 1 if per_pair else 0, arr, len(segs), po, ldo, _p(omega_out), self.stream()),
+                   "fn_latent_mix")
+
     def sweep_scores(self, r, n, status, values, which, r_std, n_std, scores, n_used):
         """fn_sweep_scores: r, n fp32 and status int32 contiguous [S][Vn]; values fp64 [Vn]; scores fp64 [4]; n_used int32 [1]"""
         _dense(r, name="r"), _dense(n, name="n"), _dense(status, torch.int32, "status"), _dense(values, torch.float64, "values")
