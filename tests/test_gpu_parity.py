@@ -2318,7 +2318,7 @@ def test_weight_images_one_launch(ops):
     assert torch.equal(f1, r1) and torch.equal(f2, r2) and torch.equal(f3, r3)
 
 
-@pytest.mark.parametrize("a_k,b_k", [(True, True), (True, False), (False, False)])
+@pytest.mark.parametrize("a_k,b_k", [(True, True), (True, False), (False, False), (False, True)])
 def test_gemm_multi(ops, a_k, b_k):
     """several small GEMMs, each a sum of products over separate operands, in one launch (odd sizes, strided views, beta, bias)"""
     torch.manual_seed(77)
