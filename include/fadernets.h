@@ -91,6 +91,41 @@ int fn_gemm_f32(int a_kmajor, int b_kmajor, int M, int N, int K, float alpha,
                 const float* A, int lda, const float* B, int ldb, float beta, float* C, int ldc,
                 const float* bias, int splitk, float* ws, size_t ws_bytes, void* stream);
 
+/* The launch plan of fn_gemm_f32: which kernel instance the call launches, over which K ranges, on which grid, and which slab reduction follows.
+ * It is decided by ONE pure host function (csrc/gemm_plan.h: shapes, leading dimensions, the alignment of the addresses, the flag bits and the number
+ * of compute units in; this struct out) that fn_gemm_f32 launches from and that fn_gemm_plan hands out, so that a test asks the library what a call
+ * reaches instead of restating the decision.  The addresses are inspected for their alignment only and never dereferenced (NULL counts as aligned);
+ * `splitk` carries the FN_GEMM_* bits exactly as for fn_gemm_f32; cus > 0 stands for the compute units of the device (nothing touches the device
+ * then), cus == 0 asks the current device.  FN_E_NULL without `plan`, FN_E_SHAPE for sizes fn_gemm_f32 refuses or cus < 0.
+ * Both entry points are additive: fn_version() stays 6. */
+enum FnGemmKernel {              /* FnGemmPlan.kernel; the names of the instances in this order: _lib.GEMM_PLAN_KERNELS */
+    FN_PLAN_STAGED_64_64_16 = 0, /* gemm_kernel<BM, BN, BK, ..>: the LDS-staged kernel */
+    FN_PLAN_STAGED_64_64_32,
+    FN_PLAN_STAGED_32_64_32,
+    FN_PLAN_STAGED_64_16_16,
+    FN_PLAN_STAGED_128_128_32,
+    FN_PLAN_NT_DIRECT_4_2,       /* gemm_nt_direct_kernel<PF, WGS>: the LDS-free Linear-forward kernel */
+    FN_PLAN_NT_DIRECT_1_4,
+    FN_PLAN_NT_X6W,              /* gemm_nt_x6w_kernel */
+    FN_PLAN_TN,                  /* gemm_tn_kernel */
+    FN_PLAN_TN_LEAN,             /* gemm_tn_lean_kernel */
+    FN_PLAN_TN_X6,               /* gemm_tn_x6_kernel (FN_GEMM_X6_PERWAVE) */
+    FN_PLAN_TN_X6W,              /* gemm_tn_x6w_kernel */
+    FN_PLAN_TN_X6V,              /* gemm_tn_x6v_kernel (FN_GEMM_X6_WIDE) */
+    FN_PLAN_KERNELS
+};
+enum FnGemmReduce { FN_PLAN_REDUCE_NONE = 0, FN_PLAN_REDUCE_SLAB = 1 /* slab_reduce_kernel */, FN_PLAN_REDUCE_SLAB4 = 2 /* slab_reduce4_kernel */ };
+typedef struct FnGemmPlan {
+    int32_t kernel;                 /* FnGemmKernel */
+    int32_t klen, ranges;           /* K ranges of klen rows (the last one may be short): (ranges - 1) klen < K <= ranges klen */
+    int32_t grid_x, grid_y, grid_z; /* tiles x 1 x ranges, or 1-D: tiles * ranges workgroups, or as many as compute units that walk those items */
+    int32_t tiles;                  /* output tiles of the instance's tile shape */
+    int32_t reduce, reduce_blocks;  /* FnGemmReduce (one exists exactly when ranges > 1) and its grid */
+    int32_t msplit;                 /* fn_gru_dwhh_f32 as one launch: rows of the output from here on come from the second source (0: one source) */
+} FnGemmPlan;
+int fn_gemm_plan(int a_kmajor, int b_kmajor, int M, int N, int K, int lda, int ldb, int ldc, const void* A, const void* B, const void* C,
+                 const void* bias, const void* ws, int splitk, int cus, FnGemmPlan* plan);
+
 /* Up to 12 small independent GEMMs in ONE launch, each the sum of up to 4 products over separate operands (the heads of the path are
  * chains of 256-row GEMMs: e.g. mu_r = [h_fwd | h_rev] W^T is two products into one output, gmm_model.py:85-86):
  *   C_j[M,N] = sum_i opA(A_ji) opB(B_ji) + beta_j * C_j + bias_j      (a_kmajor / b_kmajor as in fn_gemm_f32, shared by all jobs) */
@@ -334,6 +369,11 @@ int fn_gru_bwd_x6_ok(const FnGruBwd* scans, int n_scans);
 size_t fn_gru_dwhh_ws_bytes(int H, int splitk);
 int fn_gru_dwhh_f32(const float* dgx, const float* dghn, const float* hprev, int64_t rows, int H, float beta, float* dW,
                     int splitk, float* ws, size_t ws_bytes, void* stream);
+/* The launch plan of fn_gru_dwhh_f32 (see fn_gemm_plan; same treatment of the addresses and of cus): *n_launches = 1 and plans[0] with
+ * msplit = 2H for the one split-A launch, or *n_launches = 2 and the plans of the two products - rows [0, 2H) of dW from dgx, rows [2H, 3H) from
+ * dghn -, which do not carry FN_GEMM_LEAN on.  FN_E_NULL without n_launches / plans, FN_E_SHAPE as fn_gru_dwhh_f32 or for cus < 0. */
+int fn_gru_dwhh_plan(const void* dgx, const void* dghn, const void* hprev, const void* dW, const void* ws, int64_t rows, int H, int splitk, int cus,
+                     int32_t* n_launches, FnGemmPlan plans[2]);
 
 /* Gradient of the one-hot columns of W_ih (autograd of  onehot(x) @ W_ih[:, :V]^T, gmm_model.py:84,89,109,114,132-133):
  *   dTable[v][:] = sum over (p,b) with tok(p,b)==v of dgx_all[p][b][:]      (tok defined as in FnGruFwd)

@@ -17,6 +17,11 @@ GEMM_X6_WIDE = 0x80000       # FN_GEMM_X6_WIDE (128 x 256 output tiles per workg
 GEMM_X6_PERTILE = 0x100000   # FN_GEMM_X6_PERTILE (tests / A-B: one workgroup per tile / (tile, K range) item instead of one per CU walking its items)
 GEMM_X6_PERWAVE = 0x40000    # FN_GEMM_X6_PERWAVE (tests / A-B: the round-5 kernel, every wavefront splits its own operands)
 # FnGruFwd / FnGruBwd / FnGruCell .variant bits (FN_GRU_* in include/fadernets.h)
+# FnGemmPlan.kernel -> the kernel instance (enum FnGemmKernel of include/fadernets.h, in its order) and FnGemmPlan.reduce -> the slab reduction
+GEMM_PLAN_KERNELS = ("gemm_kernel<64,64,16>", "gemm_kernel<64,64,32>", "gemm_kernel<32,64,32>", "gemm_kernel<64,16,16>", "gemm_kernel<128,128,32>",
+                     "gemm_nt_direct_kernel<4, 2>", "gemm_nt_direct_kernel<1, 4>", "gemm_nt_x6w_kernel", "gemm_tn_kernel", "gemm_tn_lean_kernel",
+                     "gemm_tn_x6_kernel", "gemm_tn_x6w_kernel", "gemm_tn_x6v_kernel")
+GEMM_PLAN_REDUCES = (None, "slab_reduce_kernel", "slab_reduce4_kernel")
 GRU_ROWS_MASK = 0xFF         # forced rows per workgroup (scans) / forced form 1-18 (cells)
 GRU_ALT_TILING = 0x100       # the alternative wave tiling of the 64-row configuration
 GRU_SYNC_ZEROED = 0x200      # the sync_ws counters are already zero
@@ -78,6 +83,16 @@ class FnGemmSeg(C.Structure):
 class FnGemmJob(C.Structure):
     _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("seg", FnGemmSeg * 4), ("n_seg", C.c_int32), ("beta", C.c_float), ("C", vp),
                 ("ldc", C.c_int32), ("bias", vp)]
+
+
+class FnGemmPlan(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("klen", C.c_int32), ("ranges", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32),
+                ("tiles", C.c_int32), ("reduce", C.c_int32), ("reduce_blocks", C.c_int32), ("msplit", C.c_int32)]
+
+    def as_dict(self):
+        """kernel and reduce by name, grid as (x, y, z)"""
+        return dict(kernel=GEMM_PLAN_KERNELS[self.kernel], klen=self.klen, ranges=self.ranges, grid=(self.grid_x, self.grid_y, self.grid_z), tiles=self.tiles,
+                    reduce=GEMM_PLAN_REDUCES[self.reduce], reduce_blocks=self.reduce_blocks, msplit=self.msplit)
 
 
 class FnColsumJob(C.Structure):
@@ -160,6 +175,8 @@ SIGNATURES = {
     "fn_gemm_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "fn_gemm_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int,
                               C.c_float, vp, C.c_int, vp, C.c_int, vp, C.c_size_t, vp]),
+    "fn_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int,
+                               C.POINTER(FnGemmPlan)]),
     "fn_gemm_multi": (C.c_int, [C.c_int, C.c_int, C.POINTER(FnGemmJob), C.c_int, vp]),
     "fn_transpose_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "fn_colsum_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
@@ -185,6 +202,7 @@ SIGNATURES = {
     "fn_decode_forced": (C.c_int, [C.POINTER(FnDecode), C.POINTER(FnDecodeForce), vp]),
     "fn_gru_dwhh_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "fn_gru_dwhh_f32": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_size_t, vp]),
+    "fn_gru_dwhh_plan": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(FnGemmPlan)]),
     "fn_embed_grad_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "fn_embed_grad_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     vp, vp, C.c_size_t, vp]),

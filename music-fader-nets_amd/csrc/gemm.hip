@@ -5,6 +5,7 @@
 #include <utility>
 
 #include "common.h"
+#include "gemm_plan.h"
 #include "mma_core.h"
 #include "x6w_core.h"
 
@@ -1291,13 +1292,10 @@ __global__ void slab_reduce4_kernel(const float* __restrict__ slabs, int S, int 
     }
 }
 
-// split-K slabs -> C (the float4 form where everything is 16-byte aligned; same summation order per element)
-static void launch_slab_reduce(hipStream_t st, const float* slabs, int S, int M, int N, float alpha, float beta, float* C, long ldc, const float* bias) {
-    const bool v4 = (N & 3) == 0 && (ldc & 3) == 0 && (((((uintptr_t)slabs) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) == 0);
-    const long total = v4 ? (long)M * N / 4 : (long)M * N;
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    if (v4) hipLaunchKernelGGL(slab_reduce4_kernel, dim3(blocks), dim3(256), 0, st, slabs, S, M, N, alpha, beta, C, ldc, bias);
-    else hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, slabs, S, M, N, alpha, beta, C, ldc, bias);
+// split-K slabs -> C: the reduction the plan names
+static void launch_slab_reduce(const FnGemmPlan& p, hipStream_t st, const float* slabs, int M, int N, float alpha, float beta, float* C, long ldc, const float* bias) {
+    hipLaunchKernelGGL(p.reduce == FN_PLAN_REDUCE_SLAB4 ? slab_reduce4_kernel : slab_reduce_kernel, dim3(p.reduce_blocks), dim3(256), 0, st, slabs, p.ranges, M, N,
+                       alpha, beta, C, ldc, bias);
 }
 
 __global__ void transpose_kernel(const float* __restrict__ src, int R, int Cc, long src_ld, float* __restrict__ dst, long dst_ld) {
@@ -1384,33 +1382,77 @@ __global__ void sum_kernel(const float* __restrict__ x, long n, float scale, flo
     }
 }
 
-template <int BM, int BN, int BK, int WM, int WN>
-int launch_gemm(int ak, int bk, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb, float beta,
-                float* C, int ldc, const float* bias, int splitk, float* ws, hipStream_t st) {
-    const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
-    int klen = K;
-    if (splitk > 1) {
-        klen = ((K + splitk - 1) / splitk + BK - 1) / BK * BK;
-        splitk = (K + klen - 1) / klen;
-    }
-    dim3 grid(ntm * ntn, 1, splitk > 1 ? splitk : 1);
-    float* slabs = splitk > 1 ? ws : nullptr;
-#define FN_GEMM_LAUNCH(AK, BKK)                                                                                            \
-    {                                                                                                                      \
-        using SA = Stage<BM, BK, AK, NT>;                                                                                  \
-        using SB = Stage<BN, BK, BKK, NT>;                                                                                 \
-        const size_t sh = 2 * (SA::WORDS + SB::WORDS) * sizeof(float);                                                     \
-        hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, WM, WN, AK, BKK>), grid, dim3(NT), sh, st, M, N, K, alpha, A, (long)lda, \
-                           B, (long)ldb, beta, C, (long)ldc, bias, klen, slabs);                                           \
+// the staged instance KERNEL (its tile shape: gemm_plan.h) in the layout of the call, on the plan's grid and K ranges
+template <int KERNEL>
+void launch_gemm(const FnGemmPlan& p, int ak, int bk, hipStream_t st, int M, int N, int K, float alpha, const float* A, long lda, const float* B, long ldb,
+                 float beta, float* C, long ldc, const float* bias, float* slabs) {
+    constexpr StagedTile T = staged_tile(KERNEL);
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+#define FN_GEMM_LAUNCH(AK, BKK)                                                                                                              \
+    {                                                                                                                                        \
+        using SA = Stage<T.bm, T.bk, AK, NT>;                                                                                                \
+        using SB = Stage<T.bn, T.bk, BKK, NT>;                                                                                               \
+        const size_t sh = 2 * (SA::WORDS + SB::WORDS) * sizeof(float);                                                                       \
+        hipLaunchKernelGGL((gemm_kernel<T.bm, T.bn, T.bk, T.wm, T.wn, AK, BKK>), grid, dim3(NT), sh, st, M, N, K, alpha, A, lda, B, ldb, beta, C, \
+                           ldc, bias, p.klen, slabs);                                                                                        \
     }
     if (ak && bk) FN_GEMM_LAUNCH(true, true)
     else if (ak && !bk) FN_GEMM_LAUNCH(true, false)
     else if (!ak && !bk) FN_GEMM_LAUNCH(false, false)
     else FN_GEMM_LAUNCH(false, true)
 #undef FN_GEMM_LAUNCH
+}
+
+// one product from its plan: the kernel it names on its grid and K ranges, then the reduction it names.  A2 / lda2: the second source of the TN kernels
+// (rows of the output from p.msplit on), none otherwise
+int launch_plan(const FnGemmPlan& p, int ak, int bk, hipStream_t st, int M, int N, int K, float alpha, const float* A, long lda, const float* B, long ldb,
+                float beta, float* C, long ldc, const float* bias, float* ws, const float* A2, long lda2) {
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    float* slabs = p.ranges > 1 ? ws : nullptr;
+#define FN_STAGED(KERNEL) \
+    case KERNEL: launch_gemm<KERNEL>(p, ak, bk, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, slabs); break;
+#define FN_TN(KERNEL_FN, THREADS, LDS) \
+    hipLaunchKernelGGL(KERNEL_FN, grid, dim3(THREADS), LDS, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, p.klen, slabs, A2, lda2, p.msplit)
+    switch (p.kernel) {
+        FN_STAGED(FN_PLAN_STAGED_64_64_16)
+        FN_STAGED(FN_PLAN_STAGED_64_64_32)
+        FN_STAGED(FN_PLAN_STAGED_32_64_32)
+        FN_STAGED(FN_PLAN_STAGED_64_16_16)
+        FN_STAGED(FN_PLAN_STAGED_128_128_32)
+        case FN_PLAN_NT_DIRECT_4_2:
+            hipLaunchKernelGGL((gemm_nt_direct_kernel<4, 2>), grid, dim3(NT), 0, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias);
+            break;
+        case FN_PLAN_NT_DIRECT_1_4:
+            hipLaunchKernelGGL((gemm_nt_direct_kernel<1, 4>), grid, dim3(NT), 0, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias);
+            break;
+        case FN_PLAN_NT_X6W: {
+            const size_t lds = (size_t)X6W_STAGES * X6W_STAGE * 16;
+            if (const int rc = fn_set_max_lds<gemm_nt_x6w_kernel>((int)lds, FN_E_SHAPE)) return rc;
+            hipLaunchKernelGGL(gemm_nt_x6w_kernel, grid, dim3(X6W_NT), lds, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias);
+            break;
+        }
+        case FN_PLAN_TN: FN_TN(gemm_tn_kernel, NT, 0); break;
+        case FN_PLAN_TN_LEAN: FN_TN(gemm_tn_lean_kernel, NT, 0); break;
+        case FN_PLAN_TN_X6: FN_TN(gemm_tn_x6_kernel, NT, 0); break;
+        case FN_PLAN_TN_X6W: {          // producer / consumer kernel (512 threads)
+            const size_t lds = (size_t)X6W_STAGES * X6W_STAGE * 16;
+            if (const int rc = fn_set_max_lds<gemm_tn_x6w_kernel>((int)lds, FN_E_SHAPE)) return rc;
+            FN_TN(gemm_tn_x6w_kernel, X6W_NT, lds);
+            break;
+        }
+        case FN_PLAN_TN_X6V: {          // ... on 128 x 256 tiles
+            const size_t lds = (size_t)2 * X6V_STAGE * 16;
+            if (const int rc = fn_set_max_lds<gemm_tn_x6v_kernel>((int)lds, FN_E_SHAPE)) return rc;
+            FN_TN(gemm_tn_x6v_kernel, X6W_NT, lds);
+            break;
+        }
+        default: return FN_E_UNSUPPORTED;
+    }
+#undef FN_TN
+#undef FN_STAGED
     FN_CHECK_LAUNCH();
-    if (splitk > 1) {
-        launch_slab_reduce(st, slabs, splitk, M, N, alpha, beta, C, (long)ldc, bias);
+    if (p.reduce != FN_PLAN_REDUCE_NONE) {
+        launch_slab_reduce(p, st, slabs, M, N, alpha, beta, C, ldc, bias);
         FN_CHECK_LAUNCH();
     }
     return FN_OK;
@@ -1472,134 +1514,26 @@ int fn_gemm_multi(int a_kmajor, int b_kmajor, const FnGemmJob* jobs, int n_jobs,
     return FN_OK;
 }
 
-// grid of a TN launch: 1-D (K ranges dealt to the XCDs, see gemm_tn_body) when the K ranges divide by 8, else tiles x 1 x K ranges
-static dim3 tn_grid(int tiles, int splitk) {
-    return splitk > 1 && (splitk & 7) == 0 ? dim3(tiles * splitk, 1, 1) : dim3(tiles, 1, splitk > 1 ? splitk : 1);
-}
-
-// the bf16 x 6 weight-gradient product: producer / consumer kernel (512 threads, 96 KB of LDS), or the per-wave kernel of round 5 on request
-static int launch_tn_x6(int mode, int tiles, int splitk, hipStream_t st, int M, int N, int K, float alpha, const float* A, long lda, const float* B, long ldb,
-                        float beta, float* C, long ldc, const float* bias, int klen, float* slabs, const float* A2, long lda2, int msplit) {
-    // mode: FN_GEMM_X6_PERWAVE = the round-5 kernel, FN_GEMM_X6_WIDE = 128 x 256 tiles, 0 = 128 x 128 tiles (producer / consumer kernels)
-    if (mode & FN_GEMM_X6_PERWAVE) {
-        hipLaunchKernelGGL(gemm_tn_x6_kernel, tn_grid(tiles, splitk), dim3(NT), 0, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, klen, slabs, A2, lda2, msplit);
-        return FN_OK;
-    }
-    const bool wide = (mode & FN_GEMM_X6_WIDE) != 0;
-    const size_t lds = wide ? (size_t)2 * X6V_STAGE * 16 : (size_t)X6W_STAGES * X6W_STAGE * 16;
-    if (const int rc = wide ? fn_set_max_lds<gemm_tn_x6v_kernel>((int)lds, FN_E_SHAPE) : fn_set_max_lds<gemm_tn_x6w_kernel>((int)lds, FN_E_SHAPE)) return rc;
-    // 1-D launches (K ranges dealt to the XCDs): one workgroup per CU walking its (tile, K range) items instead of one workgroup per item - the next
-    // item's first blocks are requested and cut while the consumers store the finished one (FN_GEMM_X6_PERTILE: one workgroup per item, A/B and tests)
-    const int wtiles = wide ? ((M + 127) / 128) * ((N + 255) / 256) : tiles;
-    dim3 grid = tn_grid(wtiles, splitk);
-    const int cus = fn_cu_count();
-    if (grid.y == 1 && grid.z == 1 && slabs != nullptr && !(mode & FN_GEMM_X6_PERTILE) && cus >= 8 && (cus & 7) == 0 && (int)grid.x > cus) grid.x = cus;
-    if (wide) {
-        hipLaunchKernelGGL(gemm_tn_x6v_kernel, grid, dim3(X6W_NT), lds, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, klen, slabs, A2, lda2, msplit);
-    } else {
-        hipLaunchKernelGGL(gemm_tn_x6w_kernel, grid, dim3(X6W_NT), lds, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, klen, slabs, A2, lda2, msplit);
-    }
-    return FN_OK;
-}
-
-// the flag bits that ride on the `splitk` argument of fn_gemm_f32 / fn_gru_dwhh_f32 (fadernets.h)
-struct SplitkFlags {
-    static constexpr int X6_MODES = FN_GEMM_X6_PERWAVE | FN_GEMM_X6_WIDE | FN_GEMM_X6_PERTILE;
-    bool lean, x6;
-    int x6_mode, xflags, splitk;                         // xflags: the bf16 x 6 bits as they came, to hand on; splitk: the number of K ranges asked for
-    explicit SplitkFlags(int v)
-        : lean((v & FN_GEMM_LEAN) != 0), x6((v & FN_GEMM_BF16X6) != 0), x6_mode(v & X6_MODES), xflags(v & (FN_GEMM_BF16X6 | X6_MODES)),
-          splitk(v & ~(FN_GEMM_LEAN | FN_GEMM_BF16X6 | X6_MODES)) {}
-};
-
-// the TN product (both operands with K as their slow dimension, 16-byte aligned): bf16 x 6 or fp32 kernel over `splitk` K ranges, then the slab reduce
-static int launch_tn(const SplitkFlags& f, hipStream_t st, int M, int N, int K, float alpha, const float* A, long lda, const float* B, long ldb, float beta,
-                     float* C, long ldc, const float* bias, float* ws, const float* A2, long lda2, int msplit) {
-    int klen = K, splitk = f.splitk;
-    if (splitk > 1) {
-        // K ranges of whole 32-k blocks for the bf16 x 6 kernel (no fp32-MFMA tail inside a range), of 4 rows otherwise
-        const int gran = f.x6 ? 32 : 4;
-        klen = ((K + splitk - 1) / splitk + gran - 1) / gran * gran;
-        splitk = (K + klen - 1) / klen;
-    }
-    const int ntm = (M + 127) / 128, ntn = (N + 127) / 128;
-    float* slabs = splitk > 1 ? ws : nullptr;
-    if (f.x6) {
-        const int rc = launch_tn_x6(f.x6_mode, ntm * ntn, splitk, st, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, klen, slabs, A2, lda2, msplit);
-        if (rc != FN_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(f.lean ? gemm_tn_lean_kernel : gemm_tn_kernel, tn_grid(ntm * ntn, splitk), dim3(NT), 0, st, M, N, K, alpha, A, lda, B, ldb, beta, C,
-                           ldc, bias, klen, slabs, A2, lda2, msplit);
-    }
-    FN_CHECK_LAUNCH();
-    if (splitk > 1) {
-        launch_slab_reduce(st, slabs, splitk, M, N, alpha, beta, C, ldc, bias);
-        FN_CHECK_LAUNCH();
-    }
-    return FN_OK;
-}
-
 size_t fn_gemm_ws_bytes(int M, int N, int splitk) { return splitk > 1 ? (size_t)splitk * M * N * sizeof(float) : 0; }
 
 int fn_gemm_f32(int a_kmajor, int b_kmajor, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
                 float beta, float* C, int ldc, const float* bias, int splitk, float* ws, size_t ws_bytes, void* stream) {
     if (!A || !B || !C) return FN_E_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc < N) return FN_E_SHAPE;
-    const SplitkFlags f(splitk);
-    const bool lean = f.lean, x6 = f.x6;
-    const int x6_mode = f.x6_mode;
-    splitk = f.splitk;
-    if (splitk > 1 && (!ws || ws_bytes < fn_gemm_ws_bytes(M, N, splitk))) return FN_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (!a_kmajor && !b_kmajor && (lda % 4) == 0 && (ldb % 4) == 0 && lda >= 4 && ldb >= 4 &&
-        (((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0))
-        return launch_tn(f, st, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C, (long)ldc, bias, ws, (const float*)nullptr, 0L, 0);
-    // bf16 x 6, K-contiguous operands, whole 128 x 128 tiles and 32-k blocks, no split: the producer / consumer kernel
-    if (x6 && a_kmajor && b_kmajor && splitk <= 1 && (M % 128) == 0 && (N % 128) == 0 && (K % 32) == 0 && K >= 128 && (lda % 4) == 0 && (ldb % 4) == 0 &&
-        (ldc % 4) == 0 && (((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) == 0) && (long)(M / 128) * (N / 128) >= 128) {
-        const size_t lds = (size_t)X6W_STAGES * X6W_STAGE * 16;
-        if (const int rc = fn_set_max_lds<gemm_nt_x6w_kernel>((int)lds, FN_E_SHAPE)) return rc;
-        // one workgroup per CU (144 KB of LDS each) walking its tiles, unless asked for one workgroup per tile (FN_GEMM_X6_PERTILE) or the CU count is not a
-        // multiple of the 8 XCDs
-        const int ntiles = (M / 128) * (N / 128), cus = fn_cu_count();
-        const int grid = (ntiles > cus && cus >= 8 && (cus & 7) == 0 && !(x6_mode & FN_GEMM_X6_PERTILE)) ? cus : ntiles;
-        hipLaunchKernelGGL(gemm_nt_x6w_kernel, dim3(grid), dim3(X6W_NT), lds, st, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C, (long)ldc, bias);
-        FN_CHECK_LAUNCH();
-        return FN_OK;
-    }
-    // K-contiguous operands, whole 128 x 128 tiles that fill the chip, short K, no split: the LDS-free kernel
-    if (a_kmajor && b_kmajor && splitk <= 1 && (M % 128) == 0 && (N % 128) == 0 && (K % 16) == 0 && K >= 64 && (lda % 4) == 0 && (ldb % 4) == 0 &&
-        (ldc % 4) == 0 && (((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)bias)) & 15) == 0) &&
-        (long)M * lda < (1L << 30) && (long)N * ldb < (1L << 30) && (long)(M / 128) * (N / 128) >= 256) {
-        if (lean)       // <= 128 registers, no LDS: one of its wavefronts fits a SIMD beside a wavefront of the decoder-shaped forward scans (377 registers)
-            hipLaunchKernelGGL((gemm_nt_direct_kernel<1, 4>), dim3((M / 128) * (N / 128)), dim3(NT), 0, st, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C,
-                               (long)ldc, bias);
-        else
-            hipLaunchKernelGGL((gemm_nt_direct_kernel<4, 2>), dim3((M / 128) * (N / 128)), dim3(NT), 0, st, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C,
-                               (long)ldc, bias);
-        FN_CHECK_LAUNCH();
-        return FN_OK;
-    }
-    // skinny outputs (the attribute decoders' output layers: 16384 x 3 / 16 x 512): 64 x 16 tiles, 12.8 KB of LDS - a workgroup fits a CU beside one of the
-    // bf16 x 6 producer / consumer kernels (144 of 160 KB), so the loss chain of the step runs beside the dhx1 product instead of behind it; same k order
-    if (N <= 16 && a_kmajor && b_kmajor && splitk <= 1 && M >= 64)
-        return launch_gemm<64, 16, 16, 4, 1>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, splitk, ws, st);
-    const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    // 128 x 128 tiles only when they fill the chip (one workgroup per CU); below that the 64 x 64 kernel's 4x more workgroups win
-    // (decode at 2048 rows: 192 big tiles -> 55 us, 768 small ones -> 40 us per W_ih2 projection)
-    if (tiles128 * (splitk > 1 ? splitk : 1) >= 256)
-        return launch_gemm<128, 128, 32, 2, 2>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, splitk, ws, st);
-    // 64 x 64 tiles: K tiles of 32 when K allows it - one barrier per 32 MFMAs of a wave instead of per 16 (the decode's output layer,
-    // 2048 x 342 x 512: 20.5 -> see profiles); same k order
-    if (splitk <= 1 && (K % 32) == 0 && K >= 128) {
-        // ... and 32 x 64 tiles when even the 64 x 64 ones leave CUs empty (the decode's output layer at 2048 rows: 192 workgroups -> 384;
-        // same k order per output element: bit-identical)
-        const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
-        if (a_kmajor && b_kmajor && tiles64 < 240 && M >= 64)
-            return launch_gemm<32, 64, 32, 2, 2>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, splitk, ws, st);
-        return launch_gemm<64, 64, 32, 2, 2>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, splitk, ws, st);
-    }
-    return launch_gemm<64, 64, 16, 2, 2>(a_kmajor, b_kmajor, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, splitk, ws, st);
+    const int ranges = SplitkFlags(splitk).splitk;
+    if (ranges > 1 && (!ws || ws_bytes < fn_gemm_ws_bytes(M, N, ranges))) return FN_E_WORKSPACE;
+    const FnGemmPlan p = gemm_plan(a_kmajor, b_kmajor, M, N, K, lda, ldb, ldc, (uintptr_t)A, (uintptr_t)B, (uintptr_t)C, (uintptr_t)bias, (uintptr_t)ws, splitk,
+                                   fn_cu_count());
+    return launch_plan(p, a_kmajor, b_kmajor, (hipStream_t)stream, M, N, K, alpha, A, (long)lda, B, (long)ldb, beta, C, (long)ldc, bias, ws, nullptr, 0L);
+}
+
+int fn_gemm_plan(int a_kmajor, int b_kmajor, int M, int N, int K, int lda, int ldb, int ldc, const void* A, const void* B, const void* C, const void* bias,
+                 const void* ws, int splitk, int cus, FnGemmPlan* plan) {
+    if (!plan) return FN_E_NULL;
+    if (M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc < N || cus < 0) return FN_E_SHAPE;
+    *plan = gemm_plan(a_kmajor, b_kmajor, M, N, K, lda, ldb, ldc, (uintptr_t)A, (uintptr_t)B, (uintptr_t)C, (uintptr_t)bias, (uintptr_t)ws, splitk,
+                      cus > 0 ? cus : fn_cu_count());
+    return FN_OK;
 }
 
 size_t fn_gru_dwhh_ws_bytes(int H, int splitk) { return fn_gemm_ws_bytes(3 * H, H, splitk); }
@@ -1608,17 +1542,26 @@ int fn_gru_dwhh_f32(const float* dgx, const float* dghn, const float* hprev, int
                     float* ws, size_t ws_bytes, void* stream) {
     if (!dgx || !dghn || !hprev || !dW) return FN_E_NULL;
     if (rows <= 0 || rows > 0x7fffffff || H <= 0) return FN_E_SHAPE;
-    const SplitkFlags f(splitk);
-    if (f.splitk > 1 && (!ws || ws_bytes < fn_gru_dwhh_ws_bytes(H, f.splitk))) return FN_E_WORKSPACE;
-    const int M = 3 * H, N = H, K = (int)rows;
-    const bool one_launch = (2 * H) % 128 == 0 && (H % 4) == 0 && (((((uintptr_t)dgx) | ((uintptr_t)dghn) | ((uintptr_t)hprev)) & 15) == 0);
-    if (!one_launch) {          // two products: rows [0, 2H) from dgx, rows [2H, 3H) from dghn
-        const int fl = f.splitk | f.xflags;
-        int rc = fn_gemm_f32(0, 0, 2 * H, N, K, 1.0f, dgx, 3 * H, hprev, H, beta, dW, H, nullptr, fl, ws, ws_bytes, stream);
-        if (rc != FN_OK) return rc;
-        return fn_gemm_f32(0, 0, H, N, K, 1.0f, dghn, H, hprev, H, beta, dW + (size_t)2 * H * H, H, nullptr, fl, ws, ws_bytes, stream);
-    }
-    return launch_tn(f, (hipStream_t)stream, M, N, K, 1.0f, dgx, (long)3 * H, hprev, (long)H, beta, dW, (long)H, (const float*)nullptr, ws, dghn, (long)H, 2 * H);
+    const int ranges = SplitkFlags(splitk).splitk;
+    if (ranges > 1 && (!ws || ws_bytes < fn_gru_dwhh_ws_bytes(H, ranges))) return FN_E_WORKSPACE;
+    const int K = (int)rows;
+    const DwhhPlan d = dwhh_plan(H, K, (uintptr_t)dgx, (uintptr_t)dghn, (uintptr_t)hprev, (uintptr_t)dW, (uintptr_t)ws, splitk, fn_cu_count());
+    hipStream_t st = (hipStream_t)stream;
+    if (d.n == 1) return launch_plan(d.launch[0], 0, 0, st, 3 * H, H, K, 1.0f, dgx, (long)3 * H, hprev, (long)H, beta, dW, (long)H, nullptr, ws, dghn, (long)H);
+    // two products: rows [0, 2H) from dgx, rows [2H, 3H) from dghn
+    if (const int rc = launch_plan(d.launch[0], 0, 0, st, 2 * H, H, K, 1.0f, dgx, (long)3 * H, hprev, (long)H, beta, dW, (long)H, nullptr, ws, nullptr, 0L)) return rc;
+    return launch_plan(d.launch[1], 0, 0, st, H, H, K, 1.0f, dghn, (long)H, hprev, (long)H, beta, dW + (size_t)2 * H * H, (long)H, nullptr, ws, nullptr, 0L);
+}
+
+int fn_gru_dwhh_plan(const void* dgx, const void* dghn, const void* hprev, const void* dW, const void* ws, int64_t rows, int H, int splitk, int cus,
+                     int32_t* n_launches, FnGemmPlan plans[2]) {
+    if (!n_launches || !plans) return FN_E_NULL;
+    if (rows <= 0 || rows > 0x7fffffff || H <= 0 || cus < 0) return FN_E_SHAPE;
+    const DwhhPlan d = dwhh_plan(H, (int)rows, (uintptr_t)dgx, (uintptr_t)dghn, (uintptr_t)hprev, (uintptr_t)dW, (uintptr_t)ws, splitk,
+                                 cus > 0 ? cus : fn_cu_count());
+    *n_launches = d.n;
+    for (int i = 0; i < d.n; ++i) plans[i] = d.launch[i];
+    return FN_OK;
 }
 
 int fn_transpose_f32(const float* src, int R, int C, int src_ld, float* dst, int dst_ld, void* stream) {

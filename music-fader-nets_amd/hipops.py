@@ -84,6 +84,20 @@ class HipOps:
 
     # -- dense ----------------------------------------------------------------------------------
     def gemm(self, A, B, Cm, a_k=True, b_k=True, alpha=1.0, beta=0.0, bias=None, splitk=1, lean=False, nt_x6=True):
+        M, N, K, pa, lda, pb, ldb, pc, ldc, pbias, flags, ws, wsb = self._gemm_args(A, B, Cm, a_k, b_k, bias, splitk, lean, nt_x6)
+        _lib.check(self.lib.fn_gemm_f32(int(a_k), int(b_k), M, N, K, alpha, pa, lda, pb, ldb, beta, pc, ldc, pbias, flags, ws, wsb, self.stream()),
+                   "fn_gemm_f32")
+
+    def gemm_plan(self, A, B, Cm, a_k=True, b_k=True, bias=None, splitk=1, lean=False, nt_x6=True):
+        """what gemm() with these arguments launches, as the library decides it (fn_gemm_plan on the same prepared arguments, the workspace included):
+        dict(kernel, klen, ranges, grid=(x, y, z), tiles, reduce, reduce_blocks, msplit).  Nothing is enqueued."""
+        M, N, K, pa, lda, pb, ldb, pc, ldc, pbias, flags, ws, _ = self._gemm_args(A, B, Cm, a_k, b_k, bias, splitk, lean, nt_x6)
+        plan = _lib.FnGemmPlan()
+        _lib.check(self.lib.fn_gemm_plan(int(a_k), int(b_k), M, N, K, lda, ldb, ldc, pa, pb, pc, pbias, ws, flags, 0, C.byref(plan)), "fn_gemm_plan")
+        return plan.as_dict()
+
+    def _gemm_args(self, A, B, Cm, a_k, b_k, bias, splitk, lean, nt_x6):
+        """the arguments of fn_gemm_f32 / fn_gemm_plan for one product: (M, N, K, A, lda, B, ldb, C, ldc, bias, splitk | flags, workspace, its bytes)"""
         pa, ar, ac, lda = _mat(A, "A")
         pb, br, bc, ldb = _mat(B, "B")
         pc, M, N, ldc = _mat(Cm, "C")
@@ -102,9 +116,7 @@ class HipOps:
         if splitk > 1:
             wsb = self.lib.fn_gemm_ws_bytes(M, N, splitk & 0xffff)
             ws = self.workspace(wsb, "gemm")
-        _lib.check(self.lib.fn_gemm_f32(int(a_k), int(b_k), M, N, K, alpha, pa, lda, pb, ldb, beta, pc, ldc, _p(bias),
-                                        splitk | (_lib.GEMM_LEAN if lean else 0) | x6,
-                                        _p(ws), wsb, self.stream()), "fn_gemm_f32")
+        return M, N, K, pa, lda, pb, ldb, pc, ldc, _p(bias), splitk | (_lib.GEMM_LEAN if lean else 0) | x6, _p(ws), wsb
 
     def _x6_mode(self, splitk, N, K, x6):
         """kernel choice of a bf16 x 6 weight-gradient product: (K ranges, flags).  Wide (128 x 256) tiles halve the number of output tiles: twice the K
@@ -438,6 +450,19 @@ class HipOps:
 
     def gru_dwhh(self, dgx, dghn, hprev, dW, beta=0.0, splitk=1, lean=False):
         """dW [3H][H] = beta*dW + [dgx[:, :2H] | dghn]^T hprev  (dgx [rows][3H], dghn / hprev [rows][H])."""
+        rows, H, flags, ws, wsb = self._dwhh_args(dgx, dghn, hprev, dW, splitk, lean)
+        _lib.check(self.lib.fn_gru_dwhh_f32(_p(dgx), _p(dghn), _p(hprev), rows, H, beta, _p(dW), flags, ws, wsb, self.stream()), "fn_gru_dwhh_f32")
+
+    def gru_dwhh_plan(self, dgx, dghn, hprev, dW, splitk=1, lean=False):
+        """what gru_dwhh() with these arguments launches (fn_gru_dwhh_plan on the same prepared arguments): dict(form = 'one-launch' | 'two-products',
+        launches = [plan, ..] as gemm_plan gives them).  Nothing is enqueued."""
+        rows, H, flags, ws, _ = self._dwhh_args(dgx, dghn, hprev, dW, splitk, lean)
+        n, plans = C.c_int32(), (_lib.FnGemmPlan * 2)()
+        _lib.check(self.lib.fn_gru_dwhh_plan(_p(dgx), _p(dghn), _p(hprev), _p(dW), ws, rows, H, flags, 0, C.byref(n), plans), "fn_gru_dwhh_plan")
+        return dict(form="one-launch" if n.value == 1 else "two-products", launches=[plans[i].as_dict() for i in range(n.value)])
+
+    def _dwhh_args(self, dgx, dghn, hprev, dW, splitk, lean):
+        """the arguments of fn_gru_dwhh_f32 / fn_gru_dwhh_plan: (rows, H, splitk | flags, workspace, its bytes)"""
         for t, nm in ((dgx, "dgx"), (dghn, "dghn"), (hprev, "hprev"), (dW, "dW")):
             _dense(t, name=nm)
         rows, H = hprev.shape
@@ -448,8 +473,7 @@ class HipOps:
             splitk, x6 = self._x6_mode(splitk, H, rows, x6)
         wsb = int(self.lib.fn_gru_dwhh_ws_bytes(H, splitk))
         ws = self.workspace(wsb, "gemm") if wsb else None
-        _lib.check(self.lib.fn_gru_dwhh_f32(_p(dgx), _p(dghn), _p(hprev), rows, H, beta, _p(dW), splitk | (_lib.GEMM_LEAN if lean else 0) | x6,
-                                            _p(ws), wsb, self.stream()), "fn_gru_dwhh_f32")
+        return rows, H, splitk | (_lib.GEMM_LEAN if lean else 0) | x6, _p(ws), wsb
 
     def decode_greedy(self, B, steps, H, V, start_token, w_hh1_frag, b_hh1, b_ih1, table1, rowbias1, h0, w_ih2_frag, b_ih2, w_hh2_frag, b_hh2,
                       w_out_frag, b_out, tokens, logp=None, forced=None, force=None):

@@ -4,7 +4,9 @@ gemm_tn_kernel / gemm_tn_lean_kernel (also behind fn_gru_dwhh_f32) and the two s
 
   gemm_instance / multi_plan / dwhh_plan   the host-side dispatch and the device-side choice of load path restated on shapes, leading dimensions
                              and addresses: which kernel instance a call launches, its K ranges, the grid form of a TN launch, the slab
-                             reduction that follows, and per tile and K range whether the staged loop takes load_fast or load_checked
+                             reduction that follows, and per tile and K range whether the staged loop takes load_fast or load_checked;
+                             its host-side fields are checked against the library's own answer (fn_gemm_plan / fn_gru_dwhh_plan)
+  lib_gemm_plan / lib_dwhh_plan / assert_mirror_matches_library   that answer, and the comparison
   restate32(prob)            the float32 restatement: every accumulator adds its K range in order, as sequential float32 additions of 8-wide chunk
                              products; the accumulators of a split launch are then added in slab order; alpha, bias, beta C as the epilogue
   check_exact(prob, cbuf)    operands, bias and C0 integers of [-8, 8]: sum |a||b| + |bias| + |beta c| < 2^24 per output element (asserted), so every
@@ -47,8 +49,74 @@ def _al16(p, ld):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# the dispatch restated on shapes
+# the dispatch restated on shapes.  The library decides it in one place (csrc/gemm_plan.h) and hands the decision out (fn_gemm_plan /
+# fn_gru_dwhh_plan); this restatement adds what only the device sees (load paths, pipeline steps) and is itself CHECKED AGAINST THE LIBRARY: on the CPU
+# for every case and a seeded sweep (test_gemm_reference.py), on the MI355X for every launch on its real addresses (assert_mirror_matches_library)
 # ---------------------------------------------------------------------------------------------------------------------------------------------
+PLAN_CUS = 256                      # compute units the CPU tests state (an MI355X has 256); a GPU test asks for the device's own
+
+
+def _lib():
+    from mfn_import import load_package
+    load_package()
+    from music_fader_nets_amd import _lib as lib
+    return lib
+
+
+def _flags(lean, x6):
+    """lean / x6 (False, True = FN_GEMM_BF16X6, or the bf16 x 6 bits themselves) as they ride on the splitk argument"""
+    lib = _lib()
+    return (lib.GEMM_LEAN if lean else 0) | (lib.GEMM_BF16X6 if x6 is True else int(x6))
+
+
+def lib_gemm_plan(a_k, b_k, M, N, K, lda, ldb, ldc, ptrs, splitk, lean, x6=False, cus=PLAN_CUS):
+    """fn_gemm_plan for the call gemm_instance describes (same arguments), as a dict; no device is touched"""
+    import ctypes
+    lib = _lib()
+    pA, pB, pC, pbias = ptrs[:4]
+    pws = ptrs[4] if len(ptrs) > 4 else 0
+    plan = lib.FnGemmPlan()
+    rc = lib.load().fn_gemm_plan(int(a_k), int(b_k), M, N, K, lda, ldb, ldc, pA, pB, pC, pbias, pws, splitk | _flags(lean, x6), cus, ctypes.byref(plan))
+    assert rc == 0, rc
+    return plan.as_dict()
+
+
+def lib_dwhh_plan(H, rows, ptrs, splitk, lean, x6=False, cus=PLAN_CUS):
+    """fn_gru_dwhh_plan for the call dwhh_plan describes, as dict(form, launches)"""
+    import ctypes
+    lib = _lib()
+    pws = ptrs[4] if len(ptrs) > 4 else 0
+    n, plans = ctypes.c_int32(), (lib.FnGemmPlan * 2)()
+    rc = lib.load().fn_gru_dwhh_plan(ptrs[0], ptrs[1], ptrs[2], ptrs[3], pws, rows, H, splitk | _flags(lean, x6), cus, ctypes.byref(n), plans)
+    assert rc == 0, rc
+    return dict(form="one-launch" if n.value == 1 else "two-products", launches=[plans[i].as_dict() for i in range(n.value)])
+
+
+def assert_mirror_matches_library(mp, lp, M, N, what=""):
+    """the host-side fields of a mirror plan (gemm_instance / tn_plan) against the library's plan of the same call (lib_gemm_plan, HipOps.gemm_plan):
+    kernel, klen, ranges, grid form (and, the fp32 kernels have no walking form, the grid itself), reduce kernel and its trips, tiles, msplit"""
+    if mp["family"] == "x6":                         # the mirror names the family only; literal expectations: test_gemm_reference.py
+        assert lp["kernel"].startswith(mp["kernel"]), (what, mp["kernel"], lp)
+        return
+    assert lp["kernel"] == mp["kernel"], (what, mp["kernel"], lp)
+    if mp["family"] == "nt-direct":
+        tiles = (M // 128) * (N // 128)
+        assert (lp["klen"] > 0, lp["ranges"], lp["grid"], lp["tiles"], lp["reduce"], lp["reduce_blocks"]) == (True, 1, (tiles, 1, 1), tiles, None, 0), (what, lp)
+        return
+    S, tiles = mp["ranges"], mp["tiles"]
+    grid = (tiles * S, 1, 1) if mp.get("grid") == "1d" else (tiles, 1, S)
+    trips = 0 if lp["reduce"] is None else _cdiv(M * N // 4 if lp["reduce"] == "slab_reduce4_kernel" else M * N, lp["reduce_blocks"] * 256)
+    got = (lp["klen"], lp["ranges"], lp["grid"], lp["tiles"], lp["reduce"], trips, lp["msplit"])
+    assert got == (mp["klen"], S, grid, tiles, mp["reduce"], mp["reduce_trips"], mp.get("msplit", 0)), (what, mp, lp)
+    assert (lp["reduce_blocks"] == 0) == (S == 1) and lp["reduce_blocks"] <= 2048
+
+
+def assert_dwhh_mirror_matches_library(mp, lp, H, what=""):
+    assert lp["form"] == mp["form"] and len(lp["launches"]) == len(mp["launches"]), (what, mp["form"], lp)
+    for m, l, rows in zip(mp["launches"], lp["launches"], (3 * H,) if mp["form"] == "one-launch" else (2 * H, H)):
+        assert_mirror_matches_library(m, l, rows, H, what)
+
+
 def split_ranges(K, splitk, gran):
     """(klen, number of K ranges) as launch_gemm / launch_tn recompute them: ranges of whole `gran`-k blocks, the last one short"""
     if splitk <= 1:

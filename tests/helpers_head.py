@@ -9,7 +9,7 @@
                              then err <= F x max(e_ref, 2**-23) in EVERY tile, e_ref = the float32 restatement's own error in that tile,
                              F = helpers.SCAN_F_CAP.  Returns the worst ratio and where it occurred.
   head_path / nt_direct_instance   the device-side / host-side choice of K loop / kernel instance restated on shapes, so that every case can
-                             assert that it reaches the path it names.
+                             assert that it reaches the path it names; the host-side one is checked against the library (fn_gemm_plan).
 
 Input condition: every tile maximum of the float64 reference is >= SCAN_MIN_REF.  Two kinds of case have a reference that IS zero, not small:
 V = 1 (softmax = 1: nll = 0 and dlogits = 0 in exact arithmetic) and grad_scale = 0 (dlogits = 0).  There the relative error is undefined and the
@@ -90,7 +90,9 @@ def worst_ratio(err, e_ref, F):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# which K loop / kernel instance a launch takes (csrc/gemm.hip restated on shapes)
+# which K loop / kernel instance a launch takes (csrc/gemm.hip restated on shapes).  head_path restates a choice the kernel makes on the device;
+# nt_direct_instance restates the host's (csrc/gemm_plan.h) and is checked against the library's own answer, fn_gemm_plan: on the CPU for every NT case
+# and inside the sweep of test_gemm_reference.py, on the MI355X for every launch on its real addresses
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 def _aligned16(ptr, ld):
     return ptr % 16 == 0 and ld % 4 == 0

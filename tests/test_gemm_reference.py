@@ -11,10 +11,11 @@ import torch
 from fake_ops import FakeOps
 from helpers import SCAN_F_CAP, SCAN_MIN_REF
 from helpers_gemm import (DWHH_BY_ID, DWHH_CASES, G16, G32, G128, G3264, G6416, GEMM_BY_ID, GEMM_CASES, GEMM_F, GEMM_FAMILIES, GEMM_SENTINEL, MULTI_BY_ID, MULTI_CASES,
-                          NN, NT, STAGED_CASES, TN, TN_CASES, TN_NFULL, TN_PF, TNK, TNL, TT, UNREACHABLE, assert_multi_plan_matches_case, assert_plan_matches_case,
-                          c_buffer, case_family, case_plan, check_exact, check_normal, coverage_reached, coverage_wanted, dwhh_case_plan, dwhh_operands, dwhh_plan,
-                          dwhh_problem, gemm_instance, gemm_problem, k_ranges, make_problem, multi_case_plan, multi_plan, multi_problems, old_metric_accepts,
-                          restate32, slab_reduction, split_ranges)
+                          NN, NT, PLAN_CUS, STAGED, STAGED_CASES, TN, TN_CASES, TN_NFULL, TN_PF, TNK, TNL, TT, UNREACHABLE, _lib, assert_dwhh_mirror_matches_library,
+                          assert_mirror_matches_library, assert_multi_plan_matches_case, assert_plan_matches_case, c_buffer, case_family, case_plan, check_exact,
+                          check_normal, coverage_reached, coverage_wanted, dwhh_case_plan, dwhh_operands, dwhh_plan, dwhh_problem, gemm_instance, gemm_problem,
+                          k_ranges, lib_dwhh_plan, lib_gemm_plan, make_problem, multi_case_plan, multi_plan, multi_problems, old_metric_accepts, restate32,
+                          slab_reduction, split_ranges)
 
 IDS = [c["id"] for c in GEMM_CASES]
 MODES = ("exact", "normal")
@@ -163,6 +164,160 @@ def test_dwhh_and_multi_tables():
     assert {len(c["jobs"]) for c in MULTI_CASES} >= {12, 13}
     assert any(c["lay"] == TN and (j["M"], j["N"]) == (130, 70) for c in MULTI_CASES for j in c["jobs"])
     assert any(s[1][0] and s[2][0] and j["c0"] for c in MULTI_CASES for j in c["jobs"] for s in j["segs"])
+
+
+# ---- the mirror against the library's own plan (fn_gemm_plan / fn_gru_dwhh_plan: pure host functions, no device) ------------------------------
+def test_plan_kernel_names_follow_the_header_enum():
+    import os
+    import re
+    from mfn_import import ROOT
+    lib = _lib()
+    hdr = open(os.path.join(ROOT, "include", "fadernets.h")).read()
+    body = hdr.split("enum FnGemmKernel {")[1].split("};")[0]
+    names = re.findall(r"^\s*(FN_PLAN_[A-Z0-9_]+)", body, re.M)
+    assert names[-1] == "FN_PLAN_KERNELS" and len(names) - 1 == len(lib.GEMM_PLAN_KERNELS) == 13
+
+    def kernel_name(n):
+        n = n[len("FN_PLAN_"):]
+        if n.startswith("STAGED_"):
+            return "gemm_kernel<%s>" % n[len("STAGED_"):].replace("_", ",")
+        if n.startswith("NT_DIRECT_"):
+            return "gemm_nt_direct_kernel<%s>" % n[len("NT_DIRECT_"):].replace("_", ", ")
+        return "gemm_%s_kernel" % n.lower()
+    assert tuple(kernel_name(n) for n in names[:-1]) == lib.GEMM_PLAN_KERNELS
+    assert set(STAGED) | set(TN_PF) <= set(lib.GEMM_PLAN_KERNELS) and lib.GEMM_PLAN_REDUCES == (None, "slab_reduce_kernel", "slab_reduce4_kernel")
+    src = open(os.path.join(ROOT, "music-fader-nets_amd", "csrc", "gemm.hip")).read()
+    for k in lib.GEMM_PLAN_KERNELS:                          # every name is a kernel of gemm.hip
+        assert re.search(r"\b%s\b" % k.split("<")[0], src), k
+    import ctypes
+    plan = lib.FnGemmPlan()
+    fn = lib.load().fn_gemm_plan
+    assert fn(1, 1, 8, 8, 8, 8, 8, 8, 0, 0, 0, 0, 0, 1, PLAN_CUS, None) == lib.FN_E_NULL
+    for bad in (dict(M=0), dict(K=0), dict(lda=0), dict(ldc=7), dict(cus=-1)):
+        a = dict(dict(M=8, N=8, K=8, lda=8, ldb=8, ldc=8, cus=PLAN_CUS), **bad)
+        assert fn(1, 1, a["M"], a["N"], a["K"], a["lda"], a["ldb"], a["ldc"], 0, 0, 0, 0, 0, 1, a["cus"], ctypes.byref(plan)) == lib.FN_E_SHAPE, bad
+    n, plans = ctypes.c_int32(), (lib.FnGemmPlan * 2)()
+    dw = lib.load().fn_gru_dwhh_plan
+    assert dw(0, 0, 0, 0, 0, 37, 64, 1, PLAN_CUS, None, plans) == lib.FN_E_NULL and dw(0, 0, 0, 0, 0, 37, 64, 1, PLAN_CUS, ctypes.byref(n), None) == lib.FN_E_NULL
+    assert dw(0, 0, 0, 0, 0, 0, 64, 1, PLAN_CUS, ctypes.byref(n), plans) == lib.FN_E_SHAPE and dw(0, 0, 0, 0, 0, 1 << 31, 64, 1, PLAN_CUS, ctypes.byref(n), plans) == lib.FN_E_SHAPE
+    assert dw(0, 0, 0, 0, 0, 37, 0, 1, PLAN_CUS, ctypes.byref(n), plans) == lib.FN_E_SHAPE and dw(0, 0, 0, 0, 0, 37, 64, 1, -1, ctypes.byref(n), plans) == lib.FN_E_SHAPE
+
+
+def test_mirror_matches_the_library_on_every_case():
+    """every case of GEMM_CASES and DWHH_CASES on its nominal addresses, 256 compute units: the mirror's kernel, klen, ranges, grid, reduction and tiles are
+    what the library's dispatch decides (the lean cases also without the lean bit, as the GPU test runs them)"""
+    for c in GEMM_CASES:
+        ptrs = (4 * c["a_off"], 4 * c["b_off"], 4 * c["c0"], 4 * c["bias_off"] if c["bias"] else 0, 0)
+        for lean in {c["lean"], False}:
+            mp = gemm_instance(c["a_k"], c["b_k"], c["M"], c["N"], c["K"], c["lda"], c["ldb"], c["ldc"], ptrs, c["splitk"], lean)
+            lp = lib_gemm_plan(c["a_k"], c["b_k"], c["M"], c["N"], c["K"], c["lda"], c["ldb"], c["ldc"], ptrs, c["splitk"], lean)
+            assert_mirror_matches_library(mp, lp, c["M"], c["N"], c["id"])
+            assert lp["kernel"] == (c["kernel"] if lean == c["lean"] else TNK)
+    for c in DWHH_CASES:
+        mp, lp = dwhh_case_plan(c), lib_dwhh_plan(c["H"], c["rows"], (0, 0, 0, 0, 0), c["splitk"], c["lean"])
+        assert_dwhh_mirror_matches_library(mp, lp, c["H"], c["id"])
+        assert lp["form"] == c["form"] and [l["msplit"] for l in lp["launches"]] == ([2 * c["H"]] if c["form"] == "one-launch" else [0, 0])
+
+
+def test_mirror_matches_the_library_on_a_seeded_sweep():
+    """4000 random calls - all four layouts, M and N in 1 .. 600, K in 1 .. 4096, leading dimensions with and without % 4, addresses on and off 16-byte
+    boundaries, 1 / 2 / 3 / 8 / 12 / 16 K ranges asked for, lean and the bf16 x 6 bit on and off - and 300 of whole 128-tiles up to 4096 x 4096 (the
+    LDS-free and the bf16 x 6 NT kernels take nothing smaller), then 1000 fn_gru_dwhh_f32 calls: mirror == library in every one"""
+    import random
+    rnd = random.Random(20261020)
+    seen = set()
+    for i in range(4300):
+        a_k, b_k = rnd.random() < 0.5, rnd.random() < 0.5
+        if i < 4000:
+            M, N, K, splitk = rnd.randint(1, 600), rnd.randint(1, 600), rnd.randint(1, 4096), rnd.choice((1, 2, 3, 8, 12, 16))
+        else:
+            a_k, b_k = (True, True) if rnd.random() < 0.8 else (a_k, b_k)
+            M, N, K, splitk = 128 * rnd.choice((8, 15, 16, 32)), 128 * rnd.choice((8, 15, 16, 32)), 16 * rnd.randint(1, 12), rnd.choice((1, 1, 1, 2))
+        lda, ldb, ldc = (K if a_k else M) + rnd.choice((0, 0, 1, 2, 4, 8)), (K if b_k else N) + rnd.choice((0, 0, 1, 2, 4, 8)), N + rnd.choice((0, 0, 1, 2, 4, 8))
+        off = lambda: rnd.choice((0, 0, 0, 4, 8, 16))                                                                    # noqa: E731
+        ptrs = (1 << 20 | off(), 2 << 20 | off(), 3 << 20 | off(), (4 << 20 | off()) if rnd.random() < 0.7 else 0, 5 << 20 | off())
+        lean, x6 = rnd.random() < 0.5, rnd.random() < 0.3
+        mp = gemm_instance(a_k, b_k, M, N, K, lda, ldb, ldc, ptrs, splitk, lean, x6)
+        lp = lib_gemm_plan(a_k, b_k, M, N, K, lda, ldb, ldc, ptrs, splitk, lean, x6)
+        assert_mirror_matches_library(mp, lp, M, N, (i, a_k, b_k, M, N, K, lda, ldb, ldc, ptrs, splitk, lean, x6))
+        seen.add((lp["kernel"], lp["reduce"]))
+    assert {k for k, _ in seen} == set(_lib().GEMM_PLAN_KERNELS) - {"gemm_tn_x6_kernel", "gemm_tn_x6v_kernel"}, sorted(seen, key=str)     # (those two: by flag only)
+    assert {r for _, r in seen} == {None, "slab_reduce_kernel", "slab_reduce4_kernel"}
+    forms = set()
+    for i in range(1000):
+        H, rows, splitk, lean = rnd.choice((4, 30, 32, 64, 96, 100, 128, 192, 256, rnd.randint(1, 300))), rnd.randint(1, 5000), rnd.choice((1, 2, 3, 8, 12, 16)), rnd.random() < 0.5
+        ptrs = tuple((j + 1) << 24 | rnd.choice((0, 0, 0, 4, 8, 16)) for j in range(5))
+        mp, lp = dwhh_plan(H, rows, ptrs, splitk, lean), lib_dwhh_plan(H, rows, ptrs, splitk, lean)
+        assert_dwhh_mirror_matches_library(mp, lp, H, (i, H, rows, ptrs, splitk, lean))
+        forms.add((lp["form"],) + tuple(l["kernel"] for l in lp["launches"]))
+    assert {f[0] for f in forms} == {"one-launch", "two-products"} and ("two-products", TNK, G16) in forms and not any(TNL in f[1:] for f in forms if f[0] == "two-products")
+
+
+X6W, X6V, X6P, NTX6 = "gemm_tn_x6w_kernel", "gemm_tn_x6v_kernel", "gemm_tn_x6_kernel", "gemm_nt_x6w_kernel"
+
+
+def test_bf16x6_plans_are_what_the_launchers_computed():
+    """The mirror only names the family of a bf16 x 6 launch, so these are literal expectations, worked out by hand from launch_tn / launch_tn_x6 /
+    fn_gemm_f32 as they stood before the plan existed.  TN, 1536 x 512 x 65536 (48 tiles of 128 x 128, 24 of 128 x 256): 16 ranges asked for -> klen =
+    ceil(4096 / 32) 32 = 4096, 16 ranges, a 1-D grid of 48 x 16 = 768 items that one workgroup per compute unit walks (256) - unless FN_GEMM_X6_PERTILE, the
+    per-wave kernel, or 250 compute units (not a multiple of the 8 XCDs); 12 ranges -> klen = ceil(5462 / 32) 32 = 5472, 12 ranges, not a multiple of 8:
+    48 x 1 x 12; no split: 48 x 1 x 1 and no reduction.  The reduction of 1536 x 512 aligned floats: float4, 196608 / 256 = 768 blocks.
+    NT: 128 tiles at 2048 x 1024 (the least the kernel takes) - 128 workgroups; 256 at 4096 x 1024, not above 256 compute units - 256; 512 at 8192 x 1024 -
+    256 walking; misaligned, or 64 tiles, or K % 32 != 0: whatever the fp32 chain picks."""
+    lib = _lib()
+    X6, WIDE, PERTILE, PERWAVE = lib.GEMM_BF16X6, lib.GEMM_X6_WIDE, lib.GEMM_X6_PERTILE, lib.GEMM_X6_PERWAVE
+    R4 = ("slab_reduce4_kernel", 768)
+
+    def tn(flags, splitk, cus=256, M=1536, N=512, K=65536):
+        p = lib_gemm_plan(False, False, M, N, K, (M + 3) // 4 * 4, (N + 3) // 4 * 4, N, (0, 0, 0, 0, 0), splitk, False, flags, cus)
+        return p["kernel"], p["klen"], p["ranges"], p["grid"], p["tiles"], (p["reduce"], p["reduce_blocks"]), p["msplit"]
+
+    assert tn(X6, 16) == (X6W, 4096, 16, (256, 1, 1), 48, R4, 0)
+    assert tn(X6 | PERTILE, 16) == (X6W, 4096, 16, (768, 1, 1), 48, R4, 0)
+    assert tn(X6 | WIDE, 16) == (X6V, 4096, 16, (256, 1, 1), 24, R4, 0)
+    assert tn(X6 | WIDE | PERTILE, 16) == (X6V, 4096, 16, (384, 1, 1), 24, R4, 0)
+    assert tn(X6 | PERWAVE, 16) == (X6P, 4096, 16, (768, 1, 1), 48, R4, 0)
+    assert tn(X6 | PERWAVE | WIDE, 16) == (X6P, 4096, 16, (768, 1, 1), 48, R4, 0)            # the per-wave kernel has no wide form
+    assert tn(X6, 16, cus=250) == (X6W, 4096, 16, (768, 1, 1), 48, R4, 0)
+    assert tn(X6 | WIDE, 16, cus=250) == (X6V, 4096, 16, (384, 1, 1), 24, R4, 0)
+    assert tn(X6, 16, cus=1024) == (X6W, 4096, 16, (768, 1, 1), 48, R4, 0)                   # fewer items than compute units: one workgroup per item
+    assert tn(X6, 12) == (X6W, 5472, 12, (48, 1, 12), 48, R4, 0)
+    assert tn(X6 | WIDE, 12) == (X6V, 5472, 12, (24, 1, 12), 24, R4, 0)
+    assert tn(X6, 1) == (X6W, 65536, 1, (48, 1, 1), 48, (None, 0), 0)
+    assert tn(X6 | WIDE, 1) == (X6V, 65536, 1, (24, 1, 1), 24, (None, 0), 0)
+    assert tn(X6, 32) == (X6W, 2048, 32, (256, 1, 1), 48, R4, 0)
+    # K ranges of whole 32-k blocks: K = 4100 over 16 -> ceil(257 / 32) 32 = 288 rows, 15 ranges (3-D); the fp32 kernel: 260 rows, 16 ranges (1-D)
+    assert tn(X6, 16, K=4100)[1:5] == (288, 15, (48, 1, 15), 48) and tn(0, 16, K=4100)[:5] == (TNK, 260, 16, (768, 1, 1), 48)
+    assert tn(X6 | lib.GEMM_LEAN, 16)[0] == X6W and tn(lib.GEMM_LEAN, 16)[:4] == (TNL, 4096, 16, (768, 1, 1))     # no walking form on the fp32 kernels
+    # ragged 342 x 130: 3 x 2 tiles of 128 x 128, 3 x 1 of 128 x 256; N % 4 != 0: the scalar reduction, ceil(44460 / 256) = 174 blocks
+    assert tn(X6, 8, M=342, N=130, K=8192) == (X6W, 1024, 8, (48, 1, 1), 6, ("slab_reduce_kernel", 174), 0)
+    assert tn(X6 | WIDE, 8, M=342, N=130, K=8192) == (X6V, 1024, 8, (24, 1, 1), 3, ("slab_reduce_kernel", 174), 0)
+    # fn_gru_dwhh_f32 at H = 512: the same launch with the dghn band from row 1024 on
+    d = lib_dwhh_plan(512, 65536, (0, 0, 0, 0, 0), 16, False, X6)
+    assert d["form"] == "one-launch" and d["launches"] == [dict(kernel=X6W, klen=4096, ranges=16, grid=(256, 1, 1), tiles=48, reduce=R4[0], reduce_blocks=768, msplit=1024)]
+    d = lib_dwhh_plan(96, 4096, (0, 0, 0, 0, 0), 8, True, X6 | WIDE)                    # two products, 192 x 96 and 96 x 96: both on the wide kernel, 1 tile x 8 ranges
+    assert d["form"] == "two-products" and [(l["kernel"], l["klen"], l["grid"], l["tiles"], l["msplit"]) for l in d["launches"]] == [
+        (X6V, 512, (16, 1, 1), 2, 0), (X6V, 512, (8, 1, 1), 1, 0)]
+
+    def nt(M, N, K, flags=X6, ptrs=(0, 0, 0, 0, 0), cus=256, lean=False):
+        p = lib_gemm_plan(True, True, M, N, K, K, K, N, ptrs, 1, lean, flags, cus)
+        assert (p["klen"], p["ranges"], p["reduce"], p["msplit"]) == (K, 1, None, 0)
+        return p["kernel"], p["grid"], p["tiles"]
+
+    assert nt(2048, 1024, 512) == (NTX6, (128, 1, 1), 128)
+    assert nt(4096, 1024, 512) == (NTX6, (256, 1, 1), 256)
+    assert nt(8192, 1024, 512) == (NTX6, (256, 1, 1), 512)
+    assert nt(8192, 1024, 512, X6 | PERTILE) == (NTX6, (512, 1, 1), 512) and nt(8192, 1024, 512, cus=250) == (NTX6, (512, 1, 1), 512)
+    assert nt(8192, 1024, 512, cus=304) == (NTX6, (304, 1, 1), 512)
+    assert nt(2048, 1024, 512, lean=True)[0] == NTX6                                          # the lean bit is moot there
+    for ptrs in ((4, 0, 0, 0, 0), (0, 8, 0, 0, 0), (0, 0, 4, 0, 0), (0, 0, 0, 4, 0)):        # misaligned: the fp32 chain - 128 big tiles, 512 of 64 x 64
+        assert nt(2048, 1024, 512, ptrs=ptrs) == (G32, (512, 1, 1), 512), ptrs
+    assert nt(1024, 1024, 512) == (G32, (256, 1, 1), 256)                                     # 64 tiles
+    assert nt(1024, 1024, 512, 0) == (G32, (256, 1, 1), 256) and nt(2048, 1024, 512, 0) == (G32, (512, 1, 1), 512)      # and what the chain picks without the flag
+    assert nt(4096, 1024, 80) == ("gemm_nt_direct_kernel<4, 2>", (256, 1, 1), 256)            # K % 32 != 0, 256 tiles: the LDS-free kernel
+    assert nt(4096, 1024, 80, lean=True)[0] == "gemm_nt_direct_kernel<1, 4>" and nt(4096, 1024, 512, 0)[0] == "gemm_nt_direct_kernel<4, 2>"
+    assert nt(2048, 1024, 80) == (G16, (512, 1, 1), 512)                                      # K % 32 != 0, 128 tiles
+    assert nt(2048, 1024, 96)[0] == G16 and nt(2048, 1024, 128)[0] == NTX6                    # K >= 128
 
 
 # ---- the restatement passes both passes ------------------------------------------------------------------------------------------------------

@@ -3,8 +3,9 @@ paths, gemm_multi_kernel, gemm_tn_kernel / gemm_tn_lean_kernel (also behind fn_g
 per 16 x 16 tile against float64.
 
 The cases, the references, the mirror of the dispatch and the checkers are tests/helpers_gemm.py; tests/test_gemm_reference.py shows on the CPU that
-the tables reach what their ids claim, that the float32 restatement passes and that planted faults are rejected.  Every case here asserts through the
-mirror, on the real device addresses and leading dimensions, that it reaches the kernel instance, load path, grid form and reduction it names, runs
+the tables reach what their ids claim, that the mirror agrees with the library's own dispatch plan (fn_gemm_plan), that the float32 restatement passes
+and that planted faults are rejected.  Every case here asserts through the mirror, on the real device addresses and leading dimensions, that it reaches
+the kernel instance, load path, grid form and reduction it names - and that the library's plan for the very same tensors says so too -, runs
 both passes and prints its line of profiles/gemm_fp64_errors.txt.  The arithmetic of the kernel table is set to fp32 (a table of its own): the
 bf16 x 6 kernels have their own tests."""
 import ctypes as C
@@ -12,8 +13,8 @@ import ctypes as C
 import pytest
 import torch
 
-from helpers_gemm import (DWHH_CASES, G16, G32, G128, G3264, G6416, GEMM_CASES, GEMM_F, GEMM_SENTINEL, MULTI_CASES, assert_multi_plan_matches_case,
-                          assert_plan_matches_case, c_buffer, case_family, case_plan, check, dwhh_case_plan, dwhh_line, dwhh_operands, dwhh_plan, dwhh_problem,
+from helpers_gemm import (DWHH_CASES, G16, G32, G128, G3264, G6416, GEMM_CASES, GEMM_F, GEMM_SENTINEL, MULTI_CASES, assert_dwhh_mirror_matches_library,
+                          assert_mirror_matches_library, assert_multi_plan_matches_case, assert_plan_matches_case, c_buffer, case_family, case_plan, check, dwhh_case_plan, dwhh_line, dwhh_operands, dwhh_plan, dwhh_problem,
                           gemm_instance, gemm_line, gemm_problem, multi_case_plan, multi_line, multi_problems, stored)
 from mfn_import import load_package
 
@@ -76,6 +77,8 @@ def _run_gemm(ops, case, prob, lean=None):
     ws = _ws(ops, ops.lib.fn_gemm_ws_bytes(M, N, case["splitk"]))
     lean = case["lean"] if lean is None else lean
     plan = gemm_instance(case["a_k"], case["b_k"], M, N, case["K"], _ld(A), _ld(Bm), _ld(Cv), (_p(A), _p(Bm), _p(Cv), _p(bias), _p(ws)), case["splitk"], lean)
+    # ... and the mirror is what the library itself decides for these tensors (fn_gemm_plan through the argument preparation of ops.gemm)
+    assert_mirror_matches_library(plan, ops.gemm_plan(A, Bm, Cv, a_k=case["a_k"], b_k=case["b_k"], bias=bias, splitk=case["splitk"], lean=lean), M, N, case["id"])
     ops.gemm(A, Bm, Cv, a_k=case["a_k"], b_k=case["b_k"], alpha=case["alpha"], beta=case["beta"], bias=bias, splitk=case["splitk"], lean=lean)
     torch.cuda.synchronize()
     assert ws is None or _p(_ws(ops, 4)) == _p(ws)                   # the workspace the mirror saw is the one the launch used
@@ -119,6 +122,7 @@ def test_gru_dwhh_exact_and_every_tile_vs_fp64(ops, case):
         ws = _ws(ops, int(ops.lib.fn_gru_dwhh_ws_bytes(H, case["splitk"])))
         plan = dwhh_plan(H, rows, (_p(dgx), _p(dghn), _p(hp), _p(dW), _p(ws)), case["splitk"], case["lean"])
         assert plan == dwhh_case_plan(case) and plan["form"] == case["form"]
+        assert_dwhh_mirror_matches_library(plan, ops.gru_dwhh_plan(dgx, dghn, hp, dW, splitk=case["splitk"], lean=case["lean"]), H, case["id"])
         ops.gru_dwhh(dgx, dghn, hp, dW, beta=case["beta"], splitk=case["splitk"], lean=case["lean"])
         torch.cuda.synchronize()
         res[mode] = check(prob, cbuf.cpu(), 0, GEMM_F["dwhh"])
@@ -177,6 +181,7 @@ def _bare(ops, A, Bm, want_kernel, want_loads=None):
     assert plan["kernel"] == want_kernel, plan
     if want_loads is not None:
         assert plan["loads"][want_loads] > 0 and plan["loads"]["checked" if want_loads == "fast" else "fast"] == 0, plan
+    assert_mirror_matches_library(plan, ops.gemm_plan(A, Bm, Cm, a_k=True, b_k=True), M, N, want_kernel)
     ops.gemm(A, Bm, Cm, a_k=True, b_k=True)
     torch.cuda.synchronize()
     return Cm

@@ -2,7 +2,7 @@
 
 The shapes, the reference, the metric and the bound are tests/helpers_head.py; tests/test_head_reference.py shows on the CPU that the checker
 accepts the float32 restatement and rejects planted faults.  Each case asserts that its operands reach the K loop / kernel instance it names
-(the device-side / host-side conditions of csrc/gemm.hip restated on the real addresses) and prints its line of
+(the device-side / host-side conditions of csrc/gemm.hip restated on the real addresses; the host-side one also asked of the library, fn_gemm_plan) and prints its line of
 profiles/out_head_fp64_errors.txt."""
 import pytest
 import torch
@@ -114,6 +114,8 @@ def test_gemm_nt_direct_every_tile_vs_fp64(ops, case):
     prev = ops.nt_x6
     try:
         ops.nt_x6 = False
+        lp = ops.gemm_plan(A, Bm, Cv, a_k=True, b_k=True, bias=bias, lean=case["lean"], nt_x6=False)              # the library's own decision for these tensors
+        assert (lp["kernel"], lp["klen"], lp["ranges"], lp["grid"], lp["tiles"], lp["reduce"]) == (inst, K, 1, (256, 1, 1), 256, None), lp
         ops.gemm(A, Bm, Cv, a_k=True, b_k=True, alpha=NT_ALPHA, beta=case["beta"], bias=bias, lean=case["lean"], nt_x6=False)
         torch.cuda.synchronize()
     finally:

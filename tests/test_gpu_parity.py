@@ -551,6 +551,11 @@ def test_gemm_tn_bf16x6(ops, M, N, K, splitk):
     for x6 in (False, True):
         ops.dw_x6 = x6
         C = torch.full((M, N), float("nan"), device=DEV)
+        kern = ops.gemm_plan(A, B, C, a_k=False, b_k=False, splitk=splitk)["kernel"]          # what the library's dispatch launches for this very call
+        if M % 4 == 0 and N % 4 == 0:
+            assert kern.startswith("gemm_tn_x6") if x6 else kern == "gemm_tn_kernel", (x6, kern)
+        else:                                       # 342 x 512 and 200 x 130 dense: a leading dimension % 4 != 0, so neither arithmetic reaches a TN kernel - a staged fp32 instance runs both
+            assert kern.startswith("gemm_kernel<"), (x6, kern)
         ops.gemm(A, B, C, a_k=False, b_k=False, splitk=splitk)
         out[x6] = float((C.double() - ref).abs().max()) / scale
     ops.dw_x6 = _x6_default()
@@ -589,11 +594,17 @@ def test_gemm_tn_x6_producer_consumer_vs_per_wave_kernel(ops, M, N, K, splitk):
     MODES = (("perwave", False, True, False), ("tile128", False, False, False), ("tile256", "force", False, False),
              ("tile128_item", False, False, True), ("tile256_item", "force", False, True))
     ops.dw_x6 = True
+    probe = torch.empty(M, N, device=DEV)
 
     def run(fn):
         out = {}
         for name, wide, pw, item in MODES:
             ops.x6_wide, ops.x6_perwave, ops.x6_per_tile = wide, pw, item
+            kern = ops.gemm_plan(A, B, probe, a_k=False, b_k=False, splitk=splitk)["kernel"]          # the library's dispatch names the kernel the mode is for
+            if M % 4 == 0 and N % 4 == 0:
+                assert kern == {"perwave": "gemm_tn_x6_kernel", "tile128": "gemm_tn_x6w_kernel", "tile256": "gemm_tn_x6v_kernel"}[name.split("_")[0]], (name, kern)
+            else:                                   # 342 x 512, 200 x 130 and 130 x 70 dense: a leading dimension % 4 != 0 keeps every mode off the TN kernels (a staged fp32 instance)
+                assert kern.startswith("gemm_kernel<"), (name, kern)
             out[name] = fn()
         ops.x6_per_tile = False
         assert torch.equal(out["tile128"], out["tile128_item"]) and torch.equal(out["tile256"], out["tile256_item"])
@@ -674,6 +685,8 @@ def test_gemm_nt_bf16x6(ops, M, N, K):
         for x6 in (False, True):
             ops.dw_x6, ops.nt_x6 = x6, x6
             C = torch.full((M, N), float("nan"), device=DEV)
+            kern = ops.gemm_plan(A, W, C, a_k=True, b_k=True)["kernel"]          # what the library's dispatch launches for this very call
+            assert (kern == "gemm_nt_x6w_kernel") == x6 and (x6 or kern.startswith(("gemm_nt_direct_kernel", "gemm_kernel"))), (x6, kern)
             ops.gemm(A, W, C, a_k=True, b_k=True)
             err[x6] = float((C.double() - ref).abs().max()) / scale
             C2 = C0.clone()

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from helpers import SCAN_F_CAP, SCAN_MIN_REF
+from helpers_gemm import lib_gemm_plan
 from helpers_head import (HEAD_BY_ID, HEAD_CASES, HEAD_GRAD_SCALE, HEAD_SENTINEL, NT_BY_ID, NT_CASES, NT_ALPHA, NT_M, NT_N, check_head_vs_f64, check_nll_agree,
                           check_nt_vs_f64, head_buffers, head_case_path, head_fill_from, head_inputs, head_layout, head_path, head_reference, head_references,
                           head_tile_errors, nt_buffer, nt_case_instance, nt_direct_instance, nt_direct_steps, nt_layout, nt_references, old_metric_accepts,
@@ -137,6 +138,12 @@ def test_nt_case_reaches_its_instance(cid):
     lda, ldb, ldc = nt_layout(case)
     # the bf16 x 6 route would take the K % 32 == 0 cases if its flag were set: the calls switch it off
     assert nt_direct_instance(NT_M, NT_N, case["K"], lda, ldb, ldc, (0, 0, 0, 0), case["lean"], 1, x6=True) == (None if case["K"] % 32 == 0 and case["K"] >= 128 else inst)
+    # ... and the library's own dispatch (fn_gemm_plan, 256 compute units) decides the same, with and without the bf16 x 6 bit: one workgroup per tile
+    for x6 in (False, True):
+        lp = lib_gemm_plan(True, True, NT_M, NT_N, case["K"], lda, ldb, ldc, (0, 0, 0, 0, 0), 1, case["lean"], x6)
+        want = nt_direct_instance(NT_M, NT_N, case["K"], lda, ldb, ldc, (0, 0, 0, 0), case["lean"], 1, x6=x6)
+        assert lp["kernel"] == ("gemm_nt_x6w_kernel" if want is None else want)
+        assert (lp["klen"], lp["ranges"], lp["grid"], lp["tiles"], lp["reduce"], lp["reduce_blocks"], lp["msplit"]) == (case["K"], 1, (256, 1, 1), 256, None, 0, 0)
 
 
 def test_nt_cases_cover_every_remainder_with_and_without_a_steady_iteration():
@@ -151,7 +158,11 @@ def test_nt_cases_cover_every_remainder_with_and_without_a_steady_iteration():
     assert nt_direct_instance(**ok) == "gemm_nt_direct_kernel<4, 2>"
     for k, v in (("M", 1920), ("K", 48), ("K", 72), ("lda", 82), ("ldc", 2050), ("ptrs", (0, 4, 0, 0)), ("ptrs", (0, 0, 0, 8)), ("splitk", 2), ("lda", 1 << 19)):
         assert nt_direct_instance(**dict(ok, **{k: v})) is None, (k, v)
+        d = dict(ok, **{k: v})
+        lp = lib_gemm_plan(True, True, d["M"], d["N"], d["K"], d["lda"], d["ldb"], d["ldc"], d["ptrs"] + (0,), d["splitk"], False)
+        assert lp["kernel"].startswith("gemm_kernel<"), (k, v, lp)                 # the library sends each of them to a staged instance too
     assert nt_direct_instance(**dict(ok, a_k=False)) is None
+    assert lib_gemm_plan(True, True, 2048, 2048, 80, 80, 80, 2048, (0, 0, 0, 0, 0), 1, False)["kernel"] == "gemm_nt_direct_kernel<4, 2>"
 
 
 # ---- planted faults ------------------------------------------------------------------------------------------------------------------------
