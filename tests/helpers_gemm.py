@@ -6,6 +6,8 @@ gemm_tn_kernel / gemm_tn_lean_kernel (also behind fn_gru_dwhh_f32) and the two s
                              and addresses: which kernel instance a call launches, its K ranges, the grid form of a TN launch, the slab
                              reduction that follows, and per tile and K range whether the staged loop takes load_fast or load_checked;
                              its host-side fields are checked against the library's own answer (fn_gemm_plan / fn_gru_dwhh_plan)
+  x6_tn_plan / x6_nt_plan / trip_schedule   the same for a bf16 x 6 launch (the mode bits, 128 x 128 or 128 x 256 tiles, workgroups that walk items, per K
+                             range its 32-k blocks and what x6w_trips makes of them); cases, passes and restatement of those kernels: helpers_gemm_x6.py
   lib_gemm_plan / lib_dwhh_plan / assert_mirror_matches_library   that answer, and the comparison
   restate32(prob)            the float32 restatement: every accumulator adds its K range in order, as sequential float32 additions of 8-wide chunk
                              products; the accumulators of a split launch are then added in slab order; alpha, bias, beta C as the epilogue
@@ -95,10 +97,14 @@ def lib_dwhh_plan(H, rows, ptrs, splitk, lean, x6=False, cus=PLAN_CUS):
 def assert_mirror_matches_library(mp, lp, M, N, what=""):
     """the host-side fields of a mirror plan (gemm_instance / tn_plan) against the library's plan of the same call (lib_gemm_plan, HipOps.gemm_plan):
     kernel, klen, ranges, grid form (and, the fp32 kernels have no walking form, the grid itself), reduce kernel and its trips, tiles, msplit"""
-    if mp["family"] == "x6":                         # the mirror names the family only; literal expectations: test_gemm_reference.py
-        assert lp["kernel"].startswith(mp["kernel"]), (what, mp["kernel"], lp)
-        return
     assert lp["kernel"] == mp["kernel"], (what, mp["kernel"], lp)
+    if mp["family"] == "x6":                         # the bf16 x 6 kernels: the grid itself (a walking launch is cus x 1 x 1), item count = tiles x ranges
+        trips = 0 if lp["reduce"] is None else _cdiv(M * N // 4 if lp["reduce"] == "slab_reduce4_kernel" else M * N, lp["reduce_blocks"] * 256)
+        got = (lp["klen"], lp["ranges"], lp["grid"], lp["tiles"], lp["reduce"], trips, lp["msplit"])
+        assert got == (mp["klen"], mp["ranges"], mp["grid_xyz"], mp["tiles"], mp["reduce"], mp["reduce_trips"], mp["msplit"]), (what, mp, lp)
+        assert mp["items"] == lp["tiles"] * lp["ranges"] and mp["walks"] == (lp["grid"][2] == 1 and lp["grid"][0] < mp["items"]), (what, mp, lp)
+        assert (lp["reduce_blocks"] == 0) == (mp["ranges"] == 1) and lp["reduce_blocks"] <= 2048
+        return
     if mp["family"] == "nt-direct":
         tiles = (M // 128) * (N // 128)
         assert (lp["klen"] > 0, lp["ranges"], lp["grid"], lp["tiles"], lp["reduce"], lp["reduce_blocks"]) == (True, 1, (tiles, 1, 1), tiles, None, 0), (what, lp)
@@ -153,9 +159,76 @@ def staged_loads(BM, BN, BK, a_k, b_k, M, N, lda, ldb, pA, pB, ranges):
     return n
 
 
-def tn_plan(M, N, K, ldc, pC, pbias, pws, splitk, lean, x6=False, msplit=0):
+X6P, X6W, X6V, NTX6 = "gemm_tn_x6_kernel", "gemm_tn_x6w_kernel", "gemm_tn_x6v_kernel", "gemm_nt_x6w_kernel"
+# x6w_trips<NS, LEAD, PARTIAL> as each producer / consumer kernel instantiates it (x6w_produce, x6v_produce, x6w_produce_nt)
+X6_TRIPS = {X6W: (3, 2, True), X6V: (2, 1, True), NTX6: (3, 2, False)}
+
+
+def x6_bits(x6):
+    """x6 as it reaches the mirror (True = FN_GEMM_BF16X6 alone, or the bits themselves) -> (per-wave, wide, per-tile)"""
+    lib = _lib()
+    bits = 0 if x6 is True else int(x6)
+    perwave = bool(bits & lib.GEMM_X6_PERWAVE)
+    return perwave, bool(bits & lib.GEMM_X6_WIDE) and not perwave, bool(bits & lib.GEMM_X6_PERTILE)
+
+
+def trip_schedule(nblk, NS, LEAD, PARTIAL):
+    """x6w_trips(nblk) restated: the prologue requests blocks 0 .. NS + LEAD - 2 and cuts blocks 0 .. LEAD - 1 (those that exist); steady passes of NS
+    fused trips run while t + REST < nblk, REST = 2 NS + LEAD - 2 + PARTIAL; the tail runs the trips that are left (<= REST) through the guarded
+    request / cut.  prologue_only: every block was cut in the prologue (no trip cuts anything).  One barrier per block and one more."""
+    REST = 2 * NS + LEAD - 2 + (1 if PARTIAL else 0)
+    t = passes = 0
+    while t + REST < nblk:
+        t += NS
+        passes += 1
+    return dict(requested=min(NS + LEAD - 1, nblk), cut=min(LEAD, nblk), prologue_only=nblk <= LEAD, passes=passes, tail=nblk - t, rest=REST,
+                barriers=1 + nblk)
+
+
+def x6_blocks(kernel, ranges):
+    """per K range (32-k blocks the kernel's bf16 loop runs, rows of the partial last block, what becomes of it): the producer / consumer kernels count
+    a partial block as a block (its missing rows are zeros) and run the trip schedule over them; the per-wave kernel runs whole blocks in pairs plus an
+    odd one and the partial rows as fp32 MFMA steps of four"""
+    out = []
+    for k0, k1 in ranges:
+        n, r = (k1 - k0) >> 5, (k1 - k0) & 31
+        if kernel == X6P:
+            out.append((n, r, dict(pairs=n // 2, odd=n & 1, fp32_steps=_cdiv(r, 4))))
+        else:
+            out.append((n + (r > 0), r, trip_schedule(n + (r > 0), *X6_TRIPS[kernel])))
+    return out
+
+
+def x6_tn_plan(M, N, K, ldc, pC, pbias, pws, splitk, x6, msplit, cus):
+    """a bf16 x 6 TN launch in full: the kernel by the mode bits, K ranges of whole 32-k blocks, 128 x 128 or 128 x 256 tiles, the grid form and the grid
+    itself - a 1-D launch of a producer / consumer kernel with more (tile, K range) items than compute units is one workgroup per compute unit WALKING
+    items blockIdx.x, + gridDim.x, .. unless FN_GEMM_X6_PERTILE or a CU count that is no multiple of 8 -, msplit, the slab reduction, and per K range
+    its blocks and trip schedule"""
+    perwave, wide, pertile = x6_bits(x6)
+    kernel = X6P if perwave else X6V if wide else X6W
+    klen, S = split_ranges(K, splitk, 32)
+    tiles = _cdiv(M, 128) * _cdiv(N, 256 if wide else 128)
+    one_d = S > 1 and S % 8 == 0
+    items = tiles * S
+    walks = not perwave and one_d and not pertile and cus >= 8 and cus % 8 == 0 and items > cus
+    red, trips = slab_reduction(S, M, N, ldc, pws, pC, pbias)
+    return dict(kernel=kernel, family="x6", klen=klen, ranges=S, tiles=tiles, items=items, grid="1d" if one_d else "3d", walks=walks,
+                grid_xyz=(cus if walks else items if one_d else tiles, 1, 1 if one_d else S), msplit=msplit, reduce=red, reduce_trips=trips,
+                blocks=x6_blocks(kernel, k_ranges(K, klen)), loads=None)
+
+
+def x6_nt_plan(M, N, K, x6, cus):
+    """gemm_nt_x6w_kernel: whole 128 x 128 tiles, K / 32 whole blocks, one workgroup per tile or - more tiles than compute units - one per compute unit
+    walking tiles"""
+    tiles = (M // 128) * (N // 128)
+    walks = tiles > cus and cus >= 8 and cus % 8 == 0 and not x6_bits(x6)[2]
+    return dict(kernel=NTX6, family="x6", klen=K, ranges=1, tiles=tiles, items=tiles, grid="1d", walks=walks, grid_xyz=(cus if walks else tiles, 1, 1),
+                msplit=0, reduce=None, reduce_trips=0, blocks=x6_blocks(NTX6, [(0, K)]), loads=None)
+
+
+def tn_plan(M, N, K, ldc, pC, pbias, pws, splitk, lean, x6=False, msplit=0, cus=PLAN_CUS):
     if x6:
-        return dict(kernel="gemm_tn_x6", family="x6")
+        return x6_tn_plan(M, N, K, ldc, pC, pbias, pws, splitk, x6, msplit, cus)
     klen, S = split_ranges(K, splitk, 4)
     kernel = "gemm_tn_lean_kernel" if lean else "gemm_tn_kernel"
     PF = TN_PF[kernel]
@@ -168,16 +241,18 @@ def tn_plan(M, N, K, ldc, pC, pbias, pws, splitk, lean, x6=False, msplit=0):
                 reduce_trips=trips, steps=steps, tiles=_cdiv(M, 128) * _cdiv(N, 128), msplit=msplit, loads=None)
 
 
-def gemm_instance(a_k, b_k, M, N, K, lda, ldb, ldc, ptrs, splitk, lean, x6=False):
-    """what fn_gemm_f32 launches for this call.  ptrs = (A, B, C, bias[, workspace]) addresses, 0 = none; splitk = the K ranges asked for.
-    dict(kernel, family, klen, ranges, reduce, reduce_trips, and for the TN kernels grid / steps, for the staged kernel loads / nk)"""
+def gemm_instance(a_k, b_k, M, N, K, lda, ldb, ldc, ptrs, splitk, lean, x6=False, cus=PLAN_CUS):
+    """what fn_gemm_f32 launches for this call.  ptrs = (A, B, C, bias[, workspace]) addresses, 0 = none; splitk = the K ranges asked for; x6: False, True
+    (FN_GEMM_BF16X6) or the bf16 x 6 bits; cus: compute units (only the bf16 x 6 producer / consumer kernels' grids depend on it).
+    dict(kernel, family, klen, ranges, reduce, reduce_trips, and for the TN kernels grid / steps, for the staged kernel loads / nk, for the bf16 x 6
+    kernels x6_tn_plan / x6_nt_plan)"""
     pA, pB, pC, pbias = ptrs[:4]
     pws = ptrs[4] if len(ptrs) > 4 else 0
     if not a_k and not b_k and lda % 4 == 0 and ldb % 4 == 0 and lda >= 4 and ldb >= 4 and (pA | pB) % 16 == 0:
-        return tn_plan(M, N, K, ldc, pC, pbias, pws, splitk, lean, x6)
+        return tn_plan(M, N, K, ldc, pC, pbias, pws, splitk, lean, x6, cus=cus)
     al = lda % 4 == 0 and ldb % 4 == 0 and ldc % 4 == 0 and (pA | pB | pC | pbias) % 16 == 0
     if x6 and a_k and b_k and splitk <= 1 and M % 128 == 0 and N % 128 == 0 and K % 32 == 0 and K >= 128 and al and (M // 128) * (N // 128) >= 128:
-        return dict(kernel="gemm_nt_x6w_kernel", family="x6")
+        return x6_nt_plan(M, N, K, x6, cus)
     direct = nt_direct_instance(M, N, K, lda, ldb, ldc, (pA, pB, pC, pbias), lean, splitk, a_k, b_k, x6=False)
     if direct is not None:
         return dict(kernel=direct, family="nt-direct")
@@ -214,15 +289,15 @@ def multi_plan(a_k, b_k, jobs):
     return dict(kernel="gemm_multi_kernel", family="multi", grid=grid, jobs=out)
 
 
-def dwhh_plan(H, rows, ptrs, splitk, lean, x6=False):
+def dwhh_plan(H, rows, ptrs, splitk, lean, x6=False, cus=PLAN_CUS):
     """fn_gru_dwhh_f32: ptrs = (dgx, dghn, hprev, dW[, workspace]).  One split-A launch of the TN kernel (msplit = 2H, rows >= 2H from dghn) when 2H
     is a multiple of the 128-row tile, else two fn_gemm_f32 products - which do not carry the lean flag on."""
     pgx, pghn, php, pdw = ptrs[:4]
     pws = ptrs[4] if len(ptrs) > 4 else 0
     if (2 * H) % 128 == 0 and H % 4 == 0 and (pgx | pghn | php) % 16 == 0:
-        return dict(form="one-launch", launches=[tn_plan(3 * H, H, rows, H, pdw, 0, pws, splitk, lean, x6, msplit=2 * H)])
-    return dict(form="two-products", launches=[gemm_instance(False, False, 2 * H, H, rows, 3 * H, H, H, (pgx, php, pdw, 0, pws), splitk, False, x6),
-                                               gemm_instance(False, False, H, H, rows, H, H, H, (pghn, php, pdw + 8 * H * H, 0, pws), splitk, False, x6)])
+        return dict(form="one-launch", launches=[tn_plan(3 * H, H, rows, H, pdw, 0, pws, splitk, lean, x6, msplit=2 * H, cus=cus)])
+    return dict(form="two-products", launches=[gemm_instance(False, False, 2 * H, H, rows, 3 * H, H, H, (pgx, php, pdw, 0, pws), splitk, False, x6, cus),
+                                               gemm_instance(False, False, H, H, rows, H, H, H, (pghn, php, pdw + 8 * H * H, 0, pws), splitk, False, x6, cus)])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -274,24 +349,31 @@ def reference64(pieces, alpha, bias, beta, C0):
     return acc + beta * C0.double() if beta != 0.0 else acc
 
 
-def assert_exact_condition(pieces, bias, beta, C0, cid):
+def assert_exact_condition(pieces, bias, beta, C0, cid, max_abs=(8, 8)):
     """sum |a||b| + |bias| + |beta c| < 2^24 in every output element: every partial sum of the kernel, in any order and across K ranges and slabs, is then
-    an integer (or half-integer) that float32 holds exactly"""
+    an integer (or half-integer) that float32 holds exactly.  max_abs: the span of the integers of a and of b ([-8, 8] unless a pass says otherwise)"""
     mag = sum(a.double().abs() @ b.double().abs() for a, b in pieces)
     if bias is not None:
         mag = mag + bias.double().abs()
     mag = mag + abs(beta) * C0.double().abs()
     assert float(mag.max()) < 2.0 ** 24, "%s: exact pass would leave the integers float32 holds (%.0f)" % (cid, float(mag.max()))
     for a, b in pieces:
-        assert bool((a == a.round()).all()) and bool((b == b.round()).all()) and float(a.abs().max()) <= 8 and float(b.abs().max()) <= 8
+        assert bool((a == a.round()).all()) and bool((b == b.round()).all()) and float(a.abs().max()) <= max_abs[0] and float(b.abs().max()) <= max_abs[1]
 
 
-def make_problem(cid, mode, M, N, pieces, chains, alpha, beta, bias, C0):
-    """pieces = [(a [M][K], b [K][N])] in logical form; chains index into them (see restate32)"""
+def make_problem(cid, mode, M, N, pieces, chains, alpha, beta, bias, C0, restate=None, max_abs=(8, 8), defer=False):
+    """pieces = [(a [M][K], b [K][N])] in logical form; chains index into them (see restate32).  restate: another float32 restatement of the kernel's
+    arithmetic than restate32 (a callable without arguments: the bf16 x 6 kernels, helpers_gemm_x6.py).  defer (exact problems only, whose check needs no
+    e_ref): the restatement is not run here - prob['restate']() runs it (a CPU test asks that it equals float64; a GPU test has no use for it)"""
     ref64 = reference64(pieces, alpha, bias, beta, C0)
     if mode == "exact":
-        assert_exact_condition(pieces, bias, beta, C0, cid)
-    fake32 = restate32(chains, alpha, bias, beta, C0, M, N)
+        assert_exact_condition(pieces, bias, beta, C0, cid, max_abs)
+    if restate is None:
+        restate = lambda: restate32(chains, alpha, bias, beta, C0, M, N)                         # noqa: E731
+    if defer:
+        assert mode == "exact"
+        return dict(id=cid, mode=mode, M=M, N=N, pieces=pieces, chains=chains, alpha=alpha, beta=beta, bias=bias, C0=C0, ref64=ref64, restate=restate)
+    fake32 = restate()
     e_ref, den = tile_errors(fake32, ref64)
     assert den.min() >= SCAN_MIN_REF, "input condition: %s has a tile maximum of %.3e < 2**-100" % (cid, den.min())
     assert np.isfinite(e_ref).all()
@@ -327,8 +409,10 @@ def check_exact(prob, cbuf, c0=0):
     ne = torch.nonzero(~(got == prob["ref64"]))                 # NaN counts as different
     if ne.numel():
         i, j = int(ne[0][0]), int(ne[0][1])
-        raise AssertionError("%s: exact pass: %d of %d elements differ from float64, first at (%d, %d): got %r, want %r" % (
-            prob["id"], ne.shape[0], got.numel(), i, j, float(got[i, j]), float(prob["ref64"][i, j])))
+        tiles = {(int(r) // 16, int(c) // 16) for r, c in ne.tolist()}
+        raise AssertionError("%s: exact pass: %d of %d elements differ from float64 in %d of %d tiles, first at (%d, %d) in tile (rows %d.., columns %d..): got %r, want %r" % (
+            prob["id"], ne.shape[0], got.numel(), len(tiles), _cdiv(prob["M"], 16) * _cdiv(prob["N"], 16), i, j, i // 16 * 16, j // 16 * 16, float(got[i, j]),
+            float(prob["ref64"][i, j])))
     return got.numel()
 
 

@@ -257,8 +257,8 @@ X6W, X6V, X6P, NTX6 = "gemm_tn_x6w_kernel", "gemm_tn_x6v_kernel", "gemm_tn_x6_ke
 
 
 def test_bf16x6_plans_are_what_the_launchers_computed():
-    """The mirror only names the family of a bf16 x 6 launch, so these are literal expectations, worked out by hand from launch_tn / launch_tn_x6 /
-    fn_gemm_f32 as they stood before the plan existed.  TN, 1536 x 512 x 65536 (48 tiles of 128 x 128, 24 of 128 x 256): 16 ranges asked for -> klen =
+    """Literal expectations for the bf16 x 6 launches, worked out by hand from launch_tn / launch_tn_x6 / fn_gemm_f32 as they stood before the plan
+    existed (the mirror restates these launches too: x6_tn_plan / x6_nt_plan, checked against the library in test_gemm_x6_reference.py).  TN, 1536 x 512 x 65536 (48 tiles of 128 x 128, 24 of 128 x 256): 16 ranges asked for -> klen =
     ceil(4096 / 32) 32 = 4096, 16 ranges, a 1-D grid of 48 x 16 = 768 items that one workgroup per compute unit walks (256) - unless FN_GEMM_X6_PERTILE, the
     per-wave kernel, or 250 compute units (not a multiple of the 8 XCDs); 12 ranges -> klen = ceil(5462 / 32) 32 = 5472, 12 ranges, not a multiple of 8:
     48 x 1 x 12; no split: 48 x 1 x 1 and no reduction.  The reduction of 1536 x 512 aligned floats: float4, 196608 / 256 = 768 blocks.
