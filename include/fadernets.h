@@ -363,6 +363,92 @@ int fn_gru_seq_bwd(const FnGruBwd* scans, int n_scans, void* stream);
  * enqueuing anything (1 / 0).  Same element-wise gate arithmetic; gradients differ from the default kernels by fp32 rounding only. */
 int fn_gru_bwd_x6_ok(const FnGruBwd* scans, int n_scans);
 
+/* The launch plan of fn_gru_seq_fwd / fn_gru_seq_bwd / fn_gru_cell_f32 (as fn_gemm_plan for the GEMMs): ONE pure host function per entry point
+ * (csrc/gru_plan.h: the descriptors and the number of compute units in; these structs out) that the launch goes by and that fn_gru_fwd_plan /
+ * fn_gru_bwd_plan / fn_gru_cell_plan hand out.  Addresses are inspected for NULL-ness and alignment only, never dereferenced.
+ * A scan plan is an ordered list of at most three candidates: the launch takes the first one whose workgroups are all resident at once (the
+ * weight-stationary kernels spin on counters that other workgroups of the launch advance); the per-step candidate needs no residency and is the last
+ * one when present.  A bf16 x 6 request has exactly one candidate, or status FN_E_UNSUPPORTED.
+ * cus > 0 stands for the compute units of the device (before cu_budget; nothing touches the device then, fits = -1 and chosen = -1 unless the per-step
+ * candidate is the only one), cus == 0 asks the current device: fits is what the occupancy query of the launch answers and chosen the candidate the
+ * launch takes (-1 with status FN_E_UNSUPPORTED when a bf16 x 6 candidate does not fit).  Nothing is enqueued.  status: what the call returns before
+ * anything is enqueued (FN_OK: it launches a candidate).  FN_E_NULL without `plan`, FN_E_SHAPE for cus < 0.
+ * The three entry points are additive: fn_version() stays 6. */
+enum FnGruKernel {               /* FnGruCandidate.kernel; the names of the instances in this order: _lib.GRU_PLAN_KERNELS */
+    FN_GRU_FWD_X6PP_1 = 0,       /* gru_fwd_x6pp_kernel<TH> */
+    FN_GRU_FWD_X6PP_2,
+    FN_GRU_FWD_X6_1,             /* gru_fwd_x6_kernel<MT> */
+    FN_GRU_FWD_X6_2,
+    FN_GRU_FWD_PP_1,             /* gru_fwd_pp_kernel<WK> */
+    FN_GRU_FWD_PP_2,
+    FN_GRU_FWD_WS_4_1_2,         /* gru_fwd_persist_kernel<WM, WK, MT, 4> */
+    FN_GRU_FWD_WS_4_1_1,
+    FN_GRU_FWD_WS_2_2_2,
+    FN_GRU_FWD_WS_2_2_1,
+    FN_GRU_FWD_WS_1_4_1,
+    FN_GRU_FWD_STEP,             /* gru_fwd_step_kernel<NS, TM, D>, one launch per time step */
+    FN_GRU_BWD_X6_1,             /* gru_bwd_x6_kernel<TH> */
+    FN_GRU_BWD_X6_2,
+    FN_GRU_BWD_RS_1,             /* gru_bwd_rs_kernel<TH> */
+    FN_GRU_BWD_RS_2,
+    FN_GRU_BWD_WS_4_1_2,         /* gru_bwd_persist_kernel<WM, WK, MT, 8> */
+    FN_GRU_BWD_WS_4_1_1,
+    FN_GRU_BWD_WS_2_2_2,
+    FN_GRU_BWD_WS_2_2_1,
+    FN_GRU_BWD_WS_1_4_1,
+    FN_GRU_BWD_STEP,             /* gru_bwd_step_kernel<NS, TM, TN, D>, one launch per time step (and one for dh0) */
+    FN_GRU_KERNELS
+};
+enum FnGruAbsent {               /* FnGruPlan.ws_absent: why the plan has no weight-stationary candidate (FN_GRU_WS_PRESENT: it has one) */
+    FN_GRU_WS_PRESENT = 0,
+    FN_GRU_WS_H_OVER_512,
+    FN_GRU_WS_NO_SYNC_WS,
+    FN_GRU_WS_MIXED_H,
+    FN_GRU_WS_UNALIGNED,         /* an operand of the 16-byte epilogue vectors is not 16-byte aligned */
+    FN_GRU_WS_T_BELOW_2,         /* nothing to keep stationary */
+    FN_GRU_WS_SLICES_OVER_CUS,
+    FN_GRU_WS_NO_ROW_BLOCK       /* no (or not the forced) row block whose groups fit the compute units; bf16 x 6: the shapes are not eligible */
+};
+typedef struct FnGruCandidate {
+    int32_t kernel;                 /* FnGruKernel */
+    int32_t rows_per_group, groups; /* weight-stationary: batch rows of a row group, row groups of the launch (sum over the scans) */
+    int32_t slices;                 /* weight-stationary: workgroups of a row group; grid = groups * slices */
+    int32_t grid, lds_bytes;        /* weight-stationary: workgroups and dynamic LDS of the launch */
+    int32_t no_hand;                /* 1: the compiler-scheduled K loops (FN_GRU_COMPILER_LOOPS) */
+    int32_t h0_triples;             /* initial states are packed as bf16 triples (1) or as fp32 fragments (0) */
+    int32_t resident;               /* 1: every workgroup of the grid must be resident at once */
+    int32_t fits;                   /* resident candidates: 1 / 0 as the occupancy query answers, -1 = not asked */
+    int32_t tm, tn, d, ns;          /* per-step: template arguments of the FIRST launch (tn = 0: forward) */
+    int32_t tiles, launches;        /* per-step: workgroups of the first launch; launches of the call */
+} FnGruCandidate;
+typedef struct FnGruPlan {
+    int32_t status;                 /* FN_OK, or the FN_E_* the call returns before anything is enqueued */
+    int32_t n, chosen;              /* candidates; the one the launch takes (-1: not known / none) */
+    int32_t cus;                    /* compute units of the launch: the device's, or scans[0].cu_budget when that is smaller */
+    int32_t ws_absent;              /* FnGruAbsent */
+    FnGruCandidate cand[3];
+} FnGruPlan;
+int fn_gru_fwd_plan(const FnGruFwd* scans, int n_scans, int cus, FnGruPlan* plan);
+int fn_gru_bwd_plan(const FnGruBwd* scans, int n_scans, int cus, FnGruPlan* plan);
+
+enum FnGruCellFamily {           /* FnGruCellPlan.family; names: _lib.GRU_CELL_FAMILIES */
+    FN_CELL_STAGED = 0,          /* gru_cell_kernel<BM, WM, WN> */
+    FN_CELL_DIRECT,              /* gru_cell_direct_kernel<RT, PF, HAS_TAB, HAS_RB> */
+    FN_CELL_WLDS,                /* gru_cell_wlds_kernel<RT, PF, HAS_TAB, HAS_RB> */
+    FN_CELL_WLDS_OVL,            /* gru_cell_wlds_ovl_kernel<RT, PF, HAS_TAB, HAS_RB> */
+    FN_CELL_X6                   /* gru_cell_x6_kernel<HAS_TAB, HAS_RB> */
+};
+typedef struct FnGruCellPlan {
+    int32_t status;                 /* FN_OK, or the FN_E_* fn_gru_cell_f32 returns for these arguments */
+    int32_t family;                 /* FnGruCellFamily */
+    int32_t t0, t1, t2;             /* template arguments: BM, WM, WN (staged); RT, PF, 0 (direct, wlds, wlds-overlap); 0 (x6) */
+    int32_t has_tab, has_rb;        /* gx_table / gx_rowbias given: the HAS_TAB / HAS_RB instance of the families that have them */
+    int32_t kmax;                   /* the longer of the two K loops (H, or K1 with x) */
+    int32_t grid, threads, lds_bytes;
+    int32_t forced_honoured;        /* 1: variant names a form 1-18 and that form is what runs; 0: automatic choice, bf16 x 6, or the staged default stands in */
+} FnGruCellPlan;
+int fn_gru_cell_plan(const FnGruCell* c, FnGruCellPlan* plan);
+
 /* Recurrent weight gradient of one scan from its saved gate gradients (autograd of W_hh in nn.GRU / GRUCell,
  * trainer_gmm.py:249):  dW_hh[3H][H] = beta * dW_hh + [dgx[:, 0:2H] | dghn]^T hprev  over `rows` (time x batch) rows;
  * dgx [rows][3H], dghn [rows][H], hprev [rows][H] (the state BEFORE each step).  One split-K launch when 2H % 128 == 0. */

@@ -22,6 +22,15 @@ GEMM_PLAN_KERNELS = ("gemm_kernel<64,64,16>", "gemm_kernel<64,64,32>", "gemm_ker
                      "gemm_nt_direct_kernel<4, 2>", "gemm_nt_direct_kernel<1, 4>", "gemm_nt_x6w_kernel", "gemm_tn_kernel", "gemm_tn_lean_kernel",
                      "gemm_tn_x6_kernel", "gemm_tn_x6w_kernel", "gemm_tn_x6v_kernel")
 GEMM_PLAN_REDUCES = (None, "slab_reduce_kernel", "slab_reduce4_kernel")
+# FnGruCandidate.kernel -> the kernel instance (enum FnGruKernel, in its order), FnGruPlan.ws_absent (enum FnGruAbsent), FnGruCellPlan.family
+GRU_PLAN_KERNELS = ("gru_fwd_x6pp_kernel<1>", "gru_fwd_x6pp_kernel<2>", "gru_fwd_x6_kernel<1>", "gru_fwd_x6_kernel<2>", "gru_fwd_pp_kernel<1>",
+                    "gru_fwd_pp_kernel<2>", "gru_fwd_persist_kernel<4, 1, 2, 4>", "gru_fwd_persist_kernel<4, 1, 1, 4>", "gru_fwd_persist_kernel<2, 2, 2, 4>",
+                    "gru_fwd_persist_kernel<2, 2, 1, 4>", "gru_fwd_persist_kernel<1, 4, 1, 4>", "gru_fwd_step_kernel",
+                    "gru_bwd_x6_kernel<1>", "gru_bwd_x6_kernel<2>", "gru_bwd_rs_kernel<1>", "gru_bwd_rs_kernel<2>", "gru_bwd_persist_kernel<4, 1, 2, 8>",
+                    "gru_bwd_persist_kernel<4, 1, 1, 8>", "gru_bwd_persist_kernel<2, 2, 2, 8>", "gru_bwd_persist_kernel<2, 2, 1, 8>",
+                    "gru_bwd_persist_kernel<1, 4, 1, 8>", "gru_bwd_step_kernel")
+GRU_PLAN_ABSENT = (None, "H > 512", "no sync_ws", "mixed H", "unaligned", "T < 2", "slices > cus", "no row block")
+GRU_CELL_FAMILIES = ("staged", "direct", "wlds", "wlds-overlap", "x6")
 GRU_ROWS_MASK = 0xFF         # forced rows per workgroup (scans) / forced form 1-18 (cells)
 GRU_ALT_TILING = 0x100       # the alternative wave tiling of the 64-row configuration
 GRU_SYNC_ZEROED = 0x200      # the sync_ws counters are already zero
@@ -93,6 +102,36 @@ class FnGemmPlan(C.Structure):
         """kernel and reduce by name, grid as (x, y, z)"""
         return dict(kernel=GEMM_PLAN_KERNELS[self.kernel], klen=self.klen, ranges=self.ranges, grid=(self.grid_x, self.grid_y, self.grid_z), tiles=self.tiles,
                     reduce=GEMM_PLAN_REDUCES[self.reduce], reduce_blocks=self.reduce_blocks, msplit=self.msplit)
+
+
+class FnGruCandidate(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("kernel", "rows_per_group", "groups", "slices", "grid", "lds_bytes", "no_hand", "h0_triples", "resident", "fits",
+                                         "tm", "tn", "d", "ns", "tiles", "launches")]
+
+    def as_dict(self):
+        """kernel by name; fits: True / False / None (not asked)"""
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d.update(kernel=GRU_PLAN_KERNELS[self.kernel], fits=None if self.fits < 0 else bool(self.fits))
+        return d
+
+
+class FnGruPlan(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n", C.c_int32), ("chosen", C.c_int32), ("cus", C.c_int32), ("ws_absent", C.c_int32), ("cand", FnGruCandidate * 3)]
+
+    def as_dict(self):
+        """candidates in the order the launch tries them; chosen: index of the one it takes (None: not known / none)"""
+        return dict(status=self.status, chosen=None if self.chosen < 0 else self.chosen, cus=self.cus, ws_absent=GRU_PLAN_ABSENT[self.ws_absent],
+                    candidates=[self.cand[i].as_dict() for i in range(self.n)])
+
+
+class FnGruCellPlan(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("status", "family", "t0", "t1", "t2", "has_tab", "has_rb", "kmax", "grid", "threads", "lds_bytes", "forced_honoured")]
+
+    def as_dict(self):
+        """family by name, template arguments as a tuple"""
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d.update(family=GRU_CELL_FAMILIES[self.family], template=(self.t0, self.t1, self.t2), forced_honoured=bool(self.forced_honoured))
+        return d
 
 
 class FnColsumJob(C.Structure):
@@ -192,6 +231,9 @@ SIGNATURES = {
     "fn_gru_seq_fwd": (C.c_int, [C.POINTER(FnGruFwd), C.c_int, vp]),
     "fn_gru_fwd_x6_ok": (C.c_int, [C.POINTER(FnGruFwd), C.c_int]),
     "fn_gru_cell_f32": (C.c_int, [C.POINTER(FnGruCell), vp]),
+    "fn_gru_fwd_plan": (C.c_int, [C.POINTER(FnGruFwd), C.c_int, C.c_int, C.POINTER(FnGruPlan)]),
+    "fn_gru_bwd_plan": (C.c_int, [C.POINTER(FnGruBwd), C.c_int, C.c_int, C.POINTER(FnGruPlan)]),
+    "fn_gru_cell_plan": (C.c_int, [C.POINTER(FnGruCell), C.POINTER(FnGruCellPlan)]),
     "fn_out_argmax_f32": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "fn_best_tokens": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "fn_gru_seq_bwd": (C.c_int, [C.POINTER(FnGruBwd), C.c_int, vp]),

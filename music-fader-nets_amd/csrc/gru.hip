@@ -1110,23 +1110,10 @@ __global__ __launch_bounds__(256) void best_tokens_kernel(const unsigned long lo
     }
 }
 
-static bool cell_direct_ok(const CellArgs& a) {
-    auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-    if ((a.H % 32) != 0 || !al(a.h_prev) || !al(a.w_hh) || (a.ldh & 3) || (a.ldw_hh & 3)) return false;
-    if (!al(a.h_out) || (a.ldo & 3) || !al(a.b_hh) || (a.b_ih && !al(a.b_ih)) || (a.gx_table && !al(a.gx_table)) || (a.gx_rowbias && !al(a.gx_rowbias))) return false;
-    if ((long)a.B * a.ldh * 4 >= (1L << 32) || 3L * a.H * a.ldw_hh * 4 >= (1L << 32)) return false;
-    if (a.x) {
-        if ((a.K1 % 16) != 0 || !al(a.x) || !al(a.w_ih) || (a.ldx & 3) || (a.ldw_ih & 3)) return false;
-        if ((long)a.B * a.ldx * 4 >= (1L << 32) || 3L * a.H * a.ldw_ih * 4 >= (1L << 32)) return false;
-    }
-    return true;
-}
-
 template <int RT, int PF>
-int launch_cell_direct(const CellArgs& a, hipStream_t st) {
-    const int tiles = ((a.B + 32 * RT - 1) / (32 * RT)) * (a.H / 32);
+int launch_cell_direct(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
     return cell_tab_rb_switch(a, [&](auto TAB, auto RB) {
-        hipLaunchKernelGGL((gru_cell_direct_kernel<RT, PF, decltype(TAB)::value, decltype(RB)::value>), dim3(tiles), dim3(NT), 0, st, a);
+        hipLaunchKernelGGL((gru_cell_direct_kernel<RT, PF, decltype(TAB)::value, decltype(RB)::value>), dim3(p.grid), dim3(NT), 0, st, a);
         FN_CHECK_LAUNCH();
         return (int)FN_OK;
     });
@@ -1209,25 +1196,17 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_kernel(const CellArgs a, int
 }
 
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
-int launch_cell_wlds_inst(const CellArgs& a, int kmax, size_t lds, hipStream_t st) {
+int launch_cell_wlds_inst(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
     auto k = gru_cell_wlds_kernel<RT, PF, HAS_TAB, HAS_RB>;
-    if (const int rc = fn_set_max_lds<gru_cell_wlds_kernel<RT, PF, HAS_TAB, HAS_RB>>(160 * 1024, FN_E_SHAPE)) return rc;
-    const int tiles = ((a.B + 64 * RT - 1) / (64 * RT)) * (a.H / 16);
-    hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), lds, st, a, kmax);
+    if (const int rc = fn_set_max_lds<gru_cell_wlds_kernel<RT, PF, HAS_TAB, HAS_RB>>(GRU_CELL_MAX_LDS, FN_E_SHAPE)) return rc;
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(NT), (size_t)p.lds_bytes, st, a, (int)p.kmax);
     FN_CHECK_LAUNCH();
     return FN_OK;
 }
 
-static bool cell_wlds_ok(const CellArgs& a) {
-    const int kmax = a.x ? (a.K1 > a.H ? a.K1 : a.H) : a.H;
-    return (size_t)48 * kmax * 4 + 4 * 4 * 320 * 4 <= (size_t)160 * 1024;
-}
-
 template <int RT, int PF>
-int launch_cell_wlds(const CellArgs& a, hipStream_t st) {
-    const int kmax = a.x ? (a.K1 > a.H ? a.K1 : a.H) : a.H;
-    const size_t lds = (size_t)48 * kmax * 4 + 4 * 4 * 320 * 4;
-    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_wlds_inst<RT, PF, decltype(TAB)::value, decltype(RB)::value>(a, kmax, lds, st); });
+int launch_cell_wlds(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
+    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_wlds_inst<RT, PF, decltype(TAB)::value, decltype(RB)::value>(a, p, st); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1381,25 +1360,18 @@ __global__ __launch_bounds__(X6W_NT) void gru_cell_x6_kernel(const CellArgs a) {
     x6w_barrier_p();                                     // E1: the producers take it from here
 }
 
-static bool cell_x6_ok(const CellArgs& a) {
-    const uintptr_t al = (uintptr_t)a.x | (uintptr_t)a.w_ih | (uintptr_t)a.h_prev | (uintptr_t)a.w_hh | (uintptr_t)a.h_out | (uintptr_t)a.b_hh | (uintptr_t)a.b_ih |
-                         (uintptr_t)a.gx_table | (uintptr_t)a.gx_rowbias;
-    return (a.B % 128) == 0 && (a.H % 32) == 0 && a.H >= 64 && (!a.x || ((a.K1 % 32) == 0 && (a.ldx & 3) == 0 && (a.ldw_ih & 3) == 0)) && (a.ldh & 3) == 0 &&
-           (a.ldw_hh & 3) == 0 && (a.ldo & 3) == 0 && (al & 15) == 0;
-}
-
 template <bool HAS_TAB, bool HAS_RB>
-int launch_cell_x6_inst(const CellArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)X6W_STAGES * X6W_STAGE * 16;
+int launch_cell_x6_inst(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
+    static_assert(X6W_STAGES * X6W_STAGE * 16 == 3 * (4 * (4 * 3 * 64)) * 16 && X6W_NT == 512, "gru_plan.h: lds_cell_x6 and the x6 cell's threads");
     auto k = gru_cell_x6_kernel<HAS_TAB, HAS_RB>;
-    if (const int rc = fn_set_max_lds<gru_cell_x6_kernel<HAS_TAB, HAS_RB>>((int)lds, FN_E_SHAPE)) return rc;
-    hipLaunchKernelGGL(k, dim3((a.B / 128) * (a.H / 32)), dim3(X6W_NT), lds, st, a);
+    if (const int rc = fn_set_max_lds<gru_cell_x6_kernel<HAS_TAB, HAS_RB>>(p.lds_bytes, FN_E_SHAPE)) return rc;
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(X6W_NT), (size_t)p.lds_bytes, st, a);
     FN_CHECK_LAUNCH();
     return FN_OK;
 }
 
-int launch_cell_x6(const CellArgs& a, hipStream_t st) {
-    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_x6_inst<decltype(TAB)::value, decltype(RB)::value>(a, st); });
+int launch_cell_x6(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
+    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_x6_inst<decltype(TAB)::value, decltype(RB)::value>(a, p, st); });
 }
 
 FN_DEVINL void fn_wait_vm_n(int n) {                // n folds to a constant in fully unrolled loops
@@ -1552,29 +1524,25 @@ __global__ __launch_bounds__(NT) void gru_cell_wlds_ovl_kernel(const CellArgs a)
 }
 
 template <int RT, int PF, bool HAS_TAB, bool HAS_RB>
-int launch_cell_wlds_ovl_inst(const CellArgs& a, hipStream_t st) {
+int launch_cell_wlds_ovl_inst(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
     auto k = gru_cell_wlds_ovl_kernel<RT, PF, HAS_TAB, HAS_RB>;
-    if (const int rc = fn_set_max_lds<gru_cell_wlds_ovl_kernel<RT, PF, HAS_TAB, HAS_RB>>(160 * 1024, FN_E_SHAPE)) return rc;
-    const int tiles = ((a.B + 64 * RT - 1) / (64 * RT)) * (a.H / 16);
-    hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), (size_t)48 * 512 * 4 + 4 * 4 * 320 * 4, st, a);
+    if (const int rc = fn_set_max_lds<gru_cell_wlds_ovl_kernel<RT, PF, HAS_TAB, HAS_RB>>(GRU_CELL_MAX_LDS, FN_E_SHAPE)) return rc;
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(NT), (size_t)p.lds_bytes, st, a);
     FN_CHECK_LAUNCH();
     return FN_OK;
 }
 
-static bool cell_wlds_ovl_ok(const CellArgs& a) { return a.H == 512 && (!a.x || a.K1 == 512); }
-
 template <int RT, int PF>
-int launch_cell_wlds_ovl(const CellArgs& a, hipStream_t st) {
-    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_wlds_ovl_inst<RT, PF, decltype(TAB)::value, decltype(RB)::value>(a, st); });
+int launch_cell_wlds_ovl(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
+    return cell_tab_rb_switch(a, [&](auto TAB, auto RB) { return launch_cell_wlds_ovl_inst<RT, PF, decltype(TAB)::value, decltype(RB)::value>(a, p, st); });
 }
 
 template <int BM, int WM, int WN>
-int launch_cell(const CellArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)2 * (Stage<BM, GC_BK, true, NT>::WORDS + Stage<GC_BN, GC_BK, true, NT>::WORDS) * sizeof(float);
+int launch_cell(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
+    static_assert(2 * (Stage<BM, GC_BK, true, NT>::WORDS + Stage<GC_BN, GC_BK, true, NT>::WORDS) * sizeof(float) == 2 * (BM * 36 + 96 * 36) * 4, "gru_plan.h: lds_cell_staged");
     auto k = gru_cell_kernel<BM, WM, WN>;
-    if (const int rc = fn_set_max_lds<gru_cell_kernel<BM, WM, WN>>((int)lds, FN_E_SHAPE)) return rc;
-    const int tiles = ((a.B + BM - 1) / BM) * (a.H / 32);
-    hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), lds, st, a);
+    if (const int rc = fn_set_max_lds<gru_cell_kernel<BM, WM, WN>>(p.lds_bytes, FN_E_SHAPE)) return rc;
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(NT), (size_t)p.lds_bytes, st, a);
     FN_CHECK_LAUNCH();
     return FN_OK;
 }
@@ -1618,93 +1586,91 @@ int launch_pack(const float* src, int rows, int K, long ld, float* dst, hipStrea
 
 namespace {
 
-// ---- launch configuration -------------------------------------------------------------------------------
-// (TM, TN, D) = M-tiles per workgroup, N-tiles (backward only), chunks in flight per wave.  Picked by measurement on MI355X
-// (profiles/).
-struct Cfg { int tm, tn, d; };
-
+// ---- the per-step launches: the instances gru_plan.h's StepCfg can name --------------------------------------------------------------
 template <int TM, int D>
-void launch_fwd_ns(const FwdArgs& a, int tiles, hipStream_t st) {
-    if (a.n == 1) hipLaunchKernelGGL((gru_fwd_step_kernel<1, TM, D>), dim3(tiles), dim3(NT), 0, st, a);
-    else if (a.n <= 3) hipLaunchKernelGGL((gru_fwd_step_kernel<3, TM, D>), dim3(tiles), dim3(NT), 0, st, a);
-    else if (a.n == 4) hipLaunchKernelGGL((gru_fwd_step_kernel<4, TM, D>), dim3(tiles), dim3(NT), 0, st, a);
+void launch_fwd_ns(const FwdArgs& a, int ns, int tiles, hipStream_t st) {
+    if (ns == 1) hipLaunchKernelGGL((gru_fwd_step_kernel<1, TM, D>), dim3(tiles), dim3(NT), 0, st, a);
+    else if (ns == 3) hipLaunchKernelGGL((gru_fwd_step_kernel<3, TM, D>), dim3(tiles), dim3(NT), 0, st, a);
+    else if (ns == 4) hipLaunchKernelGGL((gru_fwd_step_kernel<4, TM, D>), dim3(tiles), dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((gru_fwd_step_kernel<8, TM, D>), dim3(tiles), dim3(NT), 0, st, a);
 }
 template <int TM, int TN, int D>
-void launch_bwd_ns(const BwdArgs& a, int tiles, hipStream_t st) {
-    if (a.n == 1) hipLaunchKernelGGL((gru_bwd_step_kernel<1, TM, TN, D>), dim3(tiles), dim3(NT), 0, st, a);
-    else if (a.n <= 3) hipLaunchKernelGGL((gru_bwd_step_kernel<3, TM, TN, D>), dim3(tiles), dim3(NT), 0, st, a);
-    else if (a.n == 4) hipLaunchKernelGGL((gru_bwd_step_kernel<4, TM, TN, D>), dim3(tiles), dim3(NT), 0, st, a);
+void launch_bwd_ns(const BwdArgs& a, int ns, int tiles, hipStream_t st) {
+    if (ns == 1) hipLaunchKernelGGL((gru_bwd_step_kernel<1, TM, TN, D>), dim3(tiles), dim3(NT), 0, st, a);
+    else if (ns == 3) hipLaunchKernelGGL((gru_bwd_step_kernel<3, TM, TN, D>), dim3(tiles), dim3(NT), 0, st, a);
+    else if (ns == 4) hipLaunchKernelGGL((gru_bwd_step_kernel<4, TM, TN, D>), dim3(tiles), dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((gru_bwd_step_kernel<8, TM, TN, D>), dim3(tiles), dim3(NT), 0, st, a);
 }
 
-bool launch_fwd(const Cfg& c, const FwdArgs& a, int tiles, hipStream_t st) {
-#define FN_F(TM_, D_) if (c.tm == TM_ && c.d == D_) { launch_fwd_ns<TM_, D_>(a, tiles, st); return true; }
-    FN_F(1, 2) FN_F(1, 3) FN_F(1, 4) FN_F(2, 2) FN_F(2, 3) FN_F(2, 4) FN_F(4, 1) FN_F(4, 2) FN_F(4, 3)
+bool launch_fwd(const StepCfg& c, const FwdArgs& a, hipStream_t st) {
+#define FN_F(TM_, D_) if (c.tm == TM_ && c.d == D_) { launch_fwd_ns<TM_, D_>(a, c.ns, c.tiles, st); return true; }
+    FN_F(4, 1) FN_F(2, 3)
 #undef FN_F
     return false;
 }
-bool launch_bwd(const Cfg& c, const BwdArgs& a, int tiles, hipStream_t st) {
-#define FN_B(TM_, TN_, D_) if (c.tm == TM_ && c.tn == TN_ && c.d == D_) { launch_bwd_ns<TM_, TN_, D_>(a, tiles, st); return true; }
-    FN_B(1, 1, 3) FN_B(1, 1, 4) FN_B(2, 1, 2) FN_B(2, 1, 3) FN_B(2, 1, 4) FN_B(2, 2, 2) FN_B(2, 2, 3) FN_B(2, 2, 4)
-    FN_B(4, 1, 2) FN_B(4, 1, 3) FN_B(4, 2, 2) FN_B(4, 2, 3) FN_B(4, 2, 4) FN_B(1, 2, 3) FN_B(1, 2, 4)
+bool launch_bwd(const StepCfg& c, const BwdArgs& a, hipStream_t st) {
+#define FN_B(TM_, TN_, D_) if (c.tm == TM_ && c.tn == TN_ && c.d == D_) { launch_bwd_ns<TM_, TN_, D_>(a, c.ns, c.tiles, st); return true; }
+    FN_B(4, 1, 2) FN_B(2, 1, 3)
 #undef FN_B
     return false;
 }
 
-// eligibility of the forced cell forms with the weight slice in LDS (fn_gru_cell_f32)
-bool cell_wlds_fits(const CellArgs& a) { return cell_direct_ok(a) && cell_wlds_ok(a); }
-bool cell_ovl_fits(const CellArgs& a) { return cell_direct_ok(a) && cell_wlds_ovl_ok(a); }
+// the cell plan -> the launcher of its family and template arguments
+int launch_cell_plan(const CellArgs& a, const FnGruCellPlan& p, hipStream_t st) {
+    if (p.family == FN_CELL_X6) return launch_cell_x6(a, p, st);
+#define FN_C(F_, L_, ...) if (p.family == F_ && p.t0 == FN_C0(__VA_ARGS__) && p.t1 == FN_C1(__VA_ARGS__)) return L_<__VA_ARGS__>(a, p, st);
+#define FN_C0(A_, ...) A_
+#define FN_C1(A_, B_, ...) B_
+    FN_C(FN_CELL_WLDS_OVL, launch_cell_wlds_ovl, 2, 4) FN_C(FN_CELL_WLDS_OVL, launch_cell_wlds_ovl, 3, 2)
+    FN_C(FN_CELL_WLDS_OVL, launch_cell_wlds_ovl, 4, 2) FN_C(FN_CELL_WLDS_OVL, launch_cell_wlds_ovl, 2, 2)
+    FN_C(FN_CELL_WLDS, launch_cell_wlds, 3, 4) FN_C(FN_CELL_WLDS, launch_cell_wlds, 3, 2) FN_C(FN_CELL_WLDS, launch_cell_wlds, 4, 2)
+    FN_C(FN_CELL_WLDS, launch_cell_wlds, 2, 4) FN_C(FN_CELL_WLDS, launch_cell_wlds, 2, 8)
+    FN_C(FN_CELL_DIRECT, launch_cell_direct, 4, 1) FN_C(FN_CELL_DIRECT, launch_cell_direct, 2, 4)
+    FN_C(FN_CELL_DIRECT, launch_cell_direct, 4, 2) FN_C(FN_CELL_DIRECT, launch_cell_direct, 2, 2)
+    FN_C(FN_CELL_STAGED, launch_cell, 128, 4, 1) FN_C(FN_CELL_STAGED, launch_cell, 128, 2, 2)
+    FN_C(FN_CELL_STAGED, launch_cell, 64, 4, 1) FN_C(FN_CELL_STAGED, launch_cell, 64, 2, 2)
+#undef FN_C
+#undef FN_C0
+#undef FN_C1
+    return FN_E_SHAPE;
+}
+
+// the device's answers for a plan made with its own CU count: fits of every resident candidate, chosen = the first candidate that fits (a bf16 x 6
+// candidate that does not: FN_E_UNSUPPORTED, there is no other)
+template <class Scan, class Ws>
+int resolve_plan(FnGruPlan& p, const Scan* scans, int n_scans, Ws&& ws) {
+    if (p.status != FN_OK) return FN_OK;
+    p.chosen = -1;
+    for (int i = 0; i < p.n; ++i) {
+        FnGruCandidate& c = p.cand[i];
+        if (c.resident)
+            if (const int rc = ws(c, scans, n_scans, p.cus, false, nullptr, &c.fits)) return rc;
+        if (c.fits && p.chosen < 0) p.chosen = i;
+    }
+    if (p.chosen < 0) p.status = FN_E_UNSUPPORTED;
+    return FN_OK;
+}
 
 }  // namespace
 
 extern "C" {
 
 int fn_gru_cell_f32(const FnGruCell* c, void* stream) {
-    if (!c || !c->h_prev || !c->w_hh || !c->b_hh || !c->h_out) return FN_E_NULL;
-    if (c->B <= 0 || c->H <= 0 || (c->H % 32) != 0 || c->ldh < c->H || c->ldo < c->H || c->ldw_hh < c->H) return FN_E_SHAPE;
-    if (c->x && (!c->w_ih || c->K1 <= 0 || c->ldx < c->K1 || c->ldw_ih < c->K1)) return FN_E_SHAPE;
-    if (c->gx_table && c->idx && c->idx_ld <= 0) return FN_E_SHAPE;
-    if (c->h_out == c->h_prev) return FN_E_SHAPE;              // other workgroups still read the old state
+    const FnGruCellPlan p = gru_cell_plan(c);
+    if (p.status != FN_OK) return p.status;
     CellArgs a;
     a.x = c->x; a.ldx = c->ldx; a.K1 = c->x ? c->K1 : 0; a.w_ih = c->w_ih; a.ldw_ih = c->ldw_ih;
     a.gx_table = c->gx_table; a.idx = c->idx; a.idx_ld = c->idx_ld; a.tok_const = c->start_token; a.gx_rowbias = c->gx_rowbias;
     a.h_prev = c->h_prev; a.ldh = c->ldh; a.w_hh = c->w_hh; a.ldw_hh = c->ldw_hh; a.b_ih = c->b_ih; a.b_hh = c->b_hh;
     a.h_out = c->h_out; a.ldo = c->ldo; a.B = c->B; a.H = c->H;
     a.best = reinterpret_cast<const unsigned long long*>(c->idx_best); a.best_v = c->best_v;
-    if (c->idx_best && (c->best_v <= 0 || !c->gx_table)) return FN_E_SHAPE;
-    const hipStream_t st = (hipStream_t)stream;
-    // FN_GRU_BF16X6 (as in FnGruFwd): the cell on the bf16 MFMA with exact triple splits where the shape allows it (else the fp32 cells below, as if the bit were clear)
-    const int variant = c->variant & ~FN_GRU_BF16X6;
-    if ((c->variant & FN_GRU_BF16X6) && cell_x6_ok(a)) return launch_cell_x6(a, st);
-    // measured (scratch/prof_decode_cells.sh, us per token of the tokens-only decode, profiles/r04_decode_cells_lds_free.txt): the form with the weight slice in
-    // LDS wants ONE workgroup per CU: 64 RT rows x 16 units with RT = ceil(rows / 512) - 1024 rows 71.5 (staged 82, LDS-free 77), 1152-1536 rows 88-89 (LDS-free 101-102);
-    // at 2048 rows (RT = 4) it is behind the LDS-free 128-row form (108 against 103)
-    if (variant == 0 && c->B > 512 && c->B <= 2048 && cell_direct_ok(a) && cell_wlds_ovl_ok(a)) {
-        // K1 = H = 512: the slice fills under the K loops - 640-1024 rows 60 (71), 1280-1536 rows 78-80 (88), 2048 rows 99.8 (102.9 LDS-free)
-        if (c->B <= 1024) return launch_cell_wlds_ovl<2, 2>(a, st);
-        if (c->B <= 1536) return launch_cell_wlds_ovl<3, 2>(a, st);
-        return launch_cell_wlds_ovl<4, 2>(a, st);
-    }
-    if (variant == 0 && c->B > 512 && cell_direct_ok(a)) {
-        if (c->B > 1536 || !cell_wlds_ok(a)) return c->B > 1024 ? launch_cell_direct<4, 2>(a, st) : launch_cell_direct<2, 4>(a, st);
-        return c->B > 1024 ? launch_cell_wlds<3, 2>(a, st) : launch_cell_wlds<2, 4>(a, st);
-    }
-    // tuning / tests: the forced forms, by kernel family (the staged forms agree bit for bit, the LDS-free forms 4-7 among themselves: another k order).
-    // A form this shape is not eligible for, and any other variant, runs the staged default.
-    static const struct { int variant; int (*launch)(const CellArgs&, hipStream_t); bool (*ok)(const CellArgs&); } forms[] = {
-        {15, launch_cell_wlds_ovl<2, 4>, cell_ovl_fits}, {16, launch_cell_wlds_ovl<3, 2>, cell_ovl_fits},
-        {17, launch_cell_wlds_ovl<4, 2>, cell_ovl_fits}, {18, launch_cell_wlds_ovl<2, 2>, cell_ovl_fits},
-        {13, launch_cell_wlds<3, 4>, cell_wlds_fits}, {14, launch_cell_wlds<3, 2>, cell_wlds_fits},
-        {9, launch_cell_wlds<4, 2>, cell_wlds_fits},           // (<4, 4> needs AGPR copies: not built)
-        {10, launch_cell_wlds<2, 4>, cell_wlds_fits}, {11, launch_cell_wlds<4, 2>, cell_wlds_fits}, {12, launch_cell_wlds<2, 8>, cell_wlds_fits},
-        {4, launch_cell_direct<4, 1>, cell_direct_ok}, {5, launch_cell_direct<2, 4>, cell_direct_ok},
-        {6, launch_cell_direct<4, 2>, cell_direct_ok}, {7, launch_cell_direct<2, 2>, cell_direct_ok},
-        {1, launch_cell<128, 4, 1>, nullptr}, {2, launch_cell<128, 2, 2>, nullptr}, {3, launch_cell<64, 4, 1>, nullptr}, {8, launch_cell<64, 2, 2>, nullptr},
-    };
-    for (const auto& f : forms)
-        if (f.variant == variant && (!f.ok || f.ok(a))) return f.launch(a, st);
-    return launch_cell<64, 2, 2>(a, st);
+    return launch_cell_plan(a, p, (hipStream_t)stream);
+}
+
+int fn_gru_cell_plan(const FnGruCell* c, FnGruCellPlan* plan) {
+    if (!plan) return FN_E_NULL;
+    *plan = gru_cell_plan(c);
+    return FN_OK;
 }
 
 int fn_out_argmax_f32(const float* h, int ldh, const float* W, int ldw, const float* bias, int B, int V, int K, uint64_t* best, void* stream) {
@@ -1753,36 +1719,39 @@ int fn_frag_pack(const float* src, int rows, int K, int ld, float* dst, void* st
     return launch_pack(src, rows, K, ld, dst, (hipStream_t)stream);
 }
 
+int fn_gru_fwd_plan(const FnGruFwd* scans, int n_scans, int cus, FnGruPlan* plan) {
+    if (!plan) return FN_E_NULL;
+    if (cus < 0) return FN_E_SHAPE;
+    *plan = gru_fwd_plan(scans, n_scans, cus > 0 ? cus : fn_cu_count());
+    return cus > 0 ? FN_OK : resolve_plan(*plan, scans, n_scans, fn_gru_fwd_ws);
+}
+
+int fn_gru_bwd_plan(const FnGruBwd* scans, int n_scans, int cus, FnGruPlan* plan) {
+    if (!plan) return FN_E_NULL;
+    if (cus < 0) return FN_E_SHAPE;
+    *plan = gru_bwd_plan(scans, n_scans, cus > 0 ? cus : fn_cu_count());
+    return cus > 0 ? FN_OK : resolve_plan(*plan, scans, n_scans, fn_gru_bwd_ws);
+}
+
 int fn_gru_seq_fwd(const FnGruFwd* scans, int n_scans, void* stream) {
-    if (!scans) return FN_E_NULL;
-    if (n_scans <= 0 || n_scans > FN_MAX_SCANS) return FN_E_COUNT;
-    int Tmax = 0;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruFwd& d = scans[s];
-        if (!d.w_hh_frag || !d.b_hh || !d.h_all || !d.frag_ws) return FN_E_NULL;
-        if (d.B <= 0 || d.T <= 0 || d.H <= 0 || (d.H % 32) != 0) return FN_E_SHAPE;
-        if (d.gx_table && !d.idx) return FN_E_NULL;
-        if ((((uintptr_t)d.w_hh_frag) | ((uintptr_t)d.frag_ws) | ((uintptr_t)d.h0_frag) | ((uintptr_t)d.h_last_frag)) & 15) return FN_E_ALIGN;
-        if (d.h0_frag && !d.h0) return FN_E_NULL;            // the gate epilogue reads the row-major state
-        Tmax = d.T > Tmax ? d.T : Tmax;
-    }
+    const FnGruPlan plan = gru_fwd_plan(scans, n_scans, fn_cu_count());
+    if (plan.status != FN_OK) return plan.status;
     hipStream_t st = (hipStream_t)stream;
-    {   // weight-stationary single launch when the configuration fits one workgroup per CU (gru_persist.hip)
-        const int rc = fn_gru_fwd_persist(scans, n_scans, st);
-        if (rc != FN_PERSIST_NA) return rc;
-        if (scans[0].variant & FN_GRU_BF16X6) return FN_E_UNSUPPORTED;      // the per-step kernels below do not read triple images
+    // weight-stationary single launch when a candidate fits one workgroup per CU (gru_persist.hip); asked first, so that a refused one enqueues nothing
+    for (int i = 0; i < plan.n && plan.cand[i].resident; ++i) {
+        int fits = 0;
+        const int rc = fn_gru_fwd_ws(plan.cand[i], scans, n_scans, plan.cus, true, st, &fits);
+        if (rc != FN_OK || fits) return rc;
     }
+    const FnGruCandidate& step = plan.cand[plan.n - 1];
+    if (step.resident) return FN_E_UNSUPPORTED;             // bf16 x 6: the per-step kernels below do not read triple images
     for (int s = 0; s < n_scans; ++s)          // initial states -> fragment-major (slot 0 of the ping-pong scratch)
         if (scans[s].h0 && !scans[s].h0_frag) {
             const int rc = launch_pack(scans[s].h0, scans[s].B, scans[s].H, scans[s].H, scans[s].frag_ws, st);
             if (rc != FN_OK) return rc;
         }
-    for (int p = 0; p < Tmax; ++p) {
-        // row-tile height: 64 rows when the launch already fills the chip, 32 otherwise (more workgroups)
-        long big_tiles = 0;
-        for (int s = 0; s < n_scans; ++s)
-            if (p < scans[s].T) big_tiles += (long)((scans[s].B + 63) / 64) * (scans[s].H / 16);
-        Cfg cfg = big_tiles >= 256 ? Cfg{4, 0, 1} : Cfg{2, 0, 3};
+    for (int p = 0; p < step.launches; ++p) {
+        const StepCfg cfg = gru_fwd_step_cfg(scans, n_scans, p);
         const int bm = 16 * cfg.tm;
         FwdArgs a;
         a.n = 0;
@@ -1812,45 +1781,34 @@ int fn_gru_seq_fwd(const FnGruFwd* scans, int n_scans, void* stream) {
             tiles += f.ntm * (d.H / 16);
         }
         a.total = tiles;
-        if (!launch_fwd(cfg, a, tiles, st)) return FN_E_SHAPE;
+        if (tiles != cfg.tiles || !launch_fwd(cfg, a, st)) return FN_E_SHAPE;
         FN_CHECK_LAUNCH();
     }
     return FN_OK;
 }
 
 int fn_gru_seq_bwd(const FnGruBwd* scans, int n_scans, void* stream) {
-    if (!scans) return FN_E_NULL;
-    if (n_scans <= 0 || n_scans > FN_MAX_SCANS) return FN_E_COUNT;
-    int Tmax = 0;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruBwd& d = scans[s];
-        if (!d.w_hh_t_frag || !d.h_all || !d.gates || !d.dgx_all || !d.dghn_all || !d.scratch || !d.frag_ws) return FN_E_NULL;
-        if (d.B <= 0 || d.T <= 0 || d.H <= 0 || (d.H % 32) != 0) return FN_E_SHAPE;
-        if ((((uintptr_t)d.w_hh_t_frag) | ((uintptr_t)d.frag_ws)) & 15) return FN_E_ALIGN;
-        Tmax = d.T > Tmax ? d.T : Tmax;
-    }
+    const FnGruPlan plan = gru_bwd_plan(scans, n_scans, fn_cu_count());
+    if (plan.status != FN_OK) return plan.status;
     hipStream_t st = (hipStream_t)stream;
-    {
-        const int rc = fn_gru_bwd_persist(scans, n_scans, st);
-        if (rc != FN_PERSIST_NA) return rc;
-        if (scans[0].variant & FN_GRU_BF16X6) return FN_E_UNSUPPORTED;      // the per-step kernels below do not read triple images
+    for (int i = 0; i < plan.n && plan.cand[i].resident; ++i) {
+        int fits = 0;
+        const int rc = fn_gru_bwd_ws(plan.cand[i], scans, n_scans, plan.cus, true, st, &fits);
+        if (rc != FN_OK || fits) return rc;
     }
+    if (plan.cand[plan.n - 1].resident) return FN_E_UNSUPPORTED;      // bf16 x 6: the per-step kernels below do not read triple images
+    int Tmax = 0;
+    for (int s = 0; s < n_scans; ++s) Tmax = scans[s].T > Tmax ? scans[s].T : Tmax;
     for (int it = 0; it <= Tmax; ++it) {
-        long big_tiles = 0;
-        for (int s = 0; s < n_scans; ++s) {
-            const FnGruBwd& d = scans[s];
-            if (it > d.T || (it == d.T && !d.dh0)) continue;
-            big_tiles += (long)((d.B + 63) / 64) * ((d.H + 31) / 32);
-        }
-        if (big_tiles == 0) continue;
-        Cfg cfg = big_tiles >= 192 ? Cfg{4, 1, 2} : Cfg{2, 1, 3};
+        const StepCfg cfg = gru_bwd_step_cfg(scans, n_scans, it);
+        if (!cfg.active) continue;
         const int bm = 16 * cfg.tm, bn = 16 * cfg.tn;
         BwdArgs a;
         a.n = 0;
         int tiles = 0;
         for (int s = 0; s < n_scans; ++s) {
             const FnGruBwd& d = scans[s];
-            if (it > d.T || (it == d.T && !d.dh0)) continue;
+            if (!gru_bwd_step_active(d, it)) continue;
             BwdStep& f = a.s[a.n++];
             const long BH = (long)d.B * d.H;
             const long GS = (long)fn_gru_gates_floats(d.B, d.H);
@@ -1884,7 +1842,7 @@ int fn_gru_seq_bwd(const FnGruBwd* scans, int n_scans, void* stream) {
             tiles += f.ntm * ((d.H + bn - 1) / bn);
         }
         a.total = tiles;
-        if (!launch_bwd(cfg, a, tiles, st)) return FN_E_SHAPE;
+        if (tiles != cfg.tiles || !launch_bwd(cfg, a, st)) return FN_E_SHAPE;
         FN_CHECK_LAUNCH();
     }
     return FN_OK;

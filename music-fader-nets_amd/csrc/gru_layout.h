@@ -1,6 +1,7 @@
 // gru_layout.h - private memory layouts shared by the per-step (gru.hip) and persistent (gru_persist.hip) GRU kernels.
 #pragma once
 #include "common.h"
+#include "gru_plan.h"
 #include "mma_core.h"
 
 // offset of (batch row b, gate q in {r,z,n,hn}, hidden unit u) inside one step's gate slab; nrt = ceil(B/16).
@@ -44,7 +45,6 @@ FN_DEVINL void fn_gru_gate_bwd(float dh, float r, float z, float n, float hn, fl
 // recipe R1 of cdna_hip_programming.md G16: 16-byte write-through (sc1) payload stores and L1-bypassing (sc1) loads; counters are
 // relaxed agent-scope atomics.  The asm loads are not counted by hipcc: pair them with fn_wait_vm<N>() / fn_keep() (mma_core.h).
 typedef unsigned int u32;
-constexpr int RT = 256 + 16;                        // floats of one 16x16 accumulator tile in LDS: MFMA C layout + 4 floats per 16 lanes
 constexpr u32 SPIN_LIMIT = 1u << 21;                // polls before a waiting workgroup gives up (~2 s)
 FN_DEVINL void gld4_sc1(f32x4& dst, const float* p) { asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(dst) : "v"(p) : "memory"); }
 // the trailing s_nop keeps hipcc from reusing the data registers before the store has read them
@@ -54,10 +54,10 @@ FN_DEVINL void stv4(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v
 // orders every later use of v behind the preceding (volatile) wait: the value of an asm load must not be looked at before it
 FN_DEVINL void fn_touch(f32x4& v) { asm volatile("" : "+v"(v)); }
 FN_DEVINL u32 ld_cnt(u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// host-side entry points of gru_persist.hip: return FN_OK when the persistent kernel was launched,
-// FN_PERSIST_NA when the configuration is not eligible (the caller then uses the per-step kernels).
-#define FN_PERSIST_NA 1000000
-int fn_gru_fwd_persist(const FnGruFwd* scans, int n_scans, hipStream_t st);
-int fn_gru_bwd_persist(const FnGruBwd* scans, int n_scans, hipStream_t st);
+// host-side entry points of gru_persist.hip for a resident candidate c of a scan plan (gru_plan.h): *fits = do all its workgroups fit `cus` compute
+// units at once (the occupancy query, cached per instance and device); with `launch`, a candidate that fits is enqueued: packing launches of the
+// initial states, the counter memset, the kernel.  FN_OK or an error of the runtime.
+int fn_gru_fwd_ws(const FnGruCandidate& c, const FnGruFwd* scans, int n_scans, int cus, bool launch, hipStream_t st, int* fits);
+int fn_gru_bwd_ws(const FnGruCandidate& c, const FnGruBwd* scans, int n_scans, int cus, bool launch, hipStream_t st, int* fits);
 int launch_pack(const float* src, int rows, int K, long ld, float* dst, hipStream_t st);
 extern "C" int fn_frag3_pack(const float* src, int rows, int K, int ld, void* dst, void* stream);

@@ -81,7 +81,6 @@ struct PArgs {
     u32* sync;            // [ngroups * 32] arrival counters (one per 128-byte line), zero at launch
     u32* err;             // sticky error word
 };
-constexpr int FN_MAX_GROUPS = 64;
 
 // Which (row group, slice) a workgroup is.  Default: group = id mod groups - with 8 (or 16) groups every row group sits on ONE XCD (workgroups are
 // dealt to the XCDs round robin by id), its exchange slab then lives in that XCD's L2.  That is speed only: the hand-over protocol is agent-scope
@@ -1950,20 +1949,21 @@ __global__ __launch_bounds__(NT) void gru_bwd_x6_kernel(const QArgs args) {
 
 // The weight-stationary kernels spin on counters that OTHER workgroups of the same launch advance: every workgroup of the grid
 // must be resident at the same time.  This is what a cooperative launch would assert; here the occupancy calculator is asked how
-// many workgroups of this kernel (with its dynamic LDS) fit one CU, and a grid beyond cus x that is refused (FN_PERSIST_NA -> the
-// caller takes the per-step kernels).  Kernels of OTHER streams can still delay residency; that case is covered by the bounded
-// spins (sticky error word), never by a hang.
+// many workgroups of this kernel (with its dynamic LDS) fit one CU, and a grid beyond cus x that does not fit (*fits = 0: the caller
+// goes on to the plan's next candidate).  Kernels of OTHER streams can still delay residency; that case is covered by the bounded
+// spins (sticky error word), never by a hang.  a == nullptr: only the question; else a grid that fits is launched.
 template <class Args, void (*K)(const Args)>
-int launch_k(const Args& a, int grid, size_t lds, int cus, hipStream_t st) {
+int launch_k(const Args* a, int grid, size_t lds, int cus, hipStream_t st, int* fits) {
     auto k = K;
     // per kernel instance and device: (blocks per CU << 32 | LDS bytes asked for), packed into ONE atomic word so that a reader never
     // pairs the answer for one LDS size with another; recomputed (idempotently) when the LDS size differs
     static std::atomic<unsigned long long> cache[FN_MAX_DEVICES];
     const int dev = fn_device();
-    if (dev < 0) return FN_PERSIST_NA;
+    *fits = 0;
+    if (dev < 0) return FN_OK;
     unsigned long long w = cache[dev].load(std::memory_order_acquire);
     if (w == 0 || (size_t)(w & 0xffffffffull) != lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, GRU_WS_MAX_LDS);
         if (e != hipSuccess) return (int)e;
         int nb = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), NT, lds);
@@ -1972,77 +1972,37 @@ int launch_k(const Args& a, int grid, size_t lds, int cus, hipStream_t st) {
         cache[dev].store(w, std::memory_order_release);
     }
     const long blocks_per_cu = (w >> 32) == 0x7fffffffull ? -1 : (long)(w >> 32);
-    if (blocks_per_cu < 0 || (long)grid > (long)cus * blocks_per_cu) return FN_PERSIST_NA;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
+    *fits = blocks_per_cu >= 0 && (long)grid <= (long)cus * blocks_per_cu;
+    if (!a || !*fits) return FN_OK;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, *a);
     FN_CHECK_LAUNCH();
     return FN_OK;
 }
 
-// compute units the launch of these scans may occupy: the device's, or scans[0].cu_budget when that is smaller
-template <class Scan>
-int budget_cus(const Scan* scans) {
-    const int cus = fn_cu_count();
-    return scans[0].cu_budget > 0 && scans[0].cu_budget < cus ? scans[0].cu_budget : cus;
-}
-
-// bf16 x 6 forward scans: row tiles per wave (1 = 64-row groups, 2 = 128-row groups) of the launch, 0 = not eligible.  H = 512, every scan in
-// full row groups, saved gates, T >= 2, all row groups resident at once.
-int x6_row_tiles(const FnGruFwd* scans, int n_scans, int maxgroups) {
-    if (scans[0].H != 512) return 0;
-    long g64 = 0, g128 = 0;
-    bool d64 = true, d128 = true;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruFwd& d = scans[s];
-        if (d.H != 512 || !d.gates || d.T < 2) return 0;
-        d64 = d64 && d.B % 64 == 0; d128 = d128 && d.B % 128 == 0;
-        g64 += d.B / 64; g128 += d.B / 128;
+// FnGruKernel -> instance, one switch per direction
+#define FN_K(E_, ...) case E_: return launch_k<std::remove_const_t<std::remove_pointer_t<decltype(a)>>, __VA_ARGS__>(a, c.grid, (size_t)c.lds_bytes, cus, st, fits);
+int fwd_instance(const FnGruCandidate& c, const PArgs* a, int cus, hipStream_t st, int* fits) {
+    switch (c.kernel) {
+        FN_K(FN_GRU_FWD_X6PP_1, gru_fwd_x6pp_kernel<1>) FN_K(FN_GRU_FWD_X6PP_2, gru_fwd_x6pp_kernel<2>)
+        FN_K(FN_GRU_FWD_X6_1, gru_fwd_x6_kernel<1>) FN_K(FN_GRU_FWD_X6_2, gru_fwd_x6_kernel<2>)
+        FN_K(FN_GRU_FWD_PP_1, gru_fwd_pp_kernel<1>) FN_K(FN_GRU_FWD_PP_2, gru_fwd_pp_kernel<2>)
+        FN_K(FN_GRU_FWD_WS_4_1_2, gru_fwd_persist_kernel<4, 1, 2, 4>) FN_K(FN_GRU_FWD_WS_4_1_1, gru_fwd_persist_kernel<4, 1, 1, 4>)
+        FN_K(FN_GRU_FWD_WS_2_2_2, gru_fwd_persist_kernel<2, 2, 2, 4>) FN_K(FN_GRU_FWD_WS_2_2_1, gru_fwd_persist_kernel<2, 2, 1, 4>)
+        FN_K(FN_GRU_FWD_WS_1_4_1, gru_fwd_persist_kernel<1, 4, 1, 4>)
+        default: return FN_E_SHAPE;
     }
-    return (d64 && g64 <= maxgroups) ? 1 : ((d128 && g128 <= maxgroups) ? 2 : 0);
 }
-
-// The shapes of the register-stationary backward (gru_bwd_rs_kernel and its bf16 x 6 form gru_bwd_x6_kernel): row tiles per half (2 = 64-row groups,
-// 1 = 32-row groups), 0 = not eligible.  H = 512, every scan in full row groups, T >= 2, more than half of the chip and at most all of it (16 slices
-// x <= 16 groups, all resident).  half_chip_ok: exactly half of the chip too (g64 * 16 == cus: the caller asked for exactly this with a CU budget -
-// the half-chip launches of the decoder pipeline's backward, 8 groups on 128 CUs); rows32_ok: 32-row groups too.
-int bwd_rs_tiles(const FnGruBwd* scans, int n_scans, int cus, bool half_chip_ok, bool rows32_ok) {
-    if (scans[0].H != 512) return 0;
-    long g64 = 0, g32 = 0;
-    bool d64 = true, d32 = true;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruBwd& d = scans[s];
-        if (d.H != 512 || d.T < 2) return 0;
-        g64 += d.B / 64; g32 += d.B / 32;
-        d64 = d64 && d.B % 64 == 0;
-        d32 = d32 && d.B % 32 == 0;
+int bwd_instance(const FnGruCandidate& c, const QArgs* a, int cus, hipStream_t st, int* fits) {
+    switch (c.kernel) {
+        FN_K(FN_GRU_BWD_X6_1, gru_bwd_x6_kernel<1>) FN_K(FN_GRU_BWD_X6_2, gru_bwd_x6_kernel<2>)
+        FN_K(FN_GRU_BWD_RS_1, gru_bwd_rs_kernel<1>) FN_K(FN_GRU_BWD_RS_2, gru_bwd_rs_kernel<2>)
+        FN_K(FN_GRU_BWD_WS_4_1_2, gru_bwd_persist_kernel<4, 1, 2, 8>) FN_K(FN_GRU_BWD_WS_4_1_1, gru_bwd_persist_kernel<4, 1, 1, 8>)
+        FN_K(FN_GRU_BWD_WS_2_2_2, gru_bwd_persist_kernel<2, 2, 2, 8>) FN_K(FN_GRU_BWD_WS_2_2_1, gru_bwd_persist_kernel<2, 2, 1, 8>)
+        FN_K(FN_GRU_BWD_WS_1_4_1, gru_bwd_persist_kernel<1, 4, 1, 8>)
+        default: return FN_E_SHAPE;
     }
-    if (d64 && (g64 > 8 || (half_chip_ok && g64 * 16 == cus)) && g64 <= 16 && g64 * 16 <= cus) return 2;
-    return (rows32_ok && d32 && g32 > 8 && g32 <= 16 && g32 * 16 <= cus) ? 1 : 0;
 }
-
-// bf16 x 6 backward scans.  64-row groups (the encoder shape: 4 scans x 256 rows): 3.05 ms against 3.5 ms on the fp32 MFMA.  32-row groups (a
-// decoder-pipeline launch: 2 scans x 256 rows x 32 steps) measured SLOWER than the fp32 kernel (353 against 322-337 us: both are bound by the exchange
-// stream through the XCD's L2, which the triples make 1.5 x wider, and the 12-unit K loops are too short for the store -> arrival -> counter chain):
-// only on request (FN_GRU_X6_BWD_32ROWS)
-int x6_bwd_tiles(const FnGruBwd* scans, int n_scans, int cus) {
-    return bwd_rs_tiles(scans, n_scans, cus, true, (scans[0].variant & FN_GRU_X6_BWD_32ROWS) != 0);
-}
-
-// smallest row block of the 32-slice kernels whose group count fits on the chip with one workgroup per CU (FN_GRU_ROWS_MASK: that block or none);
-// 0 = none fits
-template <class Scan>
-int pick_rows(const Scan* scans, int n_scans, int maxgroups) {
-    const int force_rows = scans[0].variant & FN_GRU_ROWS_MASK;
-    for (const int rpw : {16, 32, 64, 128}) {
-        if (force_rows && force_rows != rpw) continue;
-        long groups = 0;
-        for (int s = 0; s < n_scans; ++s) groups += (scans[s].B + rpw - 1) / rpw;
-        if (groups <= maxgroups) return rpw;
-    }
-    return 0;
-}
-
-// K split of the 32-slice kernels' tiling for a row block
-int k_split(int rpw, int variant) { return rpw == 16 ? 4 : rpw == 32 ? 2 : (rpw == 64 && !(variant & FN_GRU_ALT_TILING)) ? 2 : 1; }
+#undef FN_K
 
 // The per-scan fields of a forward launch, its row groups of rows_per_group rows (the last one of a scan possibly partial) and sizes.  The initial
 // states that do not come as images (h0_frag) are packed into slab 0 of each scan's frag_ws (what step 0 reads), one launch per scan in scan order:
@@ -2107,143 +2067,26 @@ int begin_sync(Args& a, const Scan& s0, hipStream_t st) {
 
 extern "C" size_t fn_gru_sync_ws_bytes() { return ((size_t)FN_MAX_GROUPS * 32 + 32) * 4; }
 
-// would fn_gru_seq_fwd run this call with FN_GRU_BF16X6 (bf16 x 6)?  Shapes only: pointers are not looked at beyond NULL-ness of `gates`.
-extern "C" int fn_gru_fwd_x6_ok(const FnGruFwd* scans, int n_scans) {
-    if (!scans || n_scans < 1 || n_scans > FN_MAX_SCANS) return 0;
-    const int cus = budget_cus(scans);
-    if (cus < 32) return 0;
-    const int maxgroups = cus / 32 < FN_MAX_GROUPS ? cus / 32 : FN_MAX_GROUPS;
-    return x6_row_tiles(scans, n_scans, maxgroups) != 0;
-}
+// would fn_gru_seq_fwd / fn_gru_seq_bwd run this call with FN_GRU_BF16X6 (bf16 x 6)?  Shapes only (gru_plan.h)
+extern "C" int fn_gru_fwd_x6_ok(const FnGruFwd* scans, int n_scans) { return gru_fwd_x6_ok(scans, n_scans, fn_cu_count()); }
+extern "C" int fn_gru_bwd_x6_ok(const FnGruBwd* scans, int n_scans) { return gru_bwd_x6_ok(scans, n_scans, fn_cu_count()); }
 
-extern "C" int fn_gru_bwd_x6_ok(const FnGruBwd* scans, int n_scans) {
-    if (!scans || n_scans < 1 || n_scans > FN_MAX_SCANS) return 0;
-    return x6_bwd_tiles(scans, n_scans, budget_cus(scans)) != 0;
-}
-
-int fn_gru_fwd_persist(const FnGruFwd* scans, int n_scans, hipStream_t st) {
-    const int H = scans[0].H;
-    if (H > 512 || !scans[0].sync_ws) return FN_PERSIST_NA;
-    int Tmax = 0;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruFwd& d = scans[s];
-        if (d.H != H) return FN_PERSIST_NA;
-        if (d.h0_frag && !d.h0) return FN_E_NULL;              // the gate epilogue reads the row-major state
-        if ((((uintptr_t)d.h0_frag) | ((uintptr_t)d.h_last_frag)) & 15) return FN_E_ALIGN;
-        // the epilogue moves 16-byte vectors
-        const uintptr_t al = (uintptr_t)d.b_hh | (uintptr_t)d.b_ih | (uintptr_t)d.h0 | (uintptr_t)d.gx_dense | (uintptr_t)d.gx_table |
-                             (uintptr_t)d.gx_rowbias | (uintptr_t)d.h_all | (uintptr_t)d.gates;
-        if (al & 15) return FN_PERSIST_NA;
-        Tmax = d.T > Tmax ? d.T : Tmax;
-    }
-    if (Tmax < 2) return FN_PERSIST_NA;                 // nothing to keep stationary
-    const int cus = budget_cus(scans);
-    const int nslices = H / 16;
-    if (cus <= 0 || nslices > cus) return FN_PERSIST_NA;
-    const int maxgroups = cus / nslices < FN_MAX_GROUPS ? cus / nslices : FN_MAX_GROUPS;
-    const int variant = scans[0].variant;
+int fn_gru_fwd_ws(const FnGruCandidate& c, const FnGruFwd* scans, int n_scans, int cus, bool launch, hipStream_t st, int* fits) {
+    if (const int rc = fwd_instance(c, nullptr, cus, st, fits)) return rc;
+    if (!launch || !*fits) return FN_OK;
     PArgs a;
-    if (variant & FN_GRU_BF16X6) {
-        // exact split products on the bf16 MFMA (gru_fwd_x6_kernel).  The caller hands over w_hh_frag = fn_frag3_pack image and
-        // frag_ws of 3 * fn_frag_floats(B, H) floats.  Eligibility: x6_row_tiles() (the same predicate fn_gru_fwd_x6_ok answers with).
-        const int mt = x6_row_tiles(scans, n_scans, maxgroups);
-        if (!mt) return FN_E_UNSUPPORTED;
-        a.no_hand = 0;
-        int rc = fill_fwd_args(a, scans, n_scans, 64 * mt, true, st);
-        if (rc == FN_OK) rc = begin_sync(a, scans[0], st);
-        if (rc != FN_OK) return rc;
-        const int grid = a.ngroups * nslices;
-        const size_t lds = (size_t)3 * 16 * 3 * 1024 + (size_t)4 * 3 * RT * 4 + 16;
-        // ping-pong form (kloop3_asm.h): exactly one input source per scan; FN_GRU_X6_SINGLE_GROUP keeps the single-group kernel (tests)
-        bool pp = !(variant & FN_GRU_X6_SINGLE_GROUP) && 2 * a.ngroups <= FN_MAX_GROUPS;
-        for (int s = 0; s < n_scans && pp; ++s) pp = (scans[s].gx_table != nullptr) != (scans[s].gx_dense != nullptr);
-        if (pp) rc = mt == 1 ? launch_k<PArgs, gru_fwd_x6pp_kernel<2>>(a, grid, lds, cus, st)
-                             : launch_k<PArgs, gru_fwd_x6pp_kernel<1>>(a, grid, lds, cus, st);
-        else rc = mt == 1 ? launch_k<PArgs, gru_fwd_x6_kernel<1>>(a, grid, lds, cus, st)
-                          : launch_k<PArgs, gru_fwd_x6_kernel<2>>(a, grid, lds, cus, st);
-        return rc == FN_PERSIST_NA ? FN_E_UNSUPPORTED : rc;
-    }
-    const int rpw = pick_rows(scans, n_scans, maxgroups);
-    if (!rpw) return FN_PERSIST_NA;
-    a.no_hand = (variant & FN_GRU_COMPILER_LOOPS) ? 1 : 0;
-    if (const int rc = fill_fwd_args(a, scans, n_scans, rpw, false, st)) return rc;
+    a.no_hand = c.no_hand;
+    if (const int rc = fill_fwd_args(a, scans, n_scans, c.rows_per_group, c.h0_triples != 0, st)) return rc;
     if (const int rc = begin_sync(a, scans[0], st)) return rc;
-    const int grid = a.ngroups * nslices;
-    const int wk = k_split(rpw, variant);
-    const size_t lds = ((size_t)3 * H * 16 + (size_t)wk * (rpw / 16) * 3 * RT) * 4 + 16;
-    // ping-pong form (two halves per workgroup, kloop2_asm.h): H = 512, 128- or 64-row groups, full row groups, saved gates, one input source
-    bool pp = H == 512 && (rpw == 128 || (rpw == 64 && wk == 2)) && !(variant & (FN_GRU_COMPILER_LOOPS | FN_GRU_NO_PINGPONG)) &&
-              2 * a.ngroups <= FN_MAX_GROUPS;
-    for (int s = 0; s < n_scans && pp; ++s) {
-        const FnGruFwd& d = scans[s];
-        pp = d.B % rpw == 0 && d.gates && d.T >= 2 && ((d.gx_table != nullptr) != (d.gx_dense != nullptr));
-    }
-    if (pp) return rpw == 128 ? launch_k<PArgs, gru_fwd_pp_kernel<1>>(a, grid, lds, cus, st) : launch_k<PArgs, gru_fwd_pp_kernel<2>>(a, grid, lds, cus, st);
-    switch (rpw) {
-        case 128: return launch_k<PArgs, gru_fwd_persist_kernel<4, 1, 2, 4>>(a, grid, lds, cus, st);
-        case 64:
-            if (variant & FN_GRU_ALT_TILING) return launch_k<PArgs, gru_fwd_persist_kernel<4, 1, 1, 4>>(a, grid, lds, cus, st);
-            return launch_k<PArgs, gru_fwd_persist_kernel<2, 2, 2, 4>>(a, grid, lds, cus, st);
-        case 32: return launch_k<PArgs, gru_fwd_persist_kernel<2, 2, 1, 4>>(a, grid, lds, cus, st);
-        default: return launch_k<PArgs, gru_fwd_persist_kernel<1, 4, 1, 4>>(a, grid, lds, cus, st);
-    }
+    return fwd_instance(c, &a, cus, st, fits);
 }
 
-int fn_gru_bwd_persist(const FnGruBwd* scans, int n_scans, hipStream_t st) {
-    const int H = scans[0].H;
-    if (H > 512 || !scans[0].sync_ws) return FN_PERSIST_NA;
-    int Tmax = 0;
-    for (int s = 0; s < n_scans; ++s) {
-        const FnGruBwd& d = scans[s];
-        if (d.H != H) return FN_PERSIST_NA;
-        const uintptr_t al = (uintptr_t)d.h0 | (uintptr_t)d.h_all | (uintptr_t)d.gates | (uintptr_t)d.dh_last | (uintptr_t)d.dh_ext |
-                             (uintptr_t)d.dgx_all | (uintptr_t)d.dghn_all | (uintptr_t)d.dh0 | (uintptr_t)d.dgx_rowsum | (uintptr_t)d.dghn_rowsum;
-        if (al & 15) return FN_PERSIST_NA;
-        Tmax = d.T > Tmax ? d.T : Tmax;
-    }
-    if (Tmax < 2) return FN_PERSIST_NA;
-    const int cus = budget_cus(scans);
-    const int nslices = H / 16;
-    if (cus <= 0 || nslices > cus) return FN_PERSIST_NA;
-    const int variant = scans[0].variant;
+int fn_gru_bwd_ws(const FnGruCandidate& c, const FnGruBwd* scans, int n_scans, int cus, bool launch, hipStream_t st, int* fits) {
+    if (const int rc = bwd_instance(c, nullptr, cus, st, fits)) return rc;
+    if (!launch || !*fits) return FN_OK;
     QArgs a;
-    a.no_hand = 0;
-    if (variant & FN_GRU_BF16X6) {
-        // exact split products on the bf16 MFMA (gru_bwd_x6_kernel): w_hh_t_frag = the bf16 triple image of W_hh^T (fn_weight_images kind 4), frag_ws of
-        // 3 * fn_frag_floats(B, 3H) floats (the gate gradients are exchanged as triples).  Eligibility = fn_gru_bwd_x6_ok.
-        const int th = x6_bwd_tiles(scans, n_scans, cus);
-        if (!th) return FN_E_UNSUPPORTED;
-        fill_bwd_args(a, scans, n_scans, 32 * th);
-        if (const int rc = begin_sync(a, scans[0], st)) return rc;
-        const size_t lds = (size_t)4 * 11 * 3072 + (size_t)4 * (2 * th) * RT * 4 + 16;
-        const int rc = th == 2 ? launch_k<QArgs, gru_bwd_x6_kernel<2>>(a, a.ngroups * 16, lds, cus, st) : launch_k<QArgs, gru_bwd_x6_kernel<1>>(a, a.ngroups * 16, lds, cus, st);
-        return rc == FN_PERSIST_NA ? FN_E_UNSUPPORTED : rc;
-    }
-    // Register-stationary ping-pong form (gru_bwd_rs_kernel): 16 slices of 32 columns x up to 16 groups of 64 (or 32) rows, the shapes of
-    // bwd_rs_tiles (smaller problems keep the 32-slice kernels).  FN_GRU_COMPILER_LOOPS / _NO_PINGPONG / _NO_RS_BWD and a forced row block select the
-    // 32-slice loops.
-    const int th = (variant & (FN_GRU_COMPILER_LOOPS | FN_GRU_NO_PINGPONG | FN_GRU_NO_RS_BWD | FN_GRU_ROWS_MASK)) ? 0 : bwd_rs_tiles(scans, n_scans, cus, false, true);
-    if (th) {
-        fill_bwd_args(a, scans, n_scans, 32 * th);
-        if (const int rc = begin_sync(a, scans[0], st)) return rc;
-        const size_t lds = ((size_t)3 * H * 16 + (size_t)2 * 4 * (2 * th) * RT) * 4 + 16;
-        const int rc = th == 2 ? launch_k<QArgs, gru_bwd_rs_kernel<2>>(a, a.ngroups * 16, lds, cus, st) : launch_k<QArgs, gru_bwd_rs_kernel<1>>(a, a.ngroups * 16, lds, cus, st);
-        if (rc != FN_PERSIST_NA) return rc;
-    }
-    const int maxgroups = cus / nslices < FN_MAX_GROUPS ? cus / nslices : FN_MAX_GROUPS;
-    const int rpw = pick_rows(scans, n_scans, maxgroups);
-    if (!rpw) return FN_PERSIST_NA;
-    a.no_hand = (variant & FN_GRU_COMPILER_LOOPS) ? 1 : 0;
-    fill_bwd_args(a, scans, n_scans, rpw);
+    a.no_hand = c.no_hand;
+    fill_bwd_args(a, scans, n_scans, c.rows_per_group);
     if (const int rc = begin_sync(a, scans[0], st)) return rc;
-    const int grid = a.ngroups * nslices;
-    const size_t lds = ((size_t)3 * H * 16 + (size_t)2 * k_split(rpw, variant) * (rpw / 16) * RT) * 4 + 16;
-    switch (rpw) {
-        case 128: return launch_k<QArgs, gru_bwd_persist_kernel<4, 1, 2, 8>>(a, grid, lds, cus, st);
-        case 64:
-            if (variant & FN_GRU_ALT_TILING) return launch_k<QArgs, gru_bwd_persist_kernel<4, 1, 1, 8>>(a, grid, lds, cus, st);
-            return launch_k<QArgs, gru_bwd_persist_kernel<2, 2, 2, 8>>(a, grid, lds, cus, st);
-        case 32: return launch_k<QArgs, gru_bwd_persist_kernel<2, 2, 1, 8>>(a, grid, lds, cus, st);
-        default: return launch_k<QArgs, gru_bwd_persist_kernel<1, 4, 1, 8>>(a, grid, lds, cus, st);
-    }
+    return bwd_instance(c, &a, cus, st, fits);
 }

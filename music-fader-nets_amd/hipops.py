@@ -318,6 +318,20 @@ class HipOps:
     def gru_seq_fwd(self, scans, persistent=True, cu_budget=0, variant=None, x6=None):
         """x6: None = this launch decides for itself (bf16 x 6 where eligible, refused when it is part of a hand-over chain: h0_frag /
         h_last_frag images depend on the arithmetic), True / False = the decision the caller made for the whole chain"""
+        arr, x6 = self._fwd_args(scans, persistent, cu_budget, variant, x6)
+        _lib.check(self.lib.fn_gru_seq_fwd(arr, len(scans), self.stream()), "fn_gru_seq_fwd (bf16 x 6)" if x6 else "fn_gru_seq_fwd")
+
+    def gru_fwd_plan(self, scans, persistent=True, cu_budget=0, variant=None, x6=None):
+        """what gru_seq_fwd() with these arguments launches, as the library decides it on the current device (fn_gru_fwd_plan on the same prepared
+        descriptors: workspaces, counter region, variant bits and the bf16 x 6 decision): dict(status, chosen, cus, ws_absent, candidates = [dict(kernel,
+        rows_per_group, groups, grid, lds_bytes, fits, ..), ..] in the order they are tried).  Nothing is enqueued."""
+        arr, _ = self._fwd_args(scans, persistent, cu_budget, variant, x6)
+        plan = _lib.FnGruPlan()
+        _lib.check(self.lib.fn_gru_fwd_plan(arr, len(scans), 0, C.byref(plan)), "fn_gru_fwd_plan")
+        return plan.as_dict()
+
+    def _fwd_args(self, scans, persistent, cu_budget, variant, x6):
+        """the descriptors of fn_gru_seq_fwd / fn_gru_fwd_plan for one launch and its arithmetic: (FnGruFwd array, x6)"""
         arr = self._fwd_descriptors(scans, cu_budget)
         variant = self.variant if variant is None else variant
         sync = self._sync_region() if persistent else None
@@ -337,7 +351,7 @@ class HipOps:
             d.sync_ws, d.err_ws, d.variant = (_p(sync[0]), _p(sync[1]), int(variant) | sync[2]) if persistent else (None, None, int(variant))
             if x6:
                 d.w_hh_frag, d.variant = _p(s["w_hh_frag3"]), d.variant | _lib.GRU_BF16X6
-        _lib.check(self.lib.fn_gru_seq_fwd(arr, len(scans), self.stream()), "fn_gru_seq_fwd (bf16 x 6)" if x6 else "fn_gru_seq_fwd")
+        return arr, x6
 
     def frag3_pack(self, src, dst):
         """bf16 triple image of src [rows][K] (fn_frag3_pack); dst: 3/2 * frag_floats(rows, K) floats"""
@@ -353,6 +367,21 @@ class HipOps:
         torch matrix w_ih [3H][K1], optional token rows gx_table [V][3H] picked by idx (a [B] int32 column view, e.g. tokens[:, i - 1];
         None = start_token; or idx_best: the [B] int64 packed argmax words out_argmax left for the previous token, packed with best_v
         columns) and per-row constants gx_rowbias [B][3H]; w_hh [3H][H] is the torch matrix itself"""
+        c = self._cell_args(h_prev, w_hh, b_hh, h_out, x, w_ih, b_ih, gx_table, idx, start_token, gx_rowbias, variant, idx_best, best_v)
+        _lib.check(self.lib.fn_gru_cell_f32(C.byref(c), self.stream()), "fn_gru_cell_f32")
+
+    def gru_cell_plan(self, h_prev, w_hh, b_hh, h_out, x=None, w_ih=None, b_ih=None, gx_table=None, idx=None, start_token=0, gx_rowbias=None, variant=None,
+                      idx_best=None, best_v=0):
+        """what gru_cell() with these arguments launches (fn_gru_cell_plan on the same prepared descriptor): dict(family, template, has_tab, has_rb, kmax,
+        grid, threads, lds_bytes, forced_honoured).  Nothing is enqueued."""
+        c = self._cell_args(h_prev, w_hh, b_hh, h_out, x, w_ih, b_ih, gx_table, idx, start_token, gx_rowbias, variant, idx_best, best_v)
+        plan = _lib.FnGruCellPlan()
+        _lib.check(self.lib.fn_gru_cell_plan(C.byref(c), C.byref(plan)), "fn_gru_cell_plan")
+        _lib.check(plan.status, "fn_gru_cell_plan")
+        return plan.as_dict()
+
+    def _cell_args(self, h_prev, w_hh, b_hh, h_out, x, w_ih, b_ih, gx_table, idx, start_token, gx_rowbias, variant, idx_best, best_v):
+        """the descriptor of fn_gru_cell_f32 / fn_gru_cell_plan"""
         c = _lib.FnGruCell()
         ph, B, H, ldh = _mat(h_prev, "h_prev")
         pw, r3, Hw, ldw = _mat(w_hh, "w_hh")
@@ -383,7 +412,7 @@ class HipOps:
             if idx_best.dtype != torch.int64 or idx_best.dim() != 1 or idx_best.shape[0] != B or not idx_best.is_contiguous():
                 raise RuntimeError("gru_cell: idx_best must be a contiguous [B] int64 row")
             c.idx_best, c.best_v = idx_best.data_ptr(), int(best_v)
-        _lib.check(self.lib.fn_gru_cell_f32(C.byref(c), self.stream()), "fn_gru_cell_f32")
+        return c
 
     def out_argmax(self, h, W, bias, best):
         """fn_out_argmax_f32: best[b] = max(best[b], packed (logit, column) words of h[b] W^T + bias) - best: a ZEROED contiguous [B] int64 row"""
@@ -427,6 +456,34 @@ class HipOps:
     def gru_seq_bwd(self, scans, persistent=True, cu_budget=0, variant=None, x6=None):
         """x6: None = bf16 x 6 where the launch is eligible (a backward launch hands nothing but fp32 tensors to the next one: every launch decides for
         itself), True / False = forced"""
+        arr, x6, auto = self._bwd_args(scans, persistent, cu_budget, variant, x6)
+        rc = self.lib.fn_gru_seq_bwd(arr, len(scans), self.stream())
+        if rc == _lib.FN_E_UNSUPPORTED and x6 and auto:
+            # the shape predicate said yes, a launch-time check (alignment, occupancy) said no: nothing was launched, and a backward launch hands only
+            # fp32 tensors on - the fp32 kernels take it (a FORCED x6=True still raises)
+            x6 = self._bwd_fp32(arr, scans)
+            rc = self.lib.fn_gru_seq_bwd(arr, len(scans), self.stream())
+        _lib.check(rc, "fn_gru_seq_bwd (bf16 x 6)" if x6 else "fn_gru_seq_bwd")
+
+    def gru_bwd_plan(self, scans, persistent=True, cu_budget=0, variant=None, x6=None):
+        """what gru_seq_bwd() with these arguments launches (fn_gru_bwd_plan on the same prepared descriptors, the repeat on the fp32 kernels
+        included), as gru_fwd_plan.  Nothing is enqueued."""
+        arr, x6, auto = self._bwd_args(scans, persistent, cu_budget, variant, x6)
+        plan = _lib.FnGruPlan()
+        _lib.check(self.lib.fn_gru_bwd_plan(arr, len(scans), 0, C.byref(plan)), "fn_gru_bwd_plan")
+        if plan.status == _lib.FN_E_UNSUPPORTED and x6 and auto:
+            self._bwd_fp32(arr, scans)
+            _lib.check(self.lib.fn_gru_bwd_plan(arr, len(scans), 0, C.byref(plan)), "fn_gru_bwd_plan")
+        return plan.as_dict()
+
+    def _bwd_fp32(self, arr, scans):
+        """bf16 x 6 descriptors -> the fp32 kernels' (the weight image and the bit); returns the new x6 = False"""
+        for d, s in zip(arr, scans):
+            d.w_hh_t_frag, d.variant = _p(s["w_hh_t_frag"]), d.variant & ~_lib.GRU_BF16X6
+        return False
+
+    def _bwd_args(self, scans, persistent, cu_budget, variant, x6):
+        """the descriptors of fn_gru_seq_bwd / fn_gru_bwd_plan for one launch: (FnGruBwd array, x6, was x6 this launch's own decision)"""
         arr = self._bwd_descriptors(scans, cu_budget)
         variant = self.variant if variant is None else variant
         sync = self._sync_region() if persistent else None
@@ -438,15 +495,7 @@ class HipOps:
             d.sync_ws, d.err_ws, d.variant = (_p(sync[0]), _p(sync[1]), int(variant) | sync[2]) if persistent else (None, None, int(variant))
             if x6:
                 d.w_hh_t_frag, d.variant = _p(s["w_hh_t_frag3"]), d.variant | _lib.GRU_BF16X6
-        rc = self.lib.fn_gru_seq_bwd(arr, len(scans), self.stream())
-        if rc == _lib.FN_E_UNSUPPORTED and x6 and auto:
-            # the shape predicate said yes, a launch-time check (alignment, occupancy) said no: nothing was launched, and a backward launch hands only
-            # fp32 tensors on - the fp32 kernels take it (a FORCED x6=True still raises)
-            for d, s in zip(arr, scans):
-                d.w_hh_t_frag, d.variant = _p(s["w_hh_t_frag"]), d.variant & ~_lib.GRU_BF16X6
-            x6 = False
-            rc = self.lib.fn_gru_seq_bwd(arr, len(scans), self.stream())
-        _lib.check(rc, "fn_gru_seq_bwd (bf16 x 6)" if x6 else "fn_gru_seq_bwd")
+        return arr, x6, auto
 
     def gru_dwhh(self, dgx, dghn, hprev, dW, beta=0.0, splitk=1, lean=False):
         """dW [3H][H] = beta*dW + [dgx[:, :2H] | dghn]^T hprev  (dgx [rows][3H], dghn / hprev [rows][H])."""

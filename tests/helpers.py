@@ -887,13 +887,14 @@ def _unblock_gates(g, B, H, rows=None):
     return g[:, off.reshape(-1).to(g.device)].view(T, b.shape[0], 4, H)
 
 
-def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=None, bwd_kw=None, carry_fault=None):
+def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=None, bwd_kw=None, carry_fault=None, h_all_off=0):
     """The logical scans through a backend: ops = FakeOps (device "cpu", restricted to rows[i] of scan i) or HipOps (all rows on `device`; the
     outputs are cut to rows[i] afterwards).  chunk = None: one forward and one backward launch.  chunk = CH: time chunks of CH steps, the forward
     state handed from launch to launch as operand images (h_last_frag -> h0_frag), the backward state gradient through dh0 -> dh_last with time
     running backwards over the chunks - what the decoder pipeline does (engine.py, _bwd_chunk).  x6: the arithmetic asked for, explicitly
     (HipOps: dw_x6 and x6= of both calls; a launch that cannot take it raises).  carry_fault(ci, tensor): test hook, edits the CPU carry that
-    leaves backward chunk ci (FakeOps only).  The backward consumes the backend's OWN saved gates.  Returns per scan {quantity: CPU tensor}."""
+    leaves backward chunk ci (FakeOps only).  h_all_off: h_all is a view that many floats behind the start of its allocation (1: 4 bytes off a
+    16-byte boundary).  The backward consumes the backend's OWN saved gates.  Returns per scan {quantity: CPU tensor}."""
     fake = device == "cpu"
     fwd_kw, bwd_kw = dict(fwd_kw or {}), dict(bwd_kw or {})
     if not fake:
@@ -907,7 +908,7 @@ def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=
         B, T, H = (len(rw) if fake else s["B"]), s["T"], s["H"]
         sub.append((B, T, H))
         d = dict(B=B, T=T, H=H, reverse=int(s.get("reverse", 0)), b_hh=dev(s["b_hh"]), idx_shift=int(s.get("idx_shift", 0)), start_token=int(s.get("start_token", 0)),
-                 h_all=zeros(T, B, H), gates=zeros(T, ops.gates_floats(B, H)))
+                 h_all=zeros(T * B * H + h_all_off)[h_all_off:].view(T, B, H), gates=zeros(T, ops.gates_floats(B, H)))
         w = dev(s["w_hh"])
         d["w_hh_frag"] = zeros(ops.frag_floats(3 * H, H))
         b = dict(B=B, T=T, H=H, w_hh_t_frag=zeros(ops.frag_floats(H, 3 * H)))
@@ -1081,6 +1082,32 @@ def check_scan_vs_f64(scans, got, rows, chunk=None, key=None, F=None, ref_device
     return worst
 
 
+class PlanRecorder:
+    """HipOps with every gru_seq_fwd / gru_seq_bwd preceded by the library's own plan for the same arguments (ops.gru_fwd_plan / gru_bwd_plan on the
+    real descriptors, current device): .fwd / .bwd collect the plans, one per launch"""
+
+    def __init__(self, ops):
+        self.ops, self.fwd, self.bwd = ops, [], []
+
+    def __getattr__(self, name):
+        return getattr(self.ops, name)
+
+    def gru_seq_fwd(self, scans, **kw):
+        self.fwd.append(self.ops.gru_fwd_plan(scans, **kw))
+        self.ops.gru_seq_fwd(scans, **kw)
+
+    def gru_seq_bwd(self, scans, **kw):
+        self.bwd.append(self.ops.gru_bwd_plan(scans, **kw))
+        self.ops.gru_seq_bwd(scans, **kw)
+
+
+def chosen_kernels(plans):
+    """the kernel every recorded plan says its launch takes"""
+    for p in plans:
+        assert p["status"] == 0 and p["chosen"] is not None and p["candidates"][p["chosen"]]["fits"] is not False, p
+    return [p["candidates"][p["chosen"]]["kernel"] for p in plans]
+
+
 def scan_lines(case, kernels, worst):
     """the lines of profiles/scan_fp64_errors.txt for one case: per quantity the worst ratio over the scans and where it occurred"""
     out = []
@@ -1128,7 +1155,7 @@ def _ws_scans(gen, B, H, T=70, n=2):
 
 
 # name -> (seed, builder(gen) -> logical scans, chunk).  The shapes are the production launches of engine.py and the edges of the dispatch in
-# csrc/gru_persist.hip; tests/test_scan_reference.py runs every one of them on the CPU, tests/test_gpu_parity.py on the kernels.
+# csrc/gru_plan.h; tests/test_scan_reference.py runs every one of them on the CPU, tests/test_gpu_parity.py on the kernels.
 SCAN_INPUTS = {
     # encoder: 4 scans x 256 rows x 256 steps, token tables, two reverse, gradient from the last state only.  dh_last x 2**40 (exact in fp32): with
     # w_hh = randn / sqrt(H) the gate gradients shrink by ~2**-0.47 per step, 2**-120 over the launch - the scale keeps every step's maximum
@@ -1168,15 +1195,18 @@ def scan_inputs(name):
 _V_ROWS, _V_ALT, _V_LOOPS, _V_NOPP, _V_NORS, _V_X6ALT = 0xFF, 0x100, 0x400, 0x800, 0x2000, 0x8000
 
 
-def scan_kernel_names(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persistent=True, T=None, cus=256):
-    """(forward, backward) kernel instance a launch of these scans takes: the dispatch of fn_gru_fwd_persist / fn_gru_bwd_persist
-    (csrc/gru_persist.hip) restated on shapes, for the labels of profiles/scan_fp64_errors.txt and so that a case can assert that its shape
-    reaches the kernel it is meant for.  (What it cannot know: a launch the occupancy check refuses falls back to the per-step kernels
-    silently unless bf16 x 6 was forced.)  T: the steps per launch of a chunked chain; variants, cu_budget: (forward, backward)."""
+def scan_kernel_candidates(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persistent=True, T=None, cus=256, aligned=(True, True)):
+    """(forward, backward) kernel instances a launch of these scans can take, in the order the launch tries them: the dispatch of csrc/gru_plan.h
+    restated on shapes, independently of it (tests/test_scan_reference.py compares the two).  The launch takes the first candidate whose workgroups
+    are all resident at once - which only the device can say, so where that can change the outcome the whole list is given; the per-step kernel needs
+    no residency and is last.  A bf16 x 6 launch has one candidate, or none (the call is refused).  T: the steps per launch of a chunked chain;
+    variants, cu_budget: (forward, backward); aligned: are the operands of the 16-byte epilogue vectors 16-byte aligned (else: per step);
+    a scan with gates=False saves no gates."""
     H = scans[0]["H"]
     Bs = [s["B"] for s in scans]
     Ts = [s["T"] if T is None else T for s in scans]
     one_src = all((s.get("gx_table") is not None) != (s.get("gx_dense") is not None) for s in scans)
+    gates = all(s.get("gates", True) for s in scans)
     ceil = lambda a, b: (a + b - 1) // b
     names = []
     for back in (False, True):
@@ -1185,9 +1215,8 @@ def scan_kernel_names(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persis
         budget = cu_budget[back]
         c = budget if 0 < budget < cus else cus
         nsl = H // 16
-        if not persistent or H > 512 or max(Ts) < 2 or nsl > c:
-            assert not x6
-            names.append(step)
+        if not persistent or H > 512 or any(s["H"] != H for s in scans) or not aligned[back] or max(Ts) < 2 or nsl > c:
+            names.append([] if x6 else [step])
             continue
         maxgroups = min(c // nsl, 64)
 
@@ -1200,21 +1229,20 @@ def scan_kernel_names(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persis
         full = lambda r: all(B % r == 0 for B in Bs)
         if not back:
             if x6:
-                ok = H == 512 and min(Ts) >= 2
+                ok = H == 512 and min(Ts) >= 2 and gates
                 mt = 1 if ok and full(64) and sum(Bs) // 64 <= min(c // 32, 64) else 2 if ok and full(128) and sum(Bs) // 128 <= min(c // 32, 64) else 0
-                assert mt, "not eligible for the bf16 x 6 forward"
-                pp = not variant & _V_X6ALT and 2 * sum(Bs) // (64 * mt) <= 64 and one_src
-                names.append("gru_fwd_x6pp_kernel<%d>" % (3 - mt) if pp else "gru_fwd_x6_kernel<%d>" % mt)
+                pp = not variant & _V_X6ALT and mt and 2 * sum(Bs) // (64 * mt) <= 64 and one_src
+                names.append([] if not mt else ["gru_fwd_x6pp_kernel<%d>" % (3 - mt) if pp else "gru_fwd_x6_kernel<%d>" % mt])
                 continue
             rpw = pick_rows()
             if not rpw:
-                names.append(step)
+                names.append([step])
                 continue
             wk = ksplit(rpw)
             pp = H == 512 and (rpw == 128 or (rpw == 64 and wk == 2)) and not variant & (_V_LOOPS | _V_NOPP) and 2 * sum(ceil(B, rpw) for B in Bs) <= 64 \
-                and full(rpw) and min(Ts) >= 2 and one_src
+                and full(rpw) and min(Ts) >= 2 and one_src and gates
             tiling = {128: "4, 1, 2", 64: "4, 1, 1" if variant & _V_ALT else "2, 2, 2", 32: "2, 2, 1", 16: "1, 4, 1"}[rpw]
-            names.append("gru_fwd_pp_kernel<%d>" % (1 if rpw == 128 else 2) if pp else "gru_fwd_persist_kernel<%s, 4>" % tiling)
+            names.append(["gru_fwd_pp_kernel<%d>" % (1 if rpw == 128 else 2) if pp else "gru_fwd_persist_kernel<%s, 4>" % tiling, step])
             continue
 
         def rs_tiles(half_chip_ok, rows32_ok):
@@ -1226,21 +1254,64 @@ def scan_kernel_names(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persis
             return 1 if rows32_ok and full(32) and g32 > 8 and g32 <= 16 and g32 * 16 <= c else 0
         if x6:
             th = rs_tiles(True, bool(variant & _V_X6ALT))
-            assert th, "not eligible for the bf16 x 6 backward"
-            names.append("gru_bwd_x6_kernel<%d>" % th)
+            names.append(["gru_bwd_x6_kernel<%d>" % th] if th else [])
             continue
         th = 0 if variant & (_V_LOOPS | _V_NOPP | _V_NORS | _V_ROWS) else rs_tiles(False, True)
-        if th:
-            names.append("gru_bwd_rs_kernel<%d>" % th)
-            continue
         rpw = pick_rows()
         tiling = {128: "4, 1, 2", 64: "4, 1, 1" if variant & _V_ALT else "2, 2, 2", 32: "2, 2, 1", 16: "1, 4, 1", 0: ""}[rpw]
-        names.append("gru_bwd_persist_kernel<%s, 8>" % tiling if rpw else step)
+        names.append((["gru_bwd_rs_kernel<%d>" % th] if th else []) + (["gru_bwd_persist_kernel<%s, 8>" % tiling] if rpw else []) + [step])
     return tuple(names)
 
 
+def scan_kernel_names(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persistent=True, T=None, cus=256, aligned=(True, True)):
+    """(forward, backward) kernel instance a launch of these scans takes when the device keeps every candidate resident: the first of
+    scan_kernel_candidates, for the labels of profiles/scan_fp64_errors.txt and so that a case can assert that its shape reaches the kernel it is
+    meant for (the GPU test asks the library which candidate the device took)."""
+    cands = scan_kernel_candidates(scans, variants, x6, cu_budget, persistent, T, cus, aligned)
+    assert all(cands), "not eligible for the bf16 x 6 %s" % ("backward" if cands[0] else "forward")
+    return tuple(c[0] for c in cands)
+
+
+def lib_scan_candidates(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), persistent=True, T=None, cus=256, aligned=(True, True)):
+    """what the library plans for the launch scan_kernel_candidates describes (fn_gru_fwd_plan / fn_gru_bwd_plan with the compute units given: pure
+    host functions, no device): (forward, backward) candidate names in order, [] for a refused bf16 x 6 call.  The descriptors carry made-up
+    addresses - the plan looks at NULL-ness and alignment only -: 16-byte aligned ones, h_all (forward) / dgx_all (backward) 4 bytes off when not
+    `aligned`."""
+    import ctypes
+    from mfn_import import load_package
+    load_package()
+    from music_fader_nets_amd import _lib
+    lib, n = _lib.load(), len(scans)
+    A, out = 0x10000, []
+    opt = lambda s, k: A if s.get(k) is not None else None
+    for back in (False, True):
+        arr = ((_lib.FnGruBwd if back else _lib.FnGruFwd) * n)()
+        for d, s in zip(arr, scans):
+            d.B, d.T, d.H = s["B"], s["T"] if T is None else T, s["H"]
+            d.frag_ws, d.h0, d.cu_budget = A, opt(s, "h0"), cu_budget[back]
+            d.sync_ws = A if persistent else None
+            d.variant = variants[back] | (_lib.GRU_BF16X6 if x6 else 0)
+            d.h_all = A if back or aligned[0] else A + 4
+            d.gates = A if back or s.get("gates", True) else None       # (saved gates are optional in the forward call only)
+            if back:
+                d.w_hh_t_frag = d.dghn_all = d.scratch = A
+                d.dgx_all = A if aligned[1] else A + 4
+                d.dh_last, d.dh_ext, d.dh0 = opt(s, "dh_last"), opt(s, "dh_ext"), A if s.get("want_dh0") else None
+            else:
+                d.w_hh_frag = d.b_hh = A
+                d.b_ih, d.gx_dense, d.gx_table, d.gx_rowbias = opt(s, "b_ih"), opt(s, "gx_dense"), opt(s, "gx_table"), opt(s, "gx_rowbias")
+                d.idx, d.idx_ld = A, 1
+        plan = _lib.FnGruPlan()
+        rc = (lib.fn_gru_bwd_plan if back else lib.fn_gru_fwd_plan)(arr, n, cus, ctypes.byref(plan))
+        assert rc == 0 and plan.status in (0, _lib.FN_E_UNSUPPORTED), (rc, plan.status)
+        p = plan.as_dict()
+        assert (plan.status == 0) == bool(p["candidates"]) and all(c["fits"] is None for c in p["candidates"] if c["resident"])
+        out.append([c["kernel"] for c in p["candidates"]])
+    return tuple(out)
+
+
 # The GPU cases of test_gpu_parity.test_scans_every_step_vs_fp64: (case id, inputs, both arithmetics?, launch keywords, kernels the case is for).
-# A case whose shape does not reach the kernels named here fails (scan_kernel_names).
+# A case whose shape does not reach the kernels named here fails (scan_kernel_names, and on the GPU the library's own plan).
 def _sc(cid, inputs, fwd, bwd, x6=False, variant=0, bvariant=None, budget=0, persistent=True):
     """variant: of the forward and (bvariant None) the backward launches; budget: cu_budget of the backward launches, as engine.py gives the decoder
     pipeline's backward half of the chip"""

@@ -16,7 +16,8 @@ import pytest
 import torch
 
 from fake_ops import FakeOps
-from helpers import (NOISE_PARAMS, REPLAY_CASES, REPLAY_GRAPH_PATHS, SCAN_CASES, _unblock_gates, batch_of, check_scan_vs_f64, grad_tolerances, load_golden,
+from helpers import (NOISE_PARAMS, REPLAY_CASES, REPLAY_GRAPH_PATHS, SCAN_CASES, PlanRecorder, _unblock_gates, _ws_scans, batch_of, check_scan_vs_f64, chosen_kernels,
+                     grad_tolerances, load_golden,
                      make_model, oracle_grads_f64, relerr, replay_decode_check, replay_inputs, replay_line, replay_z, run_scans, scan_inputs, scan_kernel_names,
                      scan_lines, sd_from)
 from mfn_import import load_package
@@ -145,9 +146,19 @@ def test_gru_cell_dense(ops, B, H, K1, mode, variant):
     ref = torch.zeros(B, H)
     FakeOps().gru_cell(hp, whh, bhh, ref, **kw)
     out = torch.zeros(B, H, device=DEV)
-    ops.gru_cell(g(hp), g(whh), g(bhh), out, **{k: (g(v) if torch.is_tensor(v) and k != "idx" else v) for k, v in kw.items() if k != "idx"},
-                 idx=(g(toks)[:, 3] if mode == "table" else None) if mode != "dense" else None, variant=variant)
+    args = (g(hp), g(whh), g(bhh), out)
+    dkw = dict({k: (g(v) if torch.is_tensor(v) and k != "idx" else v) for k, v in kw.items() if k != "idx"},
+               idx=(g(toks)[:, 3] if mode == "table" else None) if mode != "dense" else None, variant=variant)
+    ops.gru_cell(*args, **dkw)
     close(out, ref, 2e-5, "gru_cell")
+    # the library's plan for the same descriptor: a forced form is honoured exactly where the hand rule says so, and the family that ran
+    plan = ops.gru_cell_plan(*args, **dkw)
+    if variant:
+        assert plan["forced_honoured"] == (variant in (2, 8) or _cell_runs_forced_family(variant, H, K1)), plan
+        assert plan["family"] == _cell_forced_family(variant) if plan["forced_honoured"] else (plan["family"], plan["template"]) == ("staged", (64, 2, 2)), plan
+    else:               # automatic: the staged kernel up to 512 rows; above, at H = 512 and K1 in {0, 512}, the overlapped fill with ceil(B / 512) row tiles
+        assert not plan["forced_honoured"]
+        assert (plan["family"], plan["template"]) == (("staged", (64, 2, 2)) if B <= 512 else ("wlds-overlap", (-(-B // 512), 2, 0))), plan
 
 
 # The K-loop tails and the four epilogue forms of the LDS-free and weight-slice cells at 70 rows (ragged against every row tile).  nks = K / 16 steps
@@ -176,6 +187,11 @@ def _cell_runs_forced_family(variant, H, K1):
     if 15 <= variant <= 18:
         return direct and H == 512 and K1 in (0, 512)
     return False
+
+
+def _cell_forced_family(variant):
+    """the kernel family a forced cell variant names"""
+    return "staged" if variant in (1, 2, 3, 8) else "direct" if 4 <= variant <= 7 else "wlds" if 9 <= variant <= 14 else "wlds-overlap" if 15 <= variant <= 18 else None
 
 
 _cell_tail_cache = {}
@@ -211,6 +227,24 @@ def test_cell_tail_cases_run_the_forced_kernels():
     cases = [(v, H, K1) for H, K1 in CELL_TAIL_SHAPES for v in CELL_TAIL_VARIANTS] + [(v, H, K1) for H, K1 in CELL_OVL_SHAPES for v in CELL_OVL_VARIANTS]
     forced = sum(_cell_runs_forced_family(*c) for c in cases)
     assert len(cases) == 10 * 7 + 2 * 4 and forced == len(cases) - 7 and 2 * forced > len(cases), (forced, len(cases))      # all but the refused H = 272
+    # the hand rule against the library's plan (fn_gru_cell_plan: a pure host function) for all 78, on 16-byte aligned made-up addresses
+    import ctypes
+    from mfn_import import load_package
+    load_package()
+    from music_fader_nets_amd import _lib
+    lib, A = _lib.load(), 0x10000
+    for v, H, K1 in cases:
+        c = _lib.FnGruCell(B=CELL_TAIL_ROWS, H=H, K1=K1, ldx=K1, ldw_ih=K1, ldh=H, ldw_hh=H, ldo=H, variant=v, h_prev=A, w_hh=A, b_hh=A, b_ih=A, h_out=2 * A)
+        if K1:
+            c.x = c.w_ih = A
+        plan = _lib.FnGruCellPlan()
+        assert lib.fn_gru_cell_plan(ctypes.byref(c), ctypes.byref(plan)) == 0
+        if H % 32:
+            assert plan.status == _lib.FN_E_SHAPE and not _cell_runs_forced_family(v, H, K1), (v, H, K1)
+            continue
+        p = plan.as_dict()
+        assert p["status"] == 0 and p["forced_honoured"] == _cell_runs_forced_family(v, H, K1), (v, H, K1, p)
+        assert p["family"] == (_cell_forced_family(v) if p["forced_honoured"] else "staged"), (v, H, K1, p)
 
 
 @pytest.mark.parametrize("variant,H,K1", [(v, H, K1) for H, K1 in CELL_TAIL_SHAPES for v in CELL_TAIL_VARIANTS]
@@ -228,6 +262,9 @@ def test_gru_cell_ring_tails_and_epilogue_forms(ops, variant, H, K1):
             continue
         ops.gru_cell(hp, whh, bhh, out[0], variant=variant, **kw)
         ops.gru_cell(hp, whh, bhh, out[1], variant=variant, **kw)
+        plan = ops.gru_cell_plan(hp, whh, bhh, out[0], variant=variant, **kw)
+        assert plan["forced_honoured"] == _cell_runs_forced_family(variant, H, K1) and (plan["has_tab"], plan["has_rb"]) == (int(tab), int(rb)), plan
+        assert plan["family"] == (_cell_forced_family(variant) if plan["forced_honoured"] else "staged"), plan
         close(out[0], ref, 2e-5, "gru_cell variant %d H %d K1 %d table %d row constant %d" % (variant, H, K1, tab, rb))
         assert torch.equal(out[0], out[1]), (variant, H, K1, tab, rb)
 
@@ -451,9 +488,16 @@ def test_scans_every_step_vs_fp64(ops, case):
     kw = [dict(persistent=case["persistent"], cu_budget=case["budget"][i], variant=case["variants"][i]) for i in (0, 1)]
     try:
         ops.dw_x6 = case["x6"]
-        got = run_scans(ops, scans, rows, device=DEV, chunk=chunk, x6=case["x6"], fwd_kw=kw[0], bwd_kw=kw[1])
+        rec = PlanRecorder(ops)
+        got = run_scans(rec, scans, rows, device=DEV, chunk=chunk, x6=case["x6"], fwd_kw=kw[0], bwd_kw=kw[1])
         torch.cuda.synchronize()
         assert not ops.gru_sync_error()
+        # the library's own plan on the real descriptors: the candidate every launch of the case took on this device is the kernel the case is for
+        for want, plans in zip(case["kernels"], (rec.fwd, rec.bwd)):
+            assert len(plans) == (1 if chunk is None else -(-scans[0]["T"] // chunk))
+            assert want is None or set(chosen_kernels(plans)) == {want}, (want, plans)
+        for i, plans in enumerate((rec.fwd, rec.bwd)):           # ... and what the hand restatement names (a case without named kernels included)
+            assert set(chosen_kernels(plans)) == {nm[i] for nm in names}, (names, plans)
         if case["x6"]:
             ops.dw_x6 = False
             f32 = run_scans(ops, scans, rows, device=DEV, chunk=chunk, x6=False)
@@ -466,6 +510,32 @@ def test_scans_every_step_vs_fp64(ops, case):
     print()
     for line in scan_lines(case["id"], names[0], worst):
         print(line)
+
+
+def test_scan_with_a_misaligned_h_all_runs_per_step(ops):
+    """B = 33, H = 64, T = 3, one scan, h_all a view 4 bytes behind a 16-byte boundary: the weight-stationary kernels' epilogues move 16-byte vectors, so
+    the plan of the forward and of the backward call has the per-step candidate only; the results are bit-identical to the per-step kernels on aligned
+    buffers and within the bound of the CPU restatement"""
+    from fake_ops import FakeOps
+    scans = _ws_scans(torch.Generator().manual_seed(3364), 33, 64, T=3, n=1)
+    ref = run_scans(FakeOps(), scans)
+    try:
+        ops.dw_x6 = False
+        rec = PlanRecorder(ops)
+        off = run_scans(rec, scans, device=DEV, h_all_off=1)
+        aligned = run_scans(ops, scans, device=DEV, fwd_kw=dict(persistent=False), bwd_kw=dict(persistent=False))
+        torch.cuda.synchronize()
+        assert not ops.gru_sync_error()
+    finally:
+        ops.dw_x6 = _x6_default()
+    for plans, step in ((rec.fwd, "gru_fwd_step_kernel"), (rec.bwd, "gru_bwd_step_kernel")):
+        assert len(plans) == 1 and plans[0]["ws_absent"] == "unaligned" and plans[0]["chosen"] == 0, plans
+        assert [c["kernel"] for c in plans[0]["candidates"]] == [step], plans
+    assert set(off[0]) == set(aligned[0]) == set(ref[0]) and {"h_all", "dgx_all", "dghn_all", "dh0", "dgx_rowsum"} <= set(off[0])
+    for k in off[0]:
+        assert torch.equal(off[0][k], aligned[0][k]), k
+        close(off[0][k], ref[0][k], 2e-5 if k in ("h_all", "gate_r", "gate_z", "gate_n", "gate_hn") else 5e-5, "misaligned h_all: " + k)
+        close(aligned[0][k], ref[0][k], 2e-5 if k in ("h_all", "gate_r", "gate_z", "gate_n", "gate_hn") else 5e-5, "per-step: " + k)
 
 
 def test_nine_scans_in_one_call_are_refused(ops):

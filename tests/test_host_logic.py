@@ -452,6 +452,23 @@ def test_gemm_plan_invariants_under_sanitizers(tmp_path):
     assert "FINDING" not in p.stdout and p.stdout.strip().endswith("1847295 plans, 0 findings"), p.stdout[-2000:]
 
 
+def test_gru_plan_invariants_under_sanitizers(tmp_path):
+    """csrc/gru_plan.h (the one place that decides what fn_gru_seq_fwd / fn_gru_seq_bwd / fn_gru_cell_f32 launch) compiled for the host
+    (csrc/host/gru_plan_check.cpp, a stand-alone program, nothing preloaded): the table of return codes, and over scans, shapes, variant bits, forced
+    row blocks, alignments, compute units and budgets every plan's grid is groups x slices within the counters, the LDS and one workgroup per compute
+    unit, the per-step candidate is last, bf16 x 6 has one candidate or none, fn_gru_*_x6_ok agree with the plan; the same for the cell - 0 findings."""
+    import subprocess
+    asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    if not os.path.isabs(asan) or not os.path.exists(asan):
+        pytest.skip("no AddressSanitizer runtime on this box (gcc -print-file-name=libasan.so)")
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "music-fader-nets_amd", "csrc", "host", "gru_plan_check.cpp")
+    exe = str(tmp_path / "gru_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-Wall", "-Werror", src, "-o", exe], check=True, capture_output=True, timeout=300)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, (p.stdout[-2000:], p.stderr[-3000:])
+    assert "FINDING" not in p.stdout and p.stdout.strip().endswith("49 return codes, 3400000 plans, 0 findings"), p.stdout[-2000:]
+
+
 def test_fake_ops_do_not_read_an_output_they_overwrite():
     """beta == 0 means the output is write-only, as in the kernels (gemm.hip: `if (beta != 0.f)`): the engine hands over uninitialised
     buffers, and 0 x NaN is NaN.  (FakeOps.gru_dwhh once formed beta * dW: the gradient comparison above failed whenever the allocator

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from fake_ops import FakeOps
-from helpers import (SCAN_BWD_QUANTITIES, SCAN_CASES, SCAN_F, SCAN_F_CAP, SCAN_INPUTS, check_scan_vs_f64, relerr, run_scans, scan_inputs, scan_kernel_names,
+from helpers import (SCAN_BWD_QUANTITIES, SCAN_CASES, SCAN_F, SCAN_F_CAP, SCAN_INPUTS, check_scan_vs_f64, lib_scan_candidates, relerr, run_scans, scan_inputs,
+                     scan_kernel_candidates, scan_kernel_names,
                      scan_reference_f64, scan_references, scan_rows, scan_step_errors)
 
 
@@ -49,7 +50,7 @@ def test_fake_ops_passes_and_inputs_satisfy_the_condition(name):
 
 def test_every_gpu_case_names_inputs_and_reaches_its_kernels():
     """the shapes of the case table reach the kernel instances the cases are meant for (the dispatch restated by scan_kernel_names), first and tail
-    chunk of a chained case alike, and together they name every instance fn_gru_fwd_persist / fn_gru_bwd_persist can launch"""
+    chunk of a chained case alike, and together they name every instance fn_gru_seq_fwd / fn_gru_seq_bwd can launch"""
     seen = set()
     for c in SCAN_CASES:
         scans, rows, chunk = scan_inputs(c["inputs"])
@@ -65,6 +66,79 @@ def test_every_gpu_case_names_inputs_and_reaches_its_kernels():
     every |= {"gru_fwd_persist_kernel<%s, 4>" % t for t in tilings} | {"gru_bwd_persist_kernel<%s, 8>" % t for t in tilings}
     assert every <= seen, sorted(every - seen)
     assert len({c["id"] for c in SCAN_CASES}) == len(SCAN_CASES)
+
+
+def test_restated_dispatch_is_the_librarys_on_every_gpu_case():
+    """scan_kernel_candidates (the hand restatement the case table is checked with) against fn_gru_fwd_plan / fn_gru_bwd_plan at 256 compute units:
+    the same candidates in the same order for every case, first and tail chunk, aligned and with a misaligned epilogue operand"""
+    for c in SCAN_CASES:
+        scans, rows, chunk = scan_inputs(c["inputs"])
+        for T in [None] if chunk is None else sorted({chunk, scans[0]["T"] % chunk or chunk}):
+            for aligned in ((True, True), (False, True), (True, False)):
+                kw = dict(variants=c["variants"], x6=c["x6"], cu_budget=c["budget"], persistent=c["persistent"], T=T, cus=256, aligned=aligned)
+                assert scan_kernel_candidates(scans, **kw) == lib_scan_candidates(scans, **kw), (c["id"], T, aligned)
+
+
+def test_restated_dispatch_is_the_librarys_on_a_seeded_sweep():
+    """the same over 4000 seeded descriptor sets drawn from the value sets of csrc/host/gru_plan_check.cpp: 1-8 scans, mostly of one B / H / T, every
+    variant bit and forced row block, compute units, budgets, alignment, gates and input sources present or absent"""
+    import random
+    rng = random.Random(20260)
+    Bs, Hs, Ts = (1, 16, 31, 32, 33, 64, 128, 200, 256, 512), (32, 64, 96, 512, 544), (1, 2, 3, 70)
+    bits = (0, 0, 0, 0, 0x100, 0x200, 0x400, 0x800, 0x1000, 0x2000, 0x8000)
+    seen = set()
+    for i in range(4000):
+        n = rng.randint(1, 8)
+        B, H, T = rng.choice(Bs), rng.choice(Hs + (512, 512)), rng.choice(Ts)
+        if i % 8 == 0:                                         # the production launches: 8 - 16 full row groups at H = 512
+            (n, B), H, T = rng.choice(((4, 256), (2, 256), (2, 512), (1, 512), (8, 64), (3, 256))), 512, 70
+        scans = []
+        for _ in range(n):
+            s = dict(B=B if rng.random() < 0.9 else rng.choice(Bs), H=H if rng.random() < 0.98 else rng.choice(Hs), T=T if rng.random() < 0.9 else rng.choice(Ts))
+            src = rng.choice(("table", "table", "dense", "both"))
+            s.update({k: True for k in (("gx_table",) if src == "table" else ("gx_dense",) if src == "dense" else ("gx_table", "gx_dense"))})
+            s["gates"] = rng.random() < 0.95
+            scans.append(s)
+        kw = dict(variants=tuple(rng.choice(bits) | rng.choice(bits) | rng.choice((0, 0, 0, 0, 16, 32, 64, 128, 5)) for _ in range(2)), x6=rng.random() < 0.3,
+                  cu_budget=(rng.choice((0, 128)), rng.choice((0, 128))), persistent=rng.random() < 0.95, cus=rng.choice((16, 31, 32, 128, 248, 256, 304)),
+                  aligned=(rng.random() < 0.9, rng.random() < 0.9))
+        if i % 8 == 0:
+            kw.update(variants=(rng.choice((0, 0x8000)), rng.choice((0, 0x8000))), x6=rng.random() < 0.5, cus=rng.choice((256, 304)), aligned=(True, True))
+        mine, theirs = scan_kernel_candidates(scans, **kw), lib_scan_candidates(scans, **kw)
+        assert mine == theirs, (i, scans, kw, mine, theirs)
+        seen.update(mine[0] + mine[1])
+    from music_fader_nets_amd import _lib
+    assert seen == set(_lib.GRU_PLAN_KERNELS), sorted(set(_lib.GRU_PLAN_KERNELS) - seen)
+
+
+def test_scan_plan_kernel_names_follow_the_header_enum():
+    import ctypes
+    import os
+    import re
+    from mfn_import import ROOT, load_package
+    load_package()
+    from music_fader_nets_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "fadernets.h")).read()
+    names = re.findall(r"^\s*(FN_GRU_(?:FWD|BWD)_[A-Z0-9_]+)", hdr.split("enum FnGruKernel {")[1].split("};")[0], re.M)
+    assert len(names) == len(_lib.GRU_PLAN_KERNELS) == 22
+
+    def kernel_name(n):
+        d, rest = n[len("FN_GRU_"):].lower().split("_", 1)
+        if rest == "step":
+            return "gru_%s_step_kernel" % d
+        if rest.startswith("ws_"):
+            return "gru_%s_persist_kernel<%s, %d>" % (d, rest[3:].replace("_", ", "), 8 if d == "bwd" else 4)
+        fam, t = rest.rsplit("_", 1)
+        return "gru_%s_%s_kernel<%s>" % (d, fam, t)
+    assert tuple(kernel_name(n) for n in names) == _lib.GRU_PLAN_KERNELS
+    src = open(os.path.join(ROOT, "music-fader-nets_amd", "csrc", "gru_persist.hip")).read() + open(os.path.join(ROOT, "music-fader-nets_amd", "csrc", "gru.hip")).read()
+    for k in _lib.GRU_PLAN_KERNELS:
+        assert re.search(r"\b%s\b" % k.split("<")[0], src), k
+    lib, plan = _lib.load(), _lib.FnGruPlan()
+    assert lib.fn_gru_fwd_plan(None, 1, 256, None) == _lib.FN_E_NULL and lib.fn_gru_bwd_plan(None, 1, 256, None) == _lib.FN_E_NULL
+    assert lib.fn_gru_fwd_plan(None, 1, -1, ctypes.byref(plan)) == _lib.FN_E_SHAPE and lib.fn_gru_bwd_plan(None, 1, -1, ctypes.byref(plan)) == _lib.FN_E_SHAPE
+    assert lib.fn_gru_fwd_plan(None, 1, 256, ctypes.byref(plan)) == 0 and plan.status == _lib.FN_E_NULL and plan.n == 0
+    assert lib.fn_gru_cell_plan(None, None) == _lib.FN_E_NULL
 
 
 @pytest.mark.parametrize("B", [65, 200, 256, 512, 33, 1])
