@@ -955,6 +955,73 @@ int fn_latent_mix(const float* a, const float* b, int64_t ab_ld, int pairs, int 
                   const FnMixSeg* segs, int n_segs, float* out, int64_t out_ld, float* omega_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Importance-weighted log-likelihood (likelihood.py): S draws from the posterior q(z|x) per piece with their densities, and the reduction of the
+ * S log-weights per piece (Burda et al., "Importance Weighted Autoencoders").  OURS; the reference reports one reparameterised sample and the
+ * analytic KL.  The text below is the specification.  Both entry points are additive: fn_version() stays 6.  LOG_2PI = log(2 pi) in fp64.
+ *
+ * fn_posterior_draw: S samples of q(z|x) = N(mu, (tau sigma)^2) for each of B source rows, up to FN_DRAW_MAX_JOBS jobs in ONE launch (jobs is a HOST
+ * array, read by value; params_dev is fn_latent_draw's FnDrawParams in DEVICE memory).  The usual two jobs (stream 0 rhythm, stream 1 note) write
+ * z_r | z_n into the teacher-forced decoder's own (B*S, 2Z+24) latent rows: sample s of source row b is row i = b*S + s, a job writes
+ * z[i*z_ld + j] for j in [0, Z) and touches no other column.  For job e, source row b, sample s, column j, with q = j / 4:
+ *   1. eps is the normal of fn_latent_draw's steps 1-2 from the counter (b, (stream_id << 16) | q, lo(offset + s), hi(offset + s)) under the key
+ *      seed; offset + s is a 64-bit add that wraps.  Sample (b, s) is therefore, bit for bit, row b of fn_latent_draw's eps_out at offset + s, and
+ *      depends on neither B, S, n_jobs nor the launch geometry.  (One device function serves both entry points.)
+ *   2. sg = tau * expf(pre[b][Z + j]) in fp32 (pre [B][2Z]: mu | v, sigma = expf(v), exactly as fn_latent_fwd reads it; tau from params_dev, clamped
+ *      as fn_latent_draw clamps it);  z[i][j] = pre[b][j] + sg * eps;  eps_out[i*Z + j] = eps when given.
+ *   3. The densities, functions of the STORED fp32 values z, mu, sg, mu_lk, lv_lk evaluated in fp64 - at the stored z, not at eps: the weight must
+ *      be the density ratio at the point the decoder sees.
+ *        logq[i] = sum_j -0.5 * (d*d + LOG_2PI) - log((double)sg),  d = ((double)z - (double)mu) / (double)sg
+ *        ll_k    = sum_j -0.5 * (dz*dz * exp(-(double)lv_lk[k][j]) + (double)lv_lk[k][j] + LOG_2PI) + log(1.0 / K),  dz = (double)z - (double)mu_lk[k][j]
+ *                  (the component log-likelihood of approx_qy_x, gmm_model.py:204-215, as fn_latent_fwd forms it)
+ *        logp[i] = m + log(sum_k exp(ll_k - m)),  m = max_k ll_k,  k ascending
+ *      Every sum over j: lane l of 64 adds its terms j = l, l + 64, ... ascending from 0.0 (a term is the whole summand, -log sg included), then
+ *      s[l] += s[l ^ o] for o = 32, 16, 8, 4, 2, 1.
+ * sg == 0 or a non-finite input gives unspecified values for that row; every access stays in bounds.  One wavefront per (b, s) row, blockIdx.y the
+ * job; no LDS, no atomics, no hand-over between workgroups; plain dword-wide vector stores, so a job's columns may start at any column of a wider row.
+ *   NULL jobs, params_dev, or a job's pre, mu_lk, lv_lk, z, logq or logp: FN_E_NULL (answered first);  n_jobs outside [1, FN_DRAW_MAX_JOBS]:
+ *   FN_E_COUNT;  B, S or Z < 1, z_ld < Z, a K < 1, a stream_id outside [0, 65535): FN_E_SHAPE;  a K > FN_POST_MAX_K (fn_latent_fwd's limit),
+ *   Z > FN_DRAW_MAX_Z, B * S >= 2^31: FN_E_UNSUPPORTED;  a float pointer (params_dev included) that is not 4-byte aligned, logq or logp not 8-byte
+ *   aligned: FN_E_ALIGN;  in this order, all before any launch.
+ *
+ * fn_iw_reduce: nll_tb is fn_out_head_f32's nll_rows of the B*S decoder rows (step t, row i at nll_tb[t*nll_ld + i]); t0, t1 [B] give the scored
+ * span [t0[b], t1[b]) of source row b, clamped to [0, T] on the device, or are both NULL for [0, T); logp_z / logq_z hold the densities of latent e
+ * at + e*lat_stride, [B*S] each (fn_posterior_draw's outputs).  One launch, two passes over a piece's samples.  Per row i = b*S + s:
+ *   recon = -(sum_t (double)nll), over the span, t ascending from 0.0 (an empty span: 0);
+ *   lw[i] = recon + sum_e (logp_e[i] - logq_e[i]), each difference formed first, then added e ascending.  lw [B*S] is a required output: the
+ *   per-sample log-weight, and the second pass's input.
+ * Per source row b, lane l of 64 taking s = l, l + 64, ... ascending (sums from 0.0, the maximum from -inf), then the xor butterfly of offsets 32 .. 1:
+ *   m = max_s lw;  W1 = sum exp(lw - m);  W2 = sum exp(lw - m)^2
+ *   out[b][0] = m + log(W1) - log((double)S)      the importance-weighted bound
+ *   out[b][1] = (sum_s lw) / S                    the one-sample ELBO, averaged
+ *   out[b][2] = W1*W1 / W2                        the effective sample size, in [1, S]
+ *   out[b][3] = (sum_s recon) / S
+ *   out[b][4+e] = (sum_s (logq_e - logp_e)) / S   the Monte-Carlo KL of latent e
+ * m == -inf gives out[b][0] = out[b][1] = -inf and out[b][2] = 0.  A NaN gives unspecified values, in bounds.  One wavefront per b: the first
+ * pass writes lw and finds m, the second re-reads lw for W1 and W2 - a lane re-reads only the lw values it wrote itself, and consecutive s are
+ * consecutive addresses of nll_tb, so the loads coalesce.  No LDS, no atomics.
+ *   NULL nll_tb, logp_z, logq_z, lw or out, one of t0 / t1 without the other: FN_E_NULL;  n_lat outside [1, FN_IW_MAX_LAT]: FN_E_COUNT;  B, S or
+ *   T < 1, nll_ld < B*S, lat_stride < B*S, out_ld < FN_IW_COLS + n_lat: FN_E_SHAPE;  B*S >= 2^31: FN_E_UNSUPPORTED;  nll_tb, t0 or t1 not 4-byte,
+ *   logp_z, logq_z, lw or out not 8-byte aligned: FN_E_ALIGN;  in this order, all before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_POST_MAX_K 8
+typedef struct FnPostJob {          /* host memory, by value, like FnDrawJob */
+    const float* pre;               /* [B][2Z]: mu | v, sigma = expf(v), exactly as fn_latent_fwd reads it   */
+    const float *mu_lk, *lv_lk;     /* [K][Z] prior tables                                                   */
+    float* z;                       /* row i = b*S + s, row stride z_ld (>= Z); writes columns [0, Z) only   */
+    float* eps_out;                 /* [B*S][Z] or NULL                                                      */
+    double *logq, *logp;            /* [B*S] each, required                                                  */
+    int32_t K, stream_id;           /* K in [1, 8] (fn_latent_fwd's limit); stream_id in [0, 65535)          */
+} FnPostJob;
+int fn_posterior_draw(const FnPostJob* jobs, int n_jobs, int B, int S, int Z, int64_t z_ld,
+                      const FnDrawParams* params_dev, void* stream);
+#define FN_IW_MAX_LAT 4
+#define FN_IW_COLS 4        /* iwae, elbo, ess, recon; then one kl column per latent */
+int fn_iw_reduce(const float* nll_tb, int T, int64_t nll_ld,           /* nll of step t, row i at nll_tb[t*nll_ld + i]: fn_out_head_f32's nll_rows */
+                 const int32_t* t0, const int32_t* t1,                 /* [B] span [t0, t1) of source row b, or both NULL = [0, T)                 */
+                 const double* logp_z, const double* logq_z, int n_lat, int64_t lat_stride,   /* latent e at + e*lat_stride, [B*S] each            */
+                 int B, int S, double* lw, double* out, int out_ld, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Reconstruction report (report.py, epochs.evaluation_phase): what the reference's evaluation_phase() computes behind its loss terms
  * (trainer_gmm.py:470-610) - the accuracies.  The reference's: `torch.argmax(a, dim=-1)` (:546) and the per-sample loop of acc() with its
  * np.trim_zeros cut (:549-565).  OURS: the negative log-likelihood and the rank of the target per token, which re-ranking decoded hypotheses

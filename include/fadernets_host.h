@@ -77,6 +77,10 @@ int fn_notes_stitch_host(const FnNote* dec, int dec_rs, int dec_ld, const int32_
 int fn_latent_draw_host(const FnDrawJob* jobs, int n_jobs, int rows, int Z, int64_t z_ld, const FnDrawParams* params, void* stream);   /* fn_latent_draw */
 int fn_latent_mix_host(const float* a, const float* b, int64_t ab_ld, int pairs, int D, const float* t, int P, int t_per_pair,
                        const FnMixSeg* segs, int n_segs, float* out, int64_t out_ld, float* omega_out, void* stream);                 /* fn_latent_mix */
+/* posterior draw with densities, importance-weight reduce */
+int fn_posterior_draw_host(const FnPostJob* jobs, int n_jobs, int B, int S, int Z, int64_t z_ld, const FnDrawParams* params, void* stream);   /* fn_posterior_draw */
+int fn_iw_reduce_host(const float* nll_tb, int T, int64_t nll_ld, const int32_t* t0, const int32_t* t1, const double* logp_z, const double* logq_z, int n_lat,
+                      int64_t lat_stride, int B, int S, double* lw, double* out, int out_ld, void* stream);                                    /* fn_iw_reduce */
 size_t fn_frag_floats_host(int rows, int K);                                                            /* fn_frag_floats */
 size_t fn_gru_gates_floats_host(int B, int H);                                                           /* fn_gru_gates_floats */
 

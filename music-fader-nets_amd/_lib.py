@@ -61,7 +61,8 @@ FN_DRAW_MAX_JOBS, FN_DRAW_MAX_Z, FN_DRAW_MAX_K = 4, 4096, 1024
 FN_MIX_LERP, FN_MIX_SLERP, FN_MIX_STEP = 0, 1, 2
 FN_MIX_MAX_SEGS, FN_MIX_MIN_SIN = 4, 1e-4
 FN_MATCH_EMPTY = 1
-_f = C.POINTER(C.c_float)
+FN_POST_MAX_K, FN_IW_MAX_LAT, FN_IW_COLS = 8, 4, 4
+_f =C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
 vp = C.c_void_p
 
@@ -202,6 +203,10 @@ class FnDrawJob(C.Structure):
     _fields_ = [("mu_lk", vp), ("lv_lk", vp), ("comp", vp), ("z", vp), ("eps_out", vp), ("comp_out", vp), ("K", C.c_int32), ("stream_id", C.c_int32)]
 
 
+class FnPostJob(C.Structure):
+    _fields_ = [("pre", vp), ("mu_lk", vp), ("lv_lk", vp), ("z", vp), ("eps_out", vp), ("logq", vp), ("logp", vp), ("K", C.c_int32), ("stream_id", C.c_int32)]
+
+
 class FnMixSeg(C.Structure):
     _fields_ = [("off", C.c_int32), ("len", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32)]
 
@@ -271,6 +276,8 @@ SIGNATURES = {
     "fn_notes_stitch": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
     "fn_latent_draw": (C.c_int, [C.POINTER(FnDrawJob), C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
     "fn_latent_mix": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FnMixSeg), C.c_int, vp, C.c_int64, vp, vp]),
+    "fn_posterior_draw": (C.c_int, [C.POINTER(FnPostJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
+    "fn_iw_reduce": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "fn_token_score": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]),
     "fn_match_rows": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),

@@ -159,6 +159,20 @@ __device__ __forceinline__ void fn_philox4x32_10(uint32_t c0, uint32_t c1, uint3
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// Box-Muller on the four words of a quad (fn_latent_draw, step 2): w -> four normals.  fn_latent_draw and fn_posterior_draw both take them from here,
+// which is what makes a posterior sample bit-equal to the prior draw's eps at the same counter.
+__device__ __forceinline__ void fn_quad_normals(const uint32_t w[4], float n[4]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float ua = (float)((w[2 * h] >> 8) + 1u) * 0x1p-24f, ub = (float)(w[2 * h + 1] >> 8) * 0x1p-24f;
+        const float r = sqrtf(-2.0f * logf(ua));
+        float s, c;
+        sincospif(2.0f * ub, &s, &c);
+        n[2 * h] = r * c;
+        n[2 * h + 1] = r * s;
+    }
+}
+
 // pack(x, v) over V columns: order-preserving key of x in the high half, V - 1 - v in the low half, so the 64-bit maximum is the largest x and, among
 // equals, the lowest column (fn_out_argmax_f32, fn_beam_step)
 __device__ __forceinline__ unsigned long long fn_pack_best(float x, int v, int V) {

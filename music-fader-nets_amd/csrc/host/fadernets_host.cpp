@@ -12,6 +12,7 @@
 #include "constrain_host.h"
 #include "notes_host.h"
 #include "latent_ops_host.h"
+#include "likelihood_host.h"
 
 namespace {
 
@@ -590,6 +591,15 @@ int fn_latent_draw_host(const FnDrawJob* jobs, int n_jobs, int rows, int Z, int6
 int fn_latent_mix_host(const float* a, const float* b, int64_t ab_ld, int pairs, int D, const float* t, int P, int t_per_pair, const FnMixSeg* segs,
                        int n_segs, float* out, int64_t out_ld, float* omega_out, void*) {
     return fn_latent_host::latent_mix(a, b, ab_ld, pairs, D, t, P, t_per_pair, segs, n_segs, out, out_ld, omega_out);
+}
+
+int fn_posterior_draw_host(const FnPostJob* jobs, int n_jobs, int B, int S, int Z, int64_t z_ld, const FnDrawParams* params, void*) {
+    return fn_lik_host::posterior_draw(jobs, n_jobs, B, S, Z, z_ld, params);
+}
+
+int fn_iw_reduce_host(const float* nll_tb, int T, int64_t nll_ld, const int32_t* t0, const int32_t* t1, const double* logp_z, const double* logq_z, int n_lat,
+                      int64_t lat_stride, int B, int S, double* lw, double* out, int out_ld, void*) {
+    return fn_lik_host::iw_reduce(nll_tb, T, nll_ld, t0, t1, logp_z, logq_z, n_lat, lat_stride, B, S, lw, out, out_ld);
 }
 
 size_t fn_decode_ws_bytes_host(int B, int H, int) { return (size_t)4 * B * H * sizeof(float) + 16; }

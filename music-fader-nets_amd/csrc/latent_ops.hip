@@ -28,15 +28,7 @@ __global__ __launch_bounds__(256) void latent_draw_kernel(DrawArgs a, int rows, 
     uint32_t w[4];
     fn_philox4x32_10((uint32_t)b, sid | (uint32_t)q, pr.offset_lo, pr.offset_hi, pr.seed_lo, pr.seed_hi, w);
     float n[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float ua = (float)((w[2 * h] >> 8) + 1u) * 0x1p-24f, ub = (float)(w[2 * h + 1] >> 8) * 0x1p-24f;
-        const float r = sqrtf(-2.0f * logf(ua));
-        float s, c;
-        sincospif(2.0f * ub, &s, &c);
-        n[2 * h] = r * c;
-        n[2 * h + 1] = r * s;
-    }
+    fn_quad_normals(w, n);
     // 3. the row's component: given, or drawn from the row's own counter
     int k = jb.comp ? jb.comp[b] : -1;
     if (k < 0) {

@@ -81,7 +81,7 @@ def training_phase(trainer, step, n_epochs, vgm_train_dl, vgm_val_dl, train_dl, 
     return step
 
 
-def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True):
+def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True, iw_samples=0):
     """``run(dl)`` of the reference's ``evaluation_phase()`` (trainer_gmm.py:479-601) over every loader of `loaders`, on
     report.reconstruction_report: a batch of eight fields ``(d, r, n, c, arousal, valence, r_density, n_density)`` is a supervised one (the
     reference's ``is_vgmidi``), a batch of six an unsupervised one.  Per loader the reference's lines
@@ -95,8 +95,15 @@ def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True):
     for the two posterior-class accuracies - a number that shrinks with the batch size; here they are per-sample means like the other three.
     ``step`` is the reference's module-level step (it sets the KL weight inside the loss only).
     -> one dict per loader: CE_X, CE_R, CE_N, l_r, l_n, kld_latent, kld_class, loss (means over the batches), acc_x, acc_r, acc_n, acc_y_r,
-    acc_y_n, topk_x (per-sample means), nll_per_token, n_tokens, n_samples, n_empty, n_batches."""
+    acc_y_n, topk_x (per-sample means), nll_per_token, n_tokens, n_samples, n_empty, n_batches.
+    iw_samples > 0 (ours): a second walk over the loader, likelihood.likelihood_report with that many posterior samples per piece, and one more line
+
+        IW: <nats_per_piece>  <nats_per_token>  <bits_per_token>  <elbo_per_piece>  <mean_ess>
+
+    with the report's dict under "iw"; with the default 0 nothing else is called or printed."""
     from .report import reconstruction_report
+    if isinstance(iw_samples, bool) or not isinstance(iw_samples, int) or iw_samples < 0:
+        raise ValueError("iw_samples: an int >= 0, got %r" % (iw_samples,))
     if trainer.dist is not None and trainer.dist.world > 1:
         raise NotImplementedError("evaluation_phase: multi-rank reporting is not implemented - run it in a single process")
     results = []
@@ -126,6 +133,11 @@ def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True):
         log("CE: {:.4}  {:.4}  {:.4}".format(res["CE_X"], res["CE_R"], res["CE_N"]))
         log("Regularized: {:.4}  {:.4}".format(res["l_r"], res["l_n"]))
         log("Acc: {:.4}  {:.4}  {:.4}  {:.4}  {:.4}".format(res["acc_x"], res["acc_r"], res["acc_n"], res["acc_y_r"], res["acc_y_n"]))
+        if iw_samples:
+            from .likelihood import likelihood_report
+            iw = res["iw"] = likelihood_report(trainer.model, dl, samples=iw_samples)
+            log("IW: {:.4}  {:.4}  {:.4}  {:.4}  {:.4}".format(iw["nats_per_piece"], iw["nats_per_token"], iw["bits_per_token"], iw["elbo_per_piece"],
+                                                                 iw["mean_ess"]))
         results.append(res)
     return results
 

@@ -875,6 +875,50 @@ class HipOps:
         _lib.check(self.lib.fn_latent_mix(pa, pb, ld, pairs, D, _p(t), P, 1 if per_pair else 0, arr, len(segs), po, ldo, _p(omega_out), self.stream()),
                    "fn_latent_mix")
 
+    def posterior_draw(self, jobs, S, params):
+        """fn_posterior_draw: jobs = up to 4 dicts of pre (contiguous fp32 [B][2Z]: mu | log sigma), mu_lk, lv_lk (contiguous fp32 [K][Z]), z (a 2-D fp32
+        view [B*S][Z] with unit inner stride; all jobs share its row stride), logq, logp (contiguous fp64 [B*S]), stream_id and optionally eps_out
+        (contiguous fp32 [B*S][Z]); params: the 32 bytes of FnDrawParams on the device"""
+        _dense(params, torch.uint8, "params")
+        if params.numel() != C.sizeof(_lib.FnDrawParams) or not 1 <= len(jobs) <= _lib.FN_DRAW_MAX_JOBS:
+            raise RuntimeError("posterior_draw: 1..%d jobs and %d parameter bytes, got %d and %d" % (
+                _lib.FN_DRAW_MAX_JOBS, C.sizeof(_lib.FnDrawParams), len(jobs), params.numel()))
+        arr = (_lib.FnPostJob * len(jobs))()
+        pz, rows, Z, z_ld = _mat(jobs[0]["z"], "z")
+        S = int(S)
+        B = rows // S if S > 0 else 0
+        for j, d in zip(arr, jobs):
+            pz, r, zc, ld = _mat(d["z"], "z")
+            pre, mu, lv, eps_out, logq, logp = d["pre"], d["mu_lk"], d["lv_lk"], d.get("eps_out"), d["logq"], d["logp"]
+            _dense(pre, name="pre"), _dense(mu, name="mu_lk"), _dense(lv, name="lv_lk"), _dense(eps_out, name="eps_out")
+            _dense(logq, torch.float64, "logq"), _dense(logp, torch.float64, "logp")
+            if B < 1 or B * S != rows or (r, zc, ld) != (rows, Z, z_ld) or tuple(pre.shape) != (B, 2 * Z) or mu.dim() != 2 or mu.shape[1] != Z or (
+                    lv.shape != mu.shape) or logq.numel() != rows or logp.numel() != rows or (eps_out is not None and eps_out.numel() != rows * Z):
+                raise RuntimeError("posterior_draw: every job writes (%d, %d) = (B*%d, Z) at a row stride of %d from pre (B, %d) and [K][%d] tables; logq, "
+                                   "logp of %d, eps_out of %d entries" % (rows, Z, S, z_ld, 2 * Z, Z, rows, rows * Z))
+            j.pre, j.mu_lk, j.lv_lk, j.z, j.eps_out, j.logq, j.logp, j.K, j.stream_id = (
+                pre.data_ptr(), mu.data_ptr(), lv.data_ptr(), d["z"].data_ptr(), None if eps_out is None else eps_out.data_ptr(), logq.data_ptr(),
+                logp.data_ptr(), mu.shape[0], int(d["stream_id"]))
+        _lib.check(self.lib.fn_posterior_draw(arr, len(jobs), B, S, Z, z_ld, _p(params), self.stream()), "fn_posterior_draw")
+
+    def iw_reduce(self, nll, B, S, logp, logq, lw, out, t0=None, t1=None):
+        """fn_iw_reduce: nll a 2-D fp32 view [T][B*S] with unit inner stride (fn_out_head_f32's nll_rows); logp, logq 2-D fp64 views [n_lat][B*S] sharing a
+        row stride; lw contiguous fp64 [B*S]; out a 2-D fp64 view [B][4 + n_lat]; t0, t1 contiguous int32 [B], both or neither"""
+        pn, T, rows, nll_ld = _mat(nll, "nll")
+        _dense(lw, torch.float64, "lw"), _dense(t0, torch.int32, "t0"), _dense(t1, torch.int32, "t1")
+        for t, nm in ((logp, "logp"), (logq, "logq"), (out, "out")):
+            _chk(t, torch.float64, nm)
+            if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise RuntimeError("iw_reduce: %s must be 2-D with contiguous rows, got shape %s strides %s" % (nm, tuple(t.shape), t.stride()))
+        ldo = lambda t: t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+        n_lat = logp.shape[0]
+        if rows != B * S or tuple(logp.shape) != (n_lat, rows) or tuple(logq.shape) != (n_lat, rows) or ldo(logp) != ldo(logq) or lw.numel() != rows or (
+                tuple(out.shape) != (B, _lib.FN_IW_COLS + n_lat)) or (t0 is None) != (t1 is None) or (t0 is not None and (t0.numel() != B or t1.numel() != B)):
+            raise RuntimeError("iw_reduce: nll%s logp%s logq%s lw%s out%s for B %d S %d" % (
+                tuple(nll.shape), tuple(logp.shape), tuple(logq.shape), tuple(lw.shape), tuple(out.shape), B, S))
+        _lib.check(self.lib.fn_iw_reduce(pn, T, nll_ld, _p(t0), _p(t1), _p(logp), _p(logq), n_lat, ldo(logp), B, S, _p(lw), _p(out), ldo(out), self.stream()),
+                   "fn_iw_reduce")
+
     def sweep_scores(self, r, n, status, values, which, r_std, n_std, scores, n_used):
         """fn_sweep_scores: r, n fp32 and status int32 contiguous [S][Vn]; values fp64 [Vn]; scores fp64 [4]; n_used int32 [1]"""
         _dense(r, name="r"), _dense(n, name="n"), _dense(status, torch.int32, "status"), _dense(values, torch.float64, "values")

@@ -168,7 +168,11 @@ def main(argv=None):
     ap.add_argument("--bf16x6", action="store_true", help="same as --arith bf16x6")
     ap.add_argument("--evaluate", action="store_true",
                     help="after training, the reference's evaluation_phase() over the four loaders: CE / Regularized / Acc lines (--model gmm, one process)")
+    ap.add_argument("--iw-samples", type=int, default=0, metavar="N",
+                    help="with --evaluate: one more line per loader, the importance-weighted log-likelihood from N posterior samples per piece (default 0: off)")
     opts = ap.parse_args(argv)
+    if opts.iw_samples < 0 or (opts.iw_samples and not opts.evaluate):
+        raise SystemExit("train: --iw-samples N >= 0 goes with --evaluate")
 
     import importlib
     pkg = importlib.import_module(__package__)
@@ -226,7 +230,7 @@ def main(argv=None):
                               name=args["name"], log=say, save=rank == 0)    # every rank runs the schedule, rank 0 writes the checkpoints
         if opts.evaluate:                                               # trainer_gmm.py:603-614
             say("Evaluate")
-            evaluation_phase(trainer, [dls[k] for k in ("train", "val", "vgm_train", "vgm_val")], log=say, step=step)
+            evaluation_phase(trainer, [dls[k] for k in ("train", "val", "vgm_train", "vgm_val")], log=say, step=step, iw_samples=opts.iw_samples)
     else:
         say("Train / Validation / Test")                                # trainer.py:74-75
         say(sizes["train"], sizes["val"], sizes["test"])
