@@ -6,7 +6,8 @@ block of that step alone: err <= SCAN_F x max(the fp32 restatement's own error t
 end-to-end gradients vs the reference's autograd: 5e-4 relative to each tensor's max; greedy-decode token ids
 bit-exact wherever the reference's own top-2 log-prob gap exceeds 1e-4 (a flipped near-tie changes every later token,
 so rows are compared up to the first sub-threshold gap); past those near-ties, every step of every decode path against an fp64 replay
-of its own tokens (helpers.replay_decode_check).
+of its own tokens (helpers.replay_decode_check).  The large-batch GRU cells additionally per 16 x 16 tile of h_out against float64, on operand
+views, K tails and exact piece passes, in tests/test_gpu_cell_paths.py.
 """
 import math
 import os
