@@ -324,6 +324,22 @@ int fn_gru_cell_f32(const FnGruCell* c, void* stream);
 int fn_out_argmax_f32(const float* h, int ldh, const float* W, int ldw, const float* bias, int B, int V, int K, uint64_t* best,
                       void* stream);
 int fn_best_tokens(const uint64_t* best, int steps, int B, int V, int32_t* tokens, int tok_ld, void* stream);
+/* The launch plan of fn_out_argmax_f32 (csrc/decode_plan.h, as fn_gru_cell_plan): status = what the call returns for these arguments (NULL, shape,
+ * a span of h or W of 4 GB or more, alignment - in this order); with FN_OK the kernel - the weight slice of a workgroup (48 rows x K) in LDS while
+ * it is at most 128 KB, on eight waves when K % 32 == 0, else the LDS-free loop -, its grid, threads and dynamic LDS.  The choice does not depend
+ * on the device; nothing touches it, nothing is enqueued.  FN_E_NULL without `plan`. */
+enum FnOutArgmaxKernel {         /* FnOutArgmaxPlan.kernel; names: _lib.OUT_ARGMAX_KERNELS */
+    FN_OUT_ARGMAX_LDS8 = 0,      /* out_argmax_lds8_kernel<4> */
+    FN_OUT_ARGMAX_LDS,           /* out_argmax_lds_kernel<8> */
+    FN_OUT_ARGMAX_DIRECT         /* out_argmax_direct_kernel<4> */
+};
+typedef struct FnOutArgmaxPlan {
+    int32_t status;
+    int32_t kernel;                 /* FnOutArgmaxKernel */
+    int32_t grid, threads, lds_bytes;
+} FnOutArgmaxPlan;
+int fn_out_argmax_plan(const float* h, int ldh, const float* W, int ldw, const float* bias, int B, int V, int K, const uint64_t* best,
+                       FnOutArgmaxPlan* plan);
 
 /* Backward of the same scans (autograd of nn.GRU / GRUCell in loss.backward(), trainer_gmm.py:249).
  *   dh_p = dh_ext[p] (+ dh_last at p = T-1) + carried gradient
@@ -538,6 +554,25 @@ typedef struct FnDecodeForce {
                                  else the first-index argmax of step i (as fn_decode_greedy)          */
 } FnDecodeForce;
 int fn_decode_forced(const FnDecode* d, const FnDecodeForce* f, void* stream);
+
+/* The launch plan of fn_decode_greedy (f == NULL) / fn_decode_forced (as fn_gru_fwd_plan for the scans): ONE pure host function (csrc/decode_plan.h:
+ * the descriptors and the number of compute units in, this struct out) that the launch goes by.  The kernel spins on counters that other workgroups
+ * of the same launch advance, so grid = nrep * per_rep is exactly what fits with one workgroup per compute unit.  status: what the call returns
+ * before anything is enqueued - the checks in their order (f's members, d's NULL members, shape, alignment), FN_E_UNSUPPORTED when one role set has
+ * more workgroups than the device compute units (no current device counts as 0 compute units), FN_E_SHAPE for more than 32 blocks; the other fields
+ * are valid with FN_OK only.  The occupancy query of the launch (does one workgroup with lds_bytes fit a compute unit) is not part of it.
+ * cus > 0 stands for the compute units of the device and touches no device, cus == 0 asks the current one.  Nothing is enqueued.
+ * FN_E_NULL without `plan`, FN_E_SHAPE for cus < 0.  fn_decode_plan and fn_out_argmax_plan are additive: fn_version() stays 6. */
+typedef struct FnDecodePlan {
+    int32_t status;
+    int32_t forced;                 /* 1: the fn_decode_forced instance of the kernel */
+    int32_t mt, block_rows, nblk;   /* row tiles of a block (1 up to 16 sequences, 4 from 353 on, else 2), its rows = 16 mt, blocks = ceil(B / block_rows) */
+    int32_t nvt, nslices;           /* output slices ceil(V / 16), hidden slices H / 16 */
+    int32_t per_rep, nrep;          /* workgroups of one role set 3 nslices + nvt + 1; replicas of it min(cus / per_rep, nblk): replica r takes blocks r, r + nrep, .. */
+    int32_t grid, threads, lds_bytes;
+    int64_t x1_off, x2_off, g2_off, logits_off, ws_floats; /* FnDecode.ws in floats: where the four regions start, where the last one ends (<= fn_decode_ws_bytes / 4) */
+} FnDecodePlan;
+int fn_decode_plan(const FnDecode* d, const FnDecodeForce* f, int cus, FnDecodePlan* plan);
 
 /* ------------------------------------------------------------------------------------------
  * Output heads

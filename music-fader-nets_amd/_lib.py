@@ -31,6 +31,8 @@ GRU_PLAN_KERNELS = ("gru_fwd_x6pp_kernel<1>", "gru_fwd_x6pp_kernel<2>", "gru_fwd
                     "gru_bwd_persist_kernel<1, 4, 1, 8>", "gru_bwd_step_kernel")
 GRU_PLAN_ABSENT = (None, "H > 512", "no sync_ws", "mixed H", "unaligned", "T < 2", "slices > cus", "no row block")
 GRU_CELL_FAMILIES = ("staged", "direct", "wlds", "wlds-overlap", "x6")
+# FnOutArgmaxPlan.kernel -> the kernel instance (enum FnOutArgmaxKernel, in its order)
+OUT_ARGMAX_KERNELS = ("out_argmax_lds8_kernel<4>", "out_argmax_lds_kernel<8>", "out_argmax_direct_kernel<4>")
 GRU_ROWS_MASK = 0xFF         # forced rows per workgroup (scans) / forced form 1-18 (cells)
 GRU_ALT_TILING = 0x100       # the alternative wave tiling of the 64-row configuration
 GRU_SYNC_ZEROED = 0x200      # the sync_ws counters are already zero
@@ -161,6 +163,27 @@ class FnDecodeForce(C.Structure):
     _fields_ = [("forced", vp), ("forced_ld", C.c_int32), ("force", vp)]
 
 
+class FnDecodePlan(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("status", "forced", "mt", "block_rows", "nblk", "nvt", "nslices", "per_rep", "nrep", "grid", "threads", "lds_bytes")] + [
+        (k, C.c_int64) for k in ("x1_off", "x2_off", "g2_off", "logits_off", "ws_floats")]
+
+    def as_dict(self):
+        """every field by name; forced as a bool"""
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d.update(forced=bool(self.forced))
+        return d
+
+
+class FnOutArgmaxPlan(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("status", "kernel", "grid", "threads", "lds_bytes")]
+
+    def as_dict(self):
+        """kernel by name"""
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d.update(kernel=OUT_ARGMAX_KERNELS[self.kernel])
+        return d
+
+
 class FnSampleParams(C.Structure):
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("offset_lo", C.c_uint32), ("offset_hi", C.c_uint32),
                 ("inv_temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32)]
@@ -240,6 +263,7 @@ SIGNATURES = {
     "fn_gru_bwd_plan": (C.c_int, [C.POINTER(FnGruBwd), C.c_int, C.c_int, C.POINTER(FnGruPlan)]),
     "fn_gru_cell_plan": (C.c_int, [C.POINTER(FnGruCell), C.POINTER(FnGruCellPlan)]),
     "fn_out_argmax_f32": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "fn_out_argmax_plan": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(FnOutArgmaxPlan)]),
     "fn_best_tokens": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "fn_gru_seq_bwd": (C.c_int, [C.POINTER(FnGruBwd), C.c_int, vp]),
     "fn_gru_bwd_x6_ok": (C.c_int, [C.POINTER(FnGruBwd), C.c_int]),
@@ -247,6 +271,7 @@ SIGNATURES = {
     "fn_decode_sync_ws_bytes": (C.c_size_t, []),
     "fn_decode_greedy": (C.c_int, [C.POINTER(FnDecode), vp]),
     "fn_decode_forced": (C.c_int, [C.POINTER(FnDecode), C.POINTER(FnDecodeForce), vp]),
+    "fn_decode_plan": (C.c_int, [C.POINTER(FnDecode), C.POINTER(FnDecodeForce), C.c_int, C.POINTER(FnDecodePlan)]),
     "fn_gru_dwhh_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "fn_gru_dwhh_f32": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_size_t, vp]),
     "fn_gru_dwhh_plan": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(FnGemmPlan)]),

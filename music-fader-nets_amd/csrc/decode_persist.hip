@@ -16,13 +16,15 @@
 // which is after every reader of step t has arrived.  The 4 waves of a workgroup split K and add their partial tiles through LDS.
 //
 // More than 32 sequences (the reference's evaluator decodes 8 fader values x 100 samples = 800 rows at once, test_class.py:84-85): the
-// batch is cut into BLOCKS of 32 rows (64 rows from FN_DECODE_MT4_ROWS sequences on) that travel through the same role workgroups one after the other - a pipeline: while L1 works on
+// batch is cut into BLOCKS of 32 rows (64 rows from DECODE_MT4_ROWS sequences on) that travel through the same role workgroups one after the other - a pipeline: while L1 works on
 // block b+1, P2 has block b, L2 block b-1 ... - with one set of counters and exchange slabs per block; the LDS-resident weight slices are
 // reused by every block, and a second replica of the whole role set (2 x 119 workgroups <= 256 CUs at H = 512) takes every other block.
 // Per-block state (a cell's own previous state slice, the per-row input constants) is re-read from the exchange slabs / L2 instead of
 // living in registers.  Per token: max(chain latency of one block, blocks per replica x busy time of the slowest role).
+// The block height, the block and replica counts, the grid, the LDS size and the carve-up of the workspace are decode_plan() of decode_plan.h.
 #include <atomic>
 
+#include "decode_plan.h"
 #include "gru_layout.h"
 
 #ifdef FN_TIMING
@@ -47,14 +49,7 @@ extern "C" int fn_ddbg_read(unsigned long long* host) {
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int C1 = 0, C2 = 32, C3 = 64, C4 = 96, C5 = 128;               // word offsets inside a block's counters (one 128-byte line each)
-constexpr int BLKW = 160;                                                 // counter words per block
-#ifndef FN_DECODE_MT4_ROWS
-#define FN_DECODE_MT4_ROWS 353                                            // from this many sequences on: 64-row blocks (measured crossover, profiles/r03_decode_block_pipeline.txt: 320 rows 34.5 vs 36.4 us per token, 384 rows 41.8 vs 35.9)
-#endif
-constexpr int MAXBLK = 32;                                                // blocks of 32 / 64 rows: up to 1024 / 2048 sequences
-constexpr int ERRW = MAXBLK * BLKW;                                       // sticky error word behind all counters
+constexpr int NT = DECODE_NT;            // (the counter offsets C1 .. C5, BLKW, MAXBLK and ERRW: decode_plan.h)
 
 struct DArgs {
     int B, steps, H, V, nvt;                         // nvt = ceil(V / 16) output slices
@@ -545,96 +540,77 @@ __global__ __launch_bounds__(NT) void decode_greedy_kernel(const DArgs a) {
     }
 }
 
+// sets the LDS attribute, asks the occupancy query (both once per instance and device) and launches the plan's grid
 template <int MT, bool FORCED>
-int launch_decode(const DArgs& a, int grid, hipStream_t st) {
+int launch_decode(const DArgs& a, const FnDecodePlan& p, hipStream_t st) {
     auto k = decode_greedy_kernel<MT, FORCED>;
     static std::atomic<int> fits[FN_MAX_DEVICES];  // write-once per device (zero-initialised): 1 = at least one workgroup of this kernel fits a CU, -1 = it does not
-    const size_t lds = ((size_t)3 * a.H * 16 + (size_t)4 * MT * 3 * RT) * 4 + 16 + 64 * 4;
     const int dev = fn_device();
     if (dev < 0) return FN_E_UNSUPPORTED;
     if (fits[dev].load(std::memory_order_acquire) == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, DECODE_MAX_LDS);
         if (e != hipSuccess) return (int)e;
         int nb = 0;                                // every role workgroup must be resident (one per CU): ask the occupancy calculator
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), NT, 160 * 1024 - 64);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), NT, DECODE_MAX_LDS);
         if (e != hipSuccess) return (int)e;
         fits[dev].store(nb > 0 ? 1 : -1, std::memory_order_release);   // idempotent: racing threads compute the same value
     }
     if (fits[dev] < 0) return FN_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(p.threads), (size_t)p.lds_bytes, st, a);
     FN_CHECK_LAUNCH();
     return FN_OK;
+}
+
+// the kernel's argument block of a plan: the descriptors' operands, the plan's blocks and replicas, FnDecode.ws carved up as the plan lays it out
+DArgs decode_args(const FnDecode* d, const FnDecodeForce* f, const FnDecodePlan& p) {
+    DArgs a;
+    a.B = d->B; a.steps = d->steps; a.H = d->H; a.V = d->V; a.nvt = p.nvt; a.nblk = p.nblk; a.nrep = p.nrep;
+    a.start_token = d->start_token; a.tok_ld = d->tok_ld;
+    a.w1 = d->w_hh1_frag; a.bhh1 = d->b_hh1; a.bih1 = d->b_ih1; a.table1 = d->table1; a.rowbias1 = d->rowbias1; a.h0 = d->h0;
+    a.wi2 = d->w_ih2_frag; a.bih2 = d->b_ih2; a.w2 = d->w_hh2_frag; a.bhh2 = d->b_hh2;
+    a.wo = d->w_out_frag; a.bo = d->b_out;
+    a.x1 = d->ws + p.x1_off; a.x2 = d->ws + p.x2_off; a.g2 = d->ws + p.g2_off; a.logits = d->ws + p.logits_off;
+    a.tokens = d->tokens; a.logp = d->logp;
+    a.sync = reinterpret_cast<u32*>(d->sync_ws);
+    a.forced = f ? f->forced : nullptr; a.force = f ? f->force : nullptr; a.forced_ld = f ? f->forced_ld : 0;
+    return a;
+}
+
+// fn_decode_greedy (f == nullptr) and fn_decode_forced: the plan's answer, then the launches it describes
+int decode_launch(const FnDecode* d, const FnDecodeForce* f, void* stream) {
+    const FnDecodePlan p = decode_plan(d, f, fn_cu_count());
+    if (p.status != FN_OK) return p.status;
+    const DArgs a = decode_args(d, f, p);
+    hipStream_t st = (hipStream_t)stream;
+    // h0 -> slot 1 of the layer-1 exchange (the operand of step 0), rows padded with zeros
+    int rc = launch_pack(d->h0, d->B, d->H, d->H, a.x1 + (size_t)p.nblk * p.block_rows * d->H, st);
+    if (rc != FN_OK) return rc;
+    hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)ERRW * 4, st);             // counters only: the error word is sticky
+    if (me != hipSuccess) return (int)me;
+    if (f) return p.mt == 1 ? launch_decode<1, true>(a, p, st) : (p.mt == 2 ? launch_decode<2, true>(a, p, st) : launch_decode<4, true>(a, p, st));
+    return p.mt == 1 ? launch_decode<1, false>(a, p, st) : (p.mt == 2 ? launch_decode<2, false>(a, p, st) : launch_decode<4, false>(a, p, st));
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t fn_decode_ws_bytes(int B, int H, int V) {
-    const size_t bp = B <= 16 ? 16 : (size_t)(B + 63) / 64 * 64, vp = (size_t)(V + 15) / 16 * 16;    // rows as the kernel tiles them (blocks of 16 / 32 / 64)
-    return (4 * bp * H + bp * 3 * H + bp * vp) * sizeof(float);
-}
+size_t fn_decode_ws_bytes(int B, int H, int V) { return decode_ws_bytes(B, H, V); }
 
-size_t fn_decode_sync_ws_bytes(void) { return (size_t)(ERRW + 32) * 4; }
+size_t fn_decode_sync_ws_bytes(void) { return decode_sync_ws_bytes(); }
 
-// fn_decode_greedy (f == nullptr) and fn_decode_forced: one set of shape / alignment / eligibility answers
-static int decode_launch(const FnDecode* d, const FnDecodeForce* f, void* stream) {
-    if (!d->w_hh1_frag || !d->b_hh1 || !d->table1 || !d->h0 || !d->w_ih2_frag || !d->w_hh2_frag || !d->b_hh2 || !d->w_out_frag || !d->b_out ||
-        !d->tokens || !d->ws || !d->sync_ws)
-        return FN_E_NULL;
-    if (d->B <= 0 || d->B > MAXBLK * 64 || d->steps <= 0 || d->H <= 0 || (d->H % 32) != 0 || d->H > 512 || d->V <= 0 || d->V > 384 || d->tok_ld < d->steps)
-        return FN_E_SHAPE;
-    const uintptr_t al = (uintptr_t)d->w_hh1_frag | (uintptr_t)d->w_ih2_frag | (uintptr_t)d->w_hh2_frag | (uintptr_t)d->w_out_frag |
-                         (uintptr_t)d->b_hh1 | (uintptr_t)d->b_ih1 | (uintptr_t)d->table1 | (uintptr_t)d->rowbias1 | (uintptr_t)d->h0 |
-                         (uintptr_t)d->b_ih2 | (uintptr_t)d->b_hh2 | (uintptr_t)d->ws;
-    if (al & 15) return FN_E_ALIGN;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return FN_E_SHAPE;
-    const int nsl = d->H / 16, nvt = (d->V + 15) / 16;
-    const int per_rep = 3 * nsl + nvt + 1;
-    if (per_rep > prop.multiProcessorCount) return FN_E_UNSUPPORTED;  // every workgroup must be resident: one per CU
-    hipStream_t st = (hipStream_t)stream;
-    // row tiles per block.  Latency regime (few blocks per replica): a block's time is its hand-over chain, 32-row blocks give the chain
-    // more blocks to overlap.  Throughput regime: a role's busy time per block is ~8.6 k cycles of latency + 6.1 k of MFMA per 32 rows, so
-    // 64-row blocks halve the latency share per row
-    const int mt = d->B <= 16 ? 1 : (d->B >= FN_DECODE_MT4_ROWS ? 4 : 2);
-    const int nblk = (d->B + mt * 16 - 1) / (mt * 16);
-    if (nblk > MAXBLK) return FN_E_SHAPE;
-    int nrep = prop.multiProcessorCount / per_rep;                     // replicas of the role set that fit one workgroup per CU
-    nrep = nrep < nblk ? nrep : nblk;
-    const int grid = nrep * per_rep;
-    const size_t bp = (size_t)nblk * mt * 16, vp = (size_t)nvt * 16;
-    DArgs a;
-    a.B = d->B; a.steps = d->steps; a.H = d->H; a.V = d->V; a.nvt = nvt; a.nblk = nblk; a.nrep = nrep;
-    a.start_token = d->start_token; a.tok_ld = d->tok_ld;
-    a.w1 = d->w_hh1_frag; a.bhh1 = d->b_hh1; a.bih1 = d->b_ih1; a.table1 = d->table1; a.rowbias1 = d->rowbias1; a.h0 = d->h0;
-    a.wi2 = d->w_ih2_frag; a.bih2 = d->b_ih2; a.w2 = d->w_hh2_frag; a.bhh2 = d->b_hh2;
-    a.wo = d->w_out_frag; a.bo = d->b_out;
-    a.x1 = d->ws; a.x2 = a.x1 + 2 * bp * d->H; a.g2 = a.x2 + 2 * bp * d->H; a.logits = a.g2 + bp * 3 * d->H;
-    (void)vp;
-    a.tokens = d->tokens; a.logp = d->logp;
-    a.sync = reinterpret_cast<u32*>(d->sync_ws);
-    a.forced = f ? f->forced : nullptr; a.force = f ? f->force : nullptr; a.forced_ld = f ? f->forced_ld : 0;
-    // h0 -> slot 1 of the layer-1 exchange (the operand of step 0), rows padded with zeros
-    int rc = launch_pack(d->h0, d->B, d->H, d->H, a.x1 + bp * d->H, st);
-    if (rc != FN_OK) return rc;
-    hipError_t me = hipMemsetAsync(a.sync, 0, (size_t)ERRW * 4, st);             // counters only: the error word is sticky
-    if (me != hipSuccess) return (int)me;
-    if (f) return mt == 1 ? launch_decode<1, true>(a, grid, st) : (mt == 2 ? launch_decode<2, true>(a, grid, st) : launch_decode<4, true>(a, grid, st));
-    return mt == 1 ? launch_decode<1, false>(a, grid, st) : (mt == 2 ? launch_decode<2, false>(a, grid, st) : launch_decode<4, false>(a, grid, st));
-}
-
-int fn_decode_greedy(const FnDecode* d, void* stream) {
-    if (!d) return FN_E_NULL;
-    return decode_launch(d, nullptr, stream);
-}
+int fn_decode_greedy(const FnDecode* d, void* stream) { return decode_launch(d, nullptr, stream); }
 
 int fn_decode_forced(const FnDecode* d, const FnDecodeForce* f, void* stream) {
     if (!d || !f) return FN_E_NULL;
-    if (!f->forced || !f->force) return FN_E_NULL;
-    if (f->forced_ld < d->steps) return FN_E_SHAPE;
     return decode_launch(d, f, stream);
+}
+
+int fn_decode_plan(const FnDecode* d, const FnDecodeForce* f, int cus, FnDecodePlan* plan) {
+    if (!plan) return FN_E_NULL;
+    if (cus < 0) return FN_E_SHAPE;
+    *plan = decode_plan(d, f, cus > 0 ? cus : fn_cu_count());
+    return FN_OK;
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 //     contiguous 256-byte run (see gate_off).
 #include <cstdio>
 
+#include "decode_plan.h"
 #include "gru_layout.h"
 #include "x6w_core.h"
 
@@ -1674,26 +1675,29 @@ int fn_gru_cell_plan(const FnGruCell* c, FnGruCellPlan* plan) {
 }
 
 int fn_out_argmax_f32(const float* h, int ldh, const float* W, int ldw, const float* bias, int B, int V, int K, uint64_t* best, void* stream) {
-    if (!h || !W || !bias || !best) return FN_E_NULL;
-    if (B <= 0 || V <= 0 || K <= 0 || (K % 16) != 0 || ldh < K || ldw < K || (ldh & 3) || (ldw & 3)) return FN_E_SHAPE;
-    if ((long)B * ldh * 4 >= (1L << 32) || (long)V * ldw * 4 >= (1L << 32)) return FN_E_SHAPE;
-    if (((((uintptr_t)h) | ((uintptr_t)W)) & 15) || (((uintptr_t)best) & 7)) return FN_E_ALIGN;
-    const size_t lds = (size_t)48 * K * sizeof(float);
-    if (lds <= (size_t)128 * 1024) {          // weight slice of a workgroup resident in LDS
-        const bool eight = (K % 32) == 0;
-        auto k = eight ? out_argmax_lds8_kernel<4> : out_argmax_lds_kernel<8>;
-        if (const int rc = eight ? fn_set_max_lds<out_argmax_lds8_kernel<4>>(144 * 1024, FN_E_SHAPE) : fn_set_max_lds<out_argmax_lds_kernel<8>>(144 * 1024, FN_E_SHAPE))
-            return rc;
-        const int grid = ((B + 63) / 64) * ((V + 47) / 48);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(eight ? 2 * NT : NT), lds + (eight ? 4 * 3 * 64 * 16 : 0), (hipStream_t)stream, h, (long)ldh, W, (long)ldw, bias, B, V, K,
-                           reinterpret_cast<unsigned long long*>(best));
-        FN_CHECK_LAUNCH();
-        return FN_OK;
+    const FnOutArgmaxPlan p = out_argmax_plan(h, ldh, W, ldw, bias, B, V, K, best);
+    if (p.status != FN_OK) return p.status;
+    unsigned long long* const out = reinterpret_cast<unsigned long long*>(best);
+    hipStream_t st = (hipStream_t)stream;
+    switch (p.kernel) {
+        case FN_OUT_ARGMAX_LDS8:
+            if (const int rc = fn_set_max_lds<out_argmax_lds8_kernel<4>>(144 * 1024, FN_E_SHAPE)) return rc;
+            hipLaunchKernelGGL((out_argmax_lds8_kernel<4>), dim3(p.grid), dim3(p.threads), (size_t)p.lds_bytes, st, h, (long)ldh, W, (long)ldw, bias, B, V, K, out);
+            break;
+        case FN_OUT_ARGMAX_LDS:
+            if (const int rc = fn_set_max_lds<out_argmax_lds_kernel<8>>(144 * 1024, FN_E_SHAPE)) return rc;
+            hipLaunchKernelGGL((out_argmax_lds_kernel<8>), dim3(p.grid), dim3(p.threads), (size_t)p.lds_bytes, st, h, (long)ldh, W, (long)ldw, bias, B, V, K, out);
+            break;
+        default:
+            hipLaunchKernelGGL((out_argmax_direct_kernel<4>), dim3(p.grid), dim3(p.threads), 0, st, h, (long)ldh, W, (long)ldw, bias, B, V, K, out);
     }
-    const int grid = ((B + 31) / 32) * ((V + 95) / 96);
-    hipLaunchKernelGGL((out_argmax_direct_kernel<4>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, h, (long)ldh, W, (long)ldw, bias, B, V, K,
-                       reinterpret_cast<unsigned long long*>(best));
     FN_CHECK_LAUNCH();
+    return FN_OK;
+}
+
+int fn_out_argmax_plan(const float* h, int ldh, const float* W, int ldw, const float* bias, int B, int V, int K, const uint64_t* best, FnOutArgmaxPlan* plan) {
+    if (!plan) return FN_E_NULL;
+    *plan = out_argmax_plan(h, ldh, W, ldw, bias, B, V, K, best);
     return FN_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../../include/fadernets_host.h"
+#include "../decode_plan.h"
 #include "sample_host.h"
 #include "constrain_host.h"
 #include "notes_host.h"
@@ -539,8 +540,8 @@ int fn_gru_cell_f32_host(const FnGruCell* c, void*) {
 }
 
 int fn_out_argmax_f32_host(const float* h, int ldh, const float* W, int ldw, const float* bias, int B, int V, int K, uint64_t* best, void*) {
-    if (!h || !W || !bias || !best) return FN_E_NULL;
-    if (B <= 0 || V <= 0 || K <= 0 || (K % 16) != 0 || ldh < K || ldw < K || (ldh & 3) || (ldw & 3)) return FN_E_SHAPE;
+    // the device's NULL and shape clauses; not its 4 GB span and alignment answers: the twin indexes with 64 bits and moves no vectors
+    if (const int rc = out_argmax_members_validate(h, ldh, W, ldw, bias, B, V, K, best)) return rc;
     for (int b = 0; b < B; ++b)
         for (int v = 0; v < V; ++v) {
             float a = 0.0f;
@@ -607,10 +608,9 @@ size_t fn_decode_sync_ws_bytes_host(void) { return 16; }
 
 // fn_decode_greedy_host (f == nullptr) and fn_decode_forced_host
 static int decode_host(const FnDecode* d, const FnDecodeForce* f) {
-    if (!d->w_hh1_frag || !d->b_hh1 || !d->table1 || !d->h0 || !d->w_ih2_frag || !d->w_hh2_frag || !d->b_hh2 || !d->w_out_frag || !d->b_out ||
-        !d->tokens || !d->ws || !d->sync_ws)
-        return FN_E_NULL;
-    if (d->B <= 0 || d->B > 2048 || d->steps <= 0 || d->H <= 0 || d->H > 512 || (d->H % 32) != 0 || d->V <= 0 || d->tok_ld < d->steps) return FN_E_SHAPE;
+    // the device's NULL and shape clauses; not its V <= 384 and alignment answers (no lanes, no vectors here), and one clause of the twin's own: it
+    // indexes the table with start_token, which the device leaves to the caller
+    if (const int rc = decode_members_validate(d)) return rc;
     if (d->start_token < 0 || d->start_token >= d->V) return FN_E_SHAPE;
     const int B = d->B, H = d->H, V = d->V;
     const std::vector<float> Whh1 = unfrag(d->w_hh1_frag, 3 * H, H), Wih2 = unfrag(d->w_ih2_frag, 3 * H, H), Whh2 = unfrag(d->w_hh2_frag, 3 * H, H),
@@ -679,8 +679,7 @@ int fn_decode_greedy_host(const FnDecode* d, void*) {
 
 int fn_decode_forced_host(const FnDecode* d, const FnDecodeForce* f, void*) {
     if (!d || !f) return FN_E_NULL;
-    if (!f->forced || !f->force) return FN_E_NULL;
-    if (f->forced_ld < d->steps) return FN_E_SHAPE;
+    if (const int rc = decode_force_validate(d, f)) return rc;
     return decode_host(d, f);
 }
 

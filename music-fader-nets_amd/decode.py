@@ -204,7 +204,7 @@ def greedy_decode(model, z, steps, want_logp=True, use_graph=None, forced=None, 
         return (logp, tokens, constraint_stats(cb)) if con is not None and con.want_stats else (logp, tokens)
     # the captured launches depend on the path taken, on the cells' / GEMMs' arithmetic switches, on the form of the constraints and - the per-token
     # paths pick every step's token pointer on the host - on the mask; the unmasked graphs are bounded by the shapes in use
-    key = (z.shape[0], steps, bool(want_logp), z.shape[0] >= eng.cell_decode_rows, bool(getattr(eng, "fused_argmax", True)), *_arith_key(eng),
+    key = (z.shape[0], steps, bool(want_logp), decode_path(eng, z.shape[0], want_logp, None, con), *_arith_key(eng),
            None if con is None else con.key(), mask)
     out, cb = _graph_replay(eng, eng.__dict__.setdefault("_decode_graphs", {}), key, lambda: _token_buffers(z, steps, want_logp, forced, con=con),
                             lambda b, warm: _decode_body(eng, b["zs"], min(steps, 2) if warm else steps, want_logp, b["logp"], b["tokens"],
@@ -285,7 +285,7 @@ def sample_decode(model, z, steps, temperature=1.0, top_k=0, top_p=1.0, seed=0, 
         cb = None if con is None else constraint_buffers(con, z.shape[0], z.device)
         logp, tokens = _decode_body(eng, z, steps, want_logp, None, None, forced=forced, mask=mask, sample=params.to(z.device), con=cb)
     else:
-        key = (z.shape[0], steps, bool(want_logp), P, z.shape[0] >= eng.cell_decode_rows, None if con is None else con.key(), *_arith_key(eng))
+        key = (z.shape[0], steps, bool(want_logp), P, decode_path(eng, z.shape[0], want_logp, params, con), None if con is None else con.key(), *_arith_key(eng))
         out, cb = _graph_replay(eng, eng.__dict__.setdefault("_sample_graphs", {}), key, lambda: _token_buffers(z, steps, want_logp, forced, params, con),
                                 lambda b, warm: _decode_body(eng, b["zs"], min(steps, 2) if warm else steps, want_logp, b["logp"], b["tokens"],
                                                              alloc_steps=steps, forced=b["fs"], mask=mask, sample=b["ps"], con=b["cb"]),
@@ -420,19 +420,45 @@ def _single_launch_ok(eng, z):
             and eng.H <= 512 and eng.single_launch_decode)
 
 
+def decode_path(eng, Bi, want_logp, sample, con):
+    """the per-token path _decode_body takes for Bi sequences: "scan_steps" (below Engine.cell_decode_rows: scan-step kernels + projection GEMM),
+    "cells" (fn_gru_cell_f32 cells, output GEMM, a head launch) or "cells_fused" (the cells with the argmax in the output layer's epilogue,
+    fn_out_argmax_f32: tokens only, no sampling, no constraints).  sample / con: None or not, as _decode_body takes them."""
+    if Bi < eng.cell_decode_rows:
+        return "scan_steps"
+    fused = not want_logp and sample is None and con is None and getattr(eng, "fused_argmax", True) and hasattr(eng.ops, "out_argmax")
+    return "cells_fused" if fused else "cells"
+
+
+def _single_launch_args(eng, h0g, rbg, steps, tokens, logp, forced=None, mask=None):
+    """the arguments of HipOps.decode_greedy / decode_plan on the initial state h0g and layer 1's row bias rbg (_init_state)"""
+    P = eng.p
+    # forced feedback (fn_decode_forced): the mask travels as device bytes, the kernel reads it step by step
+    fkw = {} if mask is None else dict(forced=forced, force=torch.tensor(mask, dtype=torch.uint8).to(tokens.device))
+    return (h0g.shape[0], steps, eng.H, E_VOCAB, E_VOCAB - 1, eng.whh_f["g"], P["grucell_g.bias_hh"], P["grucell_g.bias_ih"], eng.tab["g"], rbg, h0g,
+            eng.packs["ih2"], P["grucell_g_2.bias_ih"], eng.whh_f["g2"], P["grucell_g_2.bias_hh"], eng.packs["out"], P["linear_out_g.bias"], tokens,
+            logp), fkw
+
+
+def single_launch_plan(eng, Bi, steps, want_logp=True, forced=None, mask=None):
+    """what the one-launch decode of Bi sequences launches on this engine (HipOps.decode_plan on the arguments _decode_single_launch hands to
+    decode_greedy; the state buffers are the ones _init_state fills, unfilled), or None where it is not eligible on this device.  Nothing is enqueued."""
+    tokens = torch.zeros(Bi, steps, dtype=torch.int32, device=eng.dev)
+    logp = torch.empty(Bi, steps, E_VOCAB, device=eng.dev) if want_logp else None
+    args, fkw = _single_launch_args(eng, eng.buf("dec_h0g", (Bi, eng.H)), eng.buf("dec_rbg", (Bi, 3 * eng.H)), steps, tokens, logp, forced, mask)
+    return eng.ops.decode_plan(*args, **fkw)
+
+
 def _decode_single_launch(eng, z, steps, want_logp, forced=None, mask=None):
     """None when the library reports the configuration as not eligible (e.g. fewer CUs than role workgroups) or the launch
     timed out waiting for a hand-over: the caller then takes the per-token path."""
-    ops, P, H = eng.ops, eng.p, eng.H
+    ops = eng.ops
     Bi = z.shape[0]
     h0g, rbg = _init_state(eng, z, "dec_")
     tokens = torch.zeros(Bi, steps, dtype=torch.int32, device=z.device)
     logp = torch.empty(Bi, steps, E_VOCAB, device=z.device) if want_logp else None
-    # forced feedback (fn_decode_forced): the mask travels as device bytes, the kernel reads it step by step
-    fkw = {} if mask is None else dict(forced=forced, force=torch.tensor(mask, dtype=torch.uint8).to(z.device))
-    ok = ops.decode_greedy(Bi, steps, H, E_VOCAB, E_VOCAB - 1, eng.whh_f["g"], P["grucell_g.bias_hh"], P["grucell_g.bias_ih"], eng.tab["g"], rbg, h0g,
-                           eng.packs["ih2"], P["grucell_g_2.bias_ih"], eng.whh_f["g2"], P["grucell_g_2.bias_hh"], eng.packs["out"],
-                           P["linear_out_g.bias"], tokens, logp, **fkw)
+    args, fkw = _single_launch_args(eng, h0g, rbg, steps, tokens, logp, forced, mask)
+    ok = ops.decode_greedy(*args, **fkw)
     if not ok:
         return None
     if ops.gru_sync_error(clear=True):           # bounded spin gave up (another kernel held the CUs): results are garbage
@@ -486,13 +512,14 @@ def _decode_body(eng, z, steps, want_logp, logp, tokens, alloc_steps=None, force
         elif held is not None:
             ops.constrain_advance(tokens[:, i], E_VOCAB, con["params"], held_in=held, held_out=held)
 
-    if Bi >= eng.cell_decode_rows:
+    path = decode_path(eng, Bi, want_logp, sample, con)
+    if path != "scan_steps":
         # thousands of rows: every cell is ONE MFMA launch with the gates in its epilogue (fn_gru_cell_f32: LDS-free loop above 512 rows); layer 2 takes its input
         # projection in the same K loop - 3 launches + argmax per token instead of 4 + argmax, and no [B][3H] round trip
         # tokens only (the evaluators' sweeps): the output layer takes the argmax into its epilogue (fn_out_argmax_f32: packed (logit, column)
         # words by 64-bit atomic max, no logits, no argmax launch) and the next layer-1 cell reads its token from the packed word -
         # 3 launches per token; the int32 tokens are unpacked once at the end
-        fused = not want_logp and sample is None and con is None and getattr(eng, "fused_argmax", True) and hasattr(ops, "out_argmax")
+        fused = path == "cells_fused"
         best = eng.buf("dec_best", (max(steps, alloc_steps or 0), Bi), dtype=torch.int64)[:steps] if fused else None
         if fused:
             best.zero_()

@@ -416,12 +416,24 @@ class HipOps:
 
     def out_argmax(self, h, W, bias, best):
         """fn_out_argmax_f32: best[b] = max(best[b], packed (logit, column) words of h[b] W^T + bias) - best: a ZEROED contiguous [B] int64 row"""
+        _lib.check(self.lib.fn_out_argmax_f32(*self._out_argmax_args(h, W, bias, best), self.stream()), "fn_out_argmax_f32")
+
+    def out_argmax_plan(self, h, W, bias, best):
+        """what out_argmax() with these arguments launches (fn_out_argmax_plan on the same prepared arguments): dict(kernel, grid, threads, lds_bytes).
+        Nothing is enqueued."""
+        plan = _lib.FnOutArgmaxPlan()
+        _lib.check(self.lib.fn_out_argmax_plan(*self._out_argmax_args(h, W, bias, best), C.byref(plan)), "fn_out_argmax_plan")
+        _lib.check(plan.status, "fn_out_argmax_plan")
+        return plan.as_dict()
+
+    def _out_argmax_args(self, h, W, bias, best):
+        """the arguments of fn_out_argmax_f32 / fn_out_argmax_plan in front of the stream / the plan"""
         ph, B, K, ldh = _mat(h, "h")
         pw, V, Kw, ldw = _mat(W, "W")
         _dense(bias, name="bias")
         if Kw != K or bias.numel() != V or best.dtype != torch.int64 or best.dim() != 1 or best.shape[0] != B or not best.is_contiguous():
             raise RuntimeError("out_argmax shape mismatch h%s W%s best%s" % (tuple(h.shape), tuple(W.shape), tuple(best.shape)))
-        _lib.check(self.lib.fn_out_argmax_f32(ph, ldh, pw, ldw, _p(bias), B, V, K, best.data_ptr(), self.stream()), "fn_out_argmax_f32")
+        return ph, ldh, pw, ldw, _p(bias), B, V, K, best.data_ptr()
 
     def best_tokens(self, best, V, tokens):
         """fn_best_tokens: best [steps][B] int64 packed words -> tokens [B][steps] int32 (row stride tokens.stride(0))"""
@@ -528,6 +540,34 @@ class HipOps:
                       w_out_frag, b_out, tokens, logp=None, forced=None, force=None):
         """single-launch greedy decode of <= 2048 sequences (fn_decode_greedy); tokens int32 [B][>=steps], logp [B][steps][V] or None.
         forced int32 [B][>=steps] + force uint8 [steps] on the device: fn_decode_forced (forced[b][i] is fed after step i where force[i])"""
+        d, f = self._decode_args(B, steps, H, V, start_token, w_hh1_frag, b_hh1, b_ih1, table1, rowbias1, h0, w_ih2_frag, b_ih2, w_hh2_frag, b_hh2,
+                                 w_out_frag, b_out, tokens, logp, forced, force)
+        if f is not None:
+            rc, what = self.lib.fn_decode_forced(C.byref(d), C.byref(f), self.stream()), "fn_decode_forced"
+        else:
+            rc, what = self.lib.fn_decode_greedy(C.byref(d), self.stream()), "fn_decode_greedy"
+        if rc == _lib.FN_E_UNSUPPORTED:            # not eligible on this device (needs one CU per role workgroup)
+            return False
+        _lib.check(rc, what)
+        return True
+
+    def decode_plan(self, B, steps, H, V, start_token, w_hh1_frag, b_hh1, b_ih1, table1, rowbias1, h0, w_ih2_frag, b_ih2, w_hh2_frag, b_hh2,
+                    w_out_frag, b_out, tokens, logp=None, forced=None, force=None):
+        """what decode_greedy() with these arguments launches (fn_decode_plan on the same prepared descriptors, this device's compute units):
+        dict(forced, mt, block_rows, nblk, nvt, nslices, per_rep, nrep, grid, threads, lds_bytes, the workspace offsets), or None where decode_greedy
+        returns False (not eligible on this device).  Nothing is enqueued."""
+        d, f = self._decode_args(B, steps, H, V, start_token, w_hh1_frag, b_hh1, b_ih1, table1, rowbias1, h0, w_ih2_frag, b_ih2, w_hh2_frag, b_hh2,
+                                 w_out_frag, b_out, tokens, logp, forced, force)
+        plan = _lib.FnDecodePlan()
+        _lib.check(self.lib.fn_decode_plan(C.byref(d), None if f is None else C.byref(f), 0, C.byref(plan)), "fn_decode_plan")
+        if plan.status == _lib.FN_E_UNSUPPORTED:
+            return None
+        _lib.check(plan.status, "fn_decode_plan")
+        return plan.as_dict()
+
+    def _decode_args(self, B, steps, H, V, start_token, w_hh1_frag, b_hh1, b_ih1, table1, rowbias1, h0, w_ih2_frag, b_ih2, w_hh2_frag, b_hh2,
+                     w_out_frag, b_out, tokens, logp, forced, force):
+        """the descriptors of fn_decode_greedy / fn_decode_forced / fn_decode_plan: (FnDecode, FnDecodeForce or None)"""
         d = _lib.FnDecode()
         for t, nm in ((w_hh1_frag, "w_hh1_frag"), (b_hh1, "b_hh1"), (b_ih1, "b_ih1"), (table1, "table1"), (rowbias1, "rowbias1"), (h0, "h0"),
                       (w_ih2_frag, "w_ih2_frag"), (b_ih2, "b_ih2"), (w_hh2_frag, "w_hh2_frag"), (b_hh2, "b_hh2"), (w_out_frag, "w_out_frag"),
@@ -544,21 +584,16 @@ class HipOps:
         if key not in syncs:
             syncs[key] = torch.zeros(int(self.lib.fn_decode_sync_ws_bytes()) // 4, dtype=torch.int32, device=self.device)
         d.sync_ws = _p(syncs[key])
-        if forced is not None or force is not None:
-            if forced is None or force is None:
-                raise RuntimeError("decode_greedy: forced and force go together")
-            _dense(forced, torch.int32, "forced"), _dense(force, torch.uint8, "force")
-            if forced.shape[0] != B or forced.shape[1] < steps or force.numel() < steps:
-                raise RuntimeError("decode_greedy: forced [B][>=steps] and force [steps] expected")
-            f = _lib.FnDecodeForce()
-            f.forced, f.forced_ld, f.force = _p(forced), forced.shape[1], _p(force)
-            rc, what = self.lib.fn_decode_forced(C.byref(d), C.byref(f), self.stream()), "fn_decode_forced"
-        else:
-            rc, what = self.lib.fn_decode_greedy(C.byref(d), self.stream()), "fn_decode_greedy"
-        if rc == _lib.FN_E_UNSUPPORTED:            # not eligible on this device (needs one CU per role workgroup)
-            return False
-        _lib.check(rc, what)
-        return True
+        if forced is None and force is None:
+            return d, None
+        if forced is None or force is None:
+            raise RuntimeError("decode_greedy: forced and force go together")
+        _dense(forced, torch.int32, "forced"), _dense(force, torch.uint8, "force")
+        if forced.shape[0] != B or forced.shape[1] < steps or force.numel() < steps:
+            raise RuntimeError("decode_greedy: forced [B][>=steps] and force [steps] expected")
+        f = _lib.FnDecodeForce()
+        f.forced, f.forced_ld, f.force = _p(forced), forced.shape[1], _p(force)
+        return d, f
 
     def embed_grad(self, dgx_all, idx, idx_shift, start_token, reverse, V, out):
         _dense(dgx_all, name="dgx_all"), _dense(idx, torch.int32, "idx"), _dense(out, name="out")

@@ -280,6 +280,9 @@ REPLAY_CASES = [
     ("pipeline32", "trained64", 40, 300),
 ]
 REPLAY_GRAPH_PATHS = ("scan_steps", "cells_f32", "cells_x6")
+# the row blocks of the one-launch kernel a case's name stands for: (rows of a block, blocks) of Bi sequences - one block of 16 or 32 rows, a pipeline of
+# 32-row blocks, a pipeline of 64-row blocks; compared with what the library plans for the case's tensors (fn_decode_plan)
+ONE_LAUNCH_BLOCKS = {"one_launch": lambda Bi: (16 if Bi <= 16 else 32, 1), "pipeline32": lambda Bi: (32, -(-Bi // 32)), "pipeline64": lambda Bi: (64, -(-Bi // 64))}
 REPLAY_OUT_SCALE = 8.0     # linear_out_g.weight x 8: wider logit spreads, fewer near-ties (seeded H=512: 1.8 % of the gaps below 2e-4 -> 0.4 %)
 
 

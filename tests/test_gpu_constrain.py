@@ -114,7 +114,10 @@ def _other(pkg, con, Bi):
 def test_constrained_decode_end_to_end(mode, path, Bi):
     pkg = load_package()
     m, eng, sd, Z = _model(pkg, 64 if path == "cells" else None)
-    assert (Bi >= eng.cell_decode_rows) == (path == "cells")
+    from music_fader_nets_amd import decode as dec
+    # a constrained decode never takes the fused output layer: with and without log-probs, greedy or sampled, it is the path of the case's name
+    for want_logp in (True, False):
+        assert dec.decode_path(eng, Bi, want_logp, None if mode == "greedy" else object(), object()) == path
     z = replay_z(Bi, Z, Bi)
     zd = z.to(DEV)
     rows = replay_rows(Bi)

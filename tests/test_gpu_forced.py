@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import make_model, replay_inputs, replay_z
+from helpers import ONE_LAUNCH_BLOCKS, make_model, replay_inputs, replay_z
 from helpers_forced import (FORCED_CASES, FORCED_GRAPH_PATHS, FORCED_MASKS, fed_stream, forced_line, forced_mask, forced_tokens,
                             replay_forced_check)
 from mfn_import import load_package
@@ -22,6 +22,7 @@ def _arith_tag(eng):
 @pytest.mark.parametrize("path,weights,Bi,steps", FORCED_CASES, ids=["%s-%s-%d" % (p, w, b) for p, w, b, _ in FORCED_CASES])
 def test_forced_decode_paths_every_step_vs_fp64_replay(path, weights, Bi, steps):
     pkg = load_package()
+    from music_fader_nets_amd import decode as dec
     H, Z, sd = replay_inputs(weights)
     m = make_model(H, Z, sd, device=DEV, arith="bf16x6" if path == "cells_x6" else None)
     m.eval()
@@ -31,12 +32,17 @@ def test_forced_decode_paths_every_step_vs_fp64_replay(path, weights, Bi, steps)
         eng.single_launch_decode, eng.single_launch_skip = True, (0, -1)
         if Bi > eng.single_launch_rows:
             eng.single_launch_rows = 2048
-        assert (Bi <= 32) == (path == "one_launch") and (Bi >= 353) == (path == "pipeline64")
+        # what the library launches for this engine's own tensors (fn_decode_plan, forced and not) is what the case's name says
+        for fkw in ({}, dict(forced=forced_tokens(Bi, steps, Bi).to(device=DEV, dtype=torch.int32), mask=(True,) * steps)):
+            plan = dec.single_launch_plan(eng, Bi, steps, **fkw)
+            assert plan is not None and dec._single_launch_ok(eng, torch.empty(Bi, 1, device=DEV)) and plan["forced"] == bool(fkw)
+            assert (plan["block_rows"], plan["nblk"]) == ONE_LAUNCH_BLOCKS[path](Bi) and (plan["nblk"] == 1) == (path == "one_launch"), (path, Bi, plan)
     elif path == "scan_steps":
         eng.single_launch_decode, eng.cell_decode_rows = False, 1 << 30
+        assert dec.decode_path(eng, Bi, True, None, None) == "scan_steps" and dec.decode_path(eng, Bi, False, None, None) == "scan_steps"
     else:
         eng.single_launch_decode = False
-        assert Bi >= eng.cell_decode_rows
+        assert dec.decode_path(eng, Bi, True, None, None) == "cells" and dec.decode_path(eng, Bi, False, None, None) == "cells_fused"
         x6 = eng.ops.dw_x6 and eng.ops.cell_x6 and Bi >= eng.ops.cell_x6_rows
         assert x6 == (path == "cells_x6")
     sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
@@ -84,7 +90,6 @@ def test_forced_decode_paths_every_step_vs_fp64_replay(path, weights, Bi, steps)
     n = len(graphs)
     lp, tk = decode(zd, True, forced=forced, force=force2)
     if not one_launch:                                        # a graph of its own, and the cache of masked graphs stays capped
-        from music_fader_nets_amd import decode as dec
         want = tuple(bool(x) for x in force2[:-1]) + (False,)
         assert any(k[-1] == want for k in graphs) and sum(k[-1] is not None for k in graphs) <= dec.MAX_MASKED_GRAPHS
     st = replay_forced_check(sd, z, tk, forced, force2, fed_stream(tk, forced, force2), lp)

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from fake_ops import FakeOps
-from helpers import (NOISE_PARAMS, REPLAY_CASES, REPLAY_GRAPH_PATHS, SCAN_CASES, PlanRecorder, _unblock_gates, _ws_scans, batch_of, check_scan_vs_f64, chosen_kernels,
+from helpers import (NOISE_PARAMS, ONE_LAUNCH_BLOCKS, REPLAY_CASES, REPLAY_GRAPH_PATHS, SCAN_CASES, PlanRecorder, _unblock_gates, _ws_scans, batch_of, check_scan_vs_f64, chosen_kernels,
                      grad_tolerances, load_golden,
                      make_model, oracle_grads_f64, relerr, replay_decode_check, replay_inputs, replay_line, replay_z, run_scans, scan_inputs, scan_kernel_names,
                      scan_lines, sd_from)
@@ -1692,6 +1692,16 @@ def test_single_launch_decode_block_pipeline(H, Bi, steps):
     eng.single_launch_decode, eng.cell_decode_rows = False, 1 << 30
     lp0, tk0 = pkg.greedy_decode(m, z, steps)
     eng.single_launch_decode, eng.single_launch_rows, eng.single_launch_skip = True, 2048, (0, -1)       # force the one-launch pipeline whatever the default thresholds
+    # what the docstring claims, from the library's plan for these tensors (fn_decode_plan on this device's compute units)
+    from music_fader_nets_amd import decode as dec
+    plan = dec.single_launch_plan(eng, Bi, steps)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows = 64 if Bi >= 353 else 32
+    assert plan is not None and plan["block_rows"] == rows and plan["nblk"] == -(-Bi // rows) and plan["nblk"] > 1, plan
+    assert plan["per_rep"] == 3 * (H // 16) + 22 + 1 and plan["nrep"] == min(cus // plan["per_rep"], plan["nblk"]), (cus, plan)
+    assert plan["nrep"] == (2 if H == 512 else min(7, plan["nblk"])) and plan["grid"] == plan["nrep"] * plan["per_rep"] <= cus, (cus, plan)      # 256 compute units
+    assert Bi - (plan["nblk"] - 1) * rows == {45: 13, 64: 32, 256: 32, 400: 16, 800: 32, 1024: 64, 1500: 28}[Bi]                                 # rows of the last block
+    assert -(-plan["nblk"] // plan["nrep"]) == {45: 1, 64: 1, 256: 4, 400: 4, 800: 7, 1024: 3, 1500: 12}[Bi]                                      # blocks per replica
     lp1, tk1 = pkg.greedy_decode(m, z, steps)
     lp2, tk2 = pkg.greedy_decode(m, z, steps)
     assert not eng.ops.gru_sync_error()
@@ -1749,6 +1759,12 @@ def test_out_argmax_packed_words(ops, B, V, K):
     bias[V - 1] = bias[3]                                   # an exact tie between columns 3 and V - 1 in every row
     ref = h.double() @ W.double().t() + bias.double()
     best = torch.zeros(2, B, dtype=torch.int64, device=DEV)
+    # the kernel this K stands for in the table, from the library's plan for these tensors (fn_out_argmax_plan)
+    plan = ops.out_argmax_plan(g(h), g(W), g(bias), best[0])
+    want = {512: "out_argmax_lds8_kernel<4>", 64: "out_argmax_lds8_kernel<4>", 32: "out_argmax_lds8_kernel<4>", 48: "out_argmax_lds_kernel<8>",
+            112: "out_argmax_lds_kernel<8>", 16: "out_argmax_lds_kernel<8>", 80: "out_argmax_lds_kernel<8>", 1024: "out_argmax_direct_kernel<4>"}[K]
+    assert plan["kernel"] == want and plan["threads"] == (512 if "lds8" in want else 256), plan
+    assert plan["grid"] == (-(-B // 32) * -(-V // 96) if "direct" in want else -(-B // 64) * -(-V // 48)), plan
     ops.out_argmax(g(h), g(W), g(bias), best[0])
     best[1].fill_(-1)                                       # the all-ones word is above every packed logit and stays
     best[1, : B // 2] = 0
@@ -1851,6 +1867,7 @@ def test_decode_paths_every_step_vs_fp64_replay(path, weights, Bi, steps):
     the graph paths replay their cached graph on a second latent batch, which must pass as well (nothing of the first call baked in).
     Weights: seeded with the output layer x 8 (fewer near-ties), or the trained H = 64 weights of epoch.npz."""
     pkg = load_package()
+    from music_fader_nets_amd import decode as dec
     H, Z, sd = replay_inputs(weights)
     m = make_model(H, Z, sd, device=DEV, arith="bf16x6" if path == "cells_x6" else None)
     m.eval()
@@ -1860,12 +1877,17 @@ def test_decode_paths_every_step_vs_fp64_replay(path, weights, Bi, steps):
         eng.single_launch_decode, eng.single_launch_skip = True, (0, -1)
         if Bi > eng.single_launch_rows:
             eng.single_launch_rows = 2048
-        assert (Bi <= 32) == (path == "one_launch") and (Bi >= 353) == (path == "pipeline64")
+        # what the library launches for this engine's own tensors (fn_decode_plan) is what the case's name says
+        for want_logp in (True, False):
+            plan = dec.single_launch_plan(eng, Bi, steps, want_logp)
+            assert plan is not None and dec._single_launch_ok(eng, torch.empty(Bi, 1, device=DEV)) and not plan["forced"]
+            assert (plan["block_rows"], plan["nblk"]) == ONE_LAUNCH_BLOCKS[path](Bi) and (plan["nblk"] == 1) == (path == "one_launch"), (path, Bi, plan)
     elif path == "scan_steps":
         eng.single_launch_decode, eng.cell_decode_rows = False, 1 << 30
+        assert dec.decode_path(eng, Bi, True, None, None) == "scan_steps" and dec.decode_path(eng, Bi, False, None, None) == "scan_steps"
     else:
         eng.single_launch_decode = False
-        assert Bi >= eng.cell_decode_rows
+        assert dec.decode_path(eng, Bi, True, None, None) == "cells" and dec.decode_path(eng, Bi, False, None, None) == "cells_fused"
         x6 = eng.ops.dw_x6 and eng.ops.cell_x6 and Bi >= eng.ops.cell_x6_rows
         assert x6 == (path == "cells_x6")
     sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}

@@ -69,10 +69,13 @@ def test_sample_decode_paths_every_step_vs_fp64_replay(path, weights, Bi, steps)
     m.eval()
     eng = m.engine()
     eng.single_launch_decode = False
+    from music_fader_nets_amd import decode as dec
+    sampling = torch.zeros(32, dtype=torch.uint8)             # decode_path asks whether there are sampling parameters, not what they hold
     if path == "scan_steps":
         eng.cell_decode_rows = 1 << 30
+        assert dec.decode_path(eng, Bi, True, sampling, None) == "scan_steps"
     else:
-        assert Bi >= eng.cell_decode_rows
+        assert dec.decode_path(eng, Bi, True, sampling, None) == "cells" and dec.decode_path(eng, Bi, False, sampling, None) == "cells"
         x6 = eng.ops.dw_x6 and eng.ops.cell_x6 and Bi >= eng.ops.cell_x6_rows
         assert x6 == (path == "cells_x6")
     sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}

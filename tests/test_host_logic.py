@@ -469,6 +469,24 @@ def test_gru_plan_invariants_under_sanitizers(tmp_path):
     assert "FINDING" not in p.stdout and p.stdout.strip().endswith("49 return codes, 3400000 plans, 0 findings"), p.stdout[-2000:]
 
 
+def test_decode_plan_invariants_under_sanitizers(tmp_path):
+    """csrc/decode_plan.h (the one place that decides what fn_decode_greedy / fn_decode_forced / fn_out_argmax_f32 launch) compiled for the host
+    (csrc/host/decode_plan_check.cpp, a stand-alone program, nothing preloaded): the table of return codes, a literal table of plans, and over
+    B 1 .. 2049, H, V, compute units, forced or not every plan's grid is replicas x role set within one workgroup per compute unit, its blocks cover B
+    within the counters, LDS fits, the four workspace regions are disjoint and end inside fn_decode_ws_bytes; the output layer's kernel by K, grid and
+    LDS - 0 findings."""
+    import subprocess
+    asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    if not os.path.isabs(asan) or not os.path.exists(asan):
+        pytest.skip("no AddressSanitizer runtime on this box (gcc -print-file-name=libasan.so)")
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "music-fader-nets_amd", "csrc", "host", "decode_plan_check.cpp")
+    exe = str(tmp_path / "decode_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-Wall", "-Werror", src, "-o", exe], check=True, capture_output=True, timeout=300)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, (p.stdout[-2000:], p.stderr[-3000:])
+    assert "FINDING" not in p.stdout and p.stdout.strip().endswith("138 return codes and table entries, 1056510 plans, 0 findings"), p.stdout[-2000:]
+
+
 def test_fake_ops_do_not_read_an_output_they_overwrite():
     """beta == 0 means the output is write-only, as in the kernels (gemm.hip: `if (beta != 0.f)`): the engine hands over uninitialised
     buffers, and 0 x NaN is NaN.  (FakeOps.gru_dwhh once formed beta * dW: the gradient comparison above failed whenever the allocator
