@@ -1057,6 +1057,87 @@ int fn_iw_reduce(const float* nll_tb, int T, int64_t nll_ld,           /* nll of
                  int B, int S, double* lw, double* out, int out_ld, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Latent disentanglement report (disentangle.py): which posterior dimension holds which attribute - mutual information gap (Chen et al.), separated
+ * attribute predictability (Kumar et al.), modularity (Ridgeway & Mozer), the R^2 interpretability score (Adel et al.) and Spearman's rho - from six
+ * kernels over a code matrix and a factor matrix.  OURS: the reference's run_through_gmm copies every batch to the host and stops there.  The text
+ * below is the specification; csrc/host/disentangle_host.h has the argument checks (shared with the device entry points) and the host twins.  The six
+ * entry points are additive: fn_version() stays 6.
+ *
+ * Limits: 1 <= N <= FN_DIS_MAX_N rows, 1 <= P <= FN_DIS_MAX_D columns, 1 <= Q, A <= FN_DIS_MAX_A factor columns, 1 <= bins <= FN_DIS_MAX_BINS,
+ * a cardinality in [0, FN_DIS_MAX_BINS].  In every entry point: a required pointer NULL: FN_E_NULL;  a size < 1, a row stride below the width,
+ * n_pad < N, a cardinality outside [0, 64]: FN_E_SHAPE;  a size above its limit: FN_E_UNSUPPORTED;  a float or int32 pointer not 4-byte, a double
+ * pointer not 8-byte aligned: FN_E_ALIGN;  in this order, all before any launch.  A matrix is fp32, element (i, c) at x[i*ld + c], ld >= P: a column
+ * slice of a wider tensor works.  A "column-major image" holds element (i, c) at img[c*n_pad + i], n_pad >= N; entries i >= N are not touched.
+ *
+ * fn_column_range: lo[c] = min_i x[i][c], hi[c] = max_i x[i][c] over the FINITE entries, as fp32: exact, so no order is stated; a zero is returned as
+ * +0.0f whatever its sign (the kernel compares x + 0.0f).  status[c] = FN_DIS_NONFINITE when the column holds a NaN or an infinity, else 0: the call
+ * initialises status (and lo = +inf, hi = -inf, which is what a column without a finite entry keeps).  Workgroups of 4 x 64 threads own 64 columns and
+ * FN_DIS_RANGE_CHUNK rows and close with integer atomic min / max on the ordered bit patterns.
+ *
+ * fn_bin_columns: the bin image, uint8, column-major.  card is HOST memory, [P] int32, read by value, or NULL (every column continuous; required NULL
+ * for P > FN_DIS_MAX_A).  card[c] == 0, a continuous column, in fp64 with every operation rounded once and none fused:
+ *     t = ((double)x - (double)lo[c]) / ((double)hi[c] - (double)lo[c]) * (double)bins
+ *     bin = (int)t for 0 <= t < bins;  bins - 1 for t >= bins (x == hi lands there);  0 for t < 0, for a NaN t and where hi[c] == lo[c]
+ * card[c] == C >= 1, a discrete column of the levels 0 .. C-1 stored as floats: bin = (int)x where x is an integer in [0, C); otherwise bin = 0 and
+ * FN_DIS_BAD_LEVEL is OR-ed into status[c].  status is not initialised here: hand fn_column_range's over, or zeros.
+ *
+ * fn_joint_hist: counts[d][a][bz][bf], int32, [D][A][64][64] (the inner extents are padded to 64, so a pair's table is 16 KB): the number of rows i
+ * with bz_img[d*ldz + i] == bz and bf_img[a*ldf + i] == bf.  A bin value above 63 counts as value & 63.  The call zeroes counts itself, then one
+ * workgroup per (chunk of FN_DIS_HIST_CHUNK rows, a, d) counts in a 16 KB LDS table with integer atomics and adds its non-zero cells to global memory
+ * with integer atomics: order-free, so the counts are exact whatever the geometry.  D * A <= 65536 pairs.
+ *
+ * fn_column_ranks: the mid-rank of every element within its column, rank[i] = #{j : x[j] < x[i]} + (#{j : x[j] == x[i]} + 1) / 2, as fp32 into a
+ * column-major image (2 * rank is an integer <= 2N + 1 < 2^24, so the value is exact).  -0.0 == 0.0 is a tie.  The counting form: N^2 compares per
+ * column.  A workgroup of 256 threads owns FN_DIS_RANK_ROWS = 1024 rows of one column, four per thread in registers, and walks the column in tiles of
+ * FN_DIS_RANK_TILE = 1024 values staged in LDS (4 KB; every lane reads the same four values at a time, a broadcast); a tile's tail is padded with
+ * NaN, which is neither below nor equal to anything.  No sort, no hand-over between workgroups.  A NaN in the column gets rank 0.5 and is counted by
+ * nobody; an infinity ranks like any value.
+ *
+ * fn_column_corr: X (N x P) and Y (N x Q, Q <= FN_DIS_MAX_A) with a generic row and column stride each (element (i, c) at x[i*rs + c*cs]; strides in
+ * floats, >= 1), so one kernel serves the raw codes (row-major) and the ranks (column-major).  In fp64, two passes, one wavefront per X column:
+ *     mean_x[p] = (sum_i (double)x[i][p]) / N,   mean_y[q] likewise;
+ *     ss_x[p] = sum_i dx*dx,  ss_y[q] = sum_i dy*dy,  cross[p][q] = sum_i dx*dy,   dx = (double)x[i][p] - mean_x[p],  dy = (double)y[i][q] - mean_y[q]
+ * at the STORED means.  Every sum: lane l of 64 adds its rows i = l, l + 64, ... ascending from 0.0 (a term is the whole product, rounded before it is
+ * added: nothing is fused), then s[l] += s[l ^ o] for o = 32, 16, 8, 4, 2, 1 (fn_wave_sum_f64).  Every wavefront recomputes the Y sums in this same
+ * order; the wavefront of column 0 stores them.
+ *
+ * fn_mi_scores: from counts, per (d, a) pair, one wavefront per pair, fp64, natural logarithms.  With n = counts[bz][bf], r[bz] = sum_bf n and
+ * c[bf] = sum_bz n (integers) and T = sum n (the number of rows counted):
+ *     out[pair][0] = I   = sum over the cells with n > 0 of (n / T) * log((double)(n * T) / (double)(r[bz] * c[bf]))      (both products exact: < 2^53)
+ *     out[pair][1] = H_z = -sum over r[bz] > 0 of (r / T) * log(r / T),   out[pair][2] = H_f = -sum over c[bf] > 0 of (c / T) * log(c / T)
+ *     hits[pair] = sum_bz max_bf n, an integer: the histogram classifier's count of rows it gets right
+ * I: lane l owns column bf = l and adds its terms bz = 0 .. 63 ascending from 0.0 (an empty cell adds nothing), then the xor butterfly.  H_z: lane l
+ * owns row l, H_f: lane l owns column l, one term each (0.0 for an empty one), then the butterfly; the sign is applied last.  T == 0 gives zeros.
+ *
+ * fp64 bounds against a float64 restatement in the same orders (tests/helpers_disentangle.py): |device - restatement| <= k * 2^-52 * sum |term|,
+ * k counting the roundings on the longest path, each side erring by at most half of it:
+ *     means:               ceil(N / 64) lane adds + 6 butterfly adds + 1 division                             k = ceil(N / 64) + 7
+ *     ss, cross:           the two differences and the product of a term (3) + ceil(N / 64) + 6 adds          k = ceil(N / 64) + 9
+ *     I:                   the product of a term (1) + 2 for its logarithm (one ulp = 2 * 2^-53) + 64 + 6     k = 73
+ *     H_z, H_f:            1 + 2 + 1 lane add + 6                                                              k = 10
+ * The quotients n / T and (n * T) / (r * c) are single IEEE divisions of exact integers: the same bits on every side, so they add nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define FN_DIS_MAX_N (1 << 22)
+#define FN_DIS_MAX_D 4096
+#define FN_DIS_MAX_A 16
+#define FN_DIS_MAX_BINS 64
+#define FN_DIS_RANGE_CHUNK 1024   /* rows per workgroup of fn_column_range */
+#define FN_DIS_HIST_CHUNK 4096    /* rows per workgroup of fn_joint_hist   */
+#define FN_DIS_RANK_ROWS 1024
+#define FN_DIS_RANK_TILE 1024
+#define FN_DIS_NONFINITE 1        /* status bits */
+#define FN_DIS_BAD_LEVEL 2
+#define FN_DIS_MI_COLS 3          /* I, H_z, H_f */
+int fn_column_range(const float* x, int64_t ld, int N, int P, float* lo, float* hi, int32_t* status, void* stream);
+int fn_bin_columns(const float* x, int64_t ld, int N, int P, const float* lo, const float* hi, const int32_t* card_host, int bins, uint8_t* img,
+                   int64_t n_pad, int32_t* status, void* stream);
+int fn_joint_hist(const uint8_t* bz_img, int64_t ldz, int D, const uint8_t* bf_img, int64_t ldf, int A, int N, int32_t* counts, void* stream);
+int fn_column_ranks(const float* x, int64_t ld, int N, int P, float* ranks, int64_t n_pad, void* stream);
+int fn_column_corr(const float* X, int64_t x_rs, int64_t x_cs, int P, const float* Y, int64_t y_rs, int64_t y_cs, int Q, int N, double* mean_x,
+                   double* ss_x, double* mean_y, double* ss_y, double* cross, void* stream);
+int fn_mi_scores(const int32_t* counts, int pairs, double* out, int32_t* hits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Reconstruction report (report.py, epochs.evaluation_phase): what the reference's evaluation_phase() computes behind its loss terms
  * (trainer_gmm.py:470-610) - the accuracies.  The reference's: `torch.argmax(a, dim=-1)` (:546) and the per-sample loop of acc() with its
  * np.trim_zeros cut (:549-565).  OURS: the negative log-likelihood and the rank of the target per token, which re-ranking decoded hypotheses

@@ -18,6 +18,7 @@ from .midi import MidiNotes, midi_segments, read_midi, write_midi, write_midis  
 from .transfer import Transferred, transfer_midi, transfer_piece  # noqa: F401
 from .latent import generate, latent_classes, mix_latents, morph, prior_latents  # noqa: F401
 from .likelihood import Likelihood, likelihood_report, marginal_likelihood  # noqa: F401
+from .disentangle import Disentanglement, disentanglement, disentanglement_report  # noqa: F401
 from .report import RowMatches, ScoredTokens, TokenScores, match_rows, reconstruction_report, score_tokens, token_scores  # noqa: F401
 from .evaluators import GMMNoteEvaluator, GMMRhythmEvaluator, arousal_transfer, run_through_gmm  # noqa: F401
 
@@ -26,4 +27,5 @@ __all__ = ["MusicAttrRegGMVAE", "MusicAttrRegVAE", "MusicAttrSingleVAE", "MusicA
            "greedy_decode", "sample_decode", "beam_decode", "Constraints", "EventVocab", "EventGrid", "event_attributes", "sweep_scores", "controllability", "NoteVocab", "Notes", "tokens_to_notes", "notes_to_tokens", "estimate_chroma", "MidiNotes", "read_midi", "write_midi", "write_midis", "midi_segments", "continue_from", "fed_tokens", "training_phase", "training_phase_v2", "cpu_state_dict", "GMMRhythmEvaluator", "GMMNoteEvaluator", "arousal_transfer", "run_through_gmm", "evaluation_phase", "token_scores", "match_rows", "score_tokens",
            "reconstruction_report", "TokenScores", "RowMatches", "ScoredTokens", "Piece", "stitch_notes", "Transferred", "transfer_piece", "transfer_midi",
            "prior_latents", "generate", "mix_latents", "morph", "latent_classes",
-           "Likelihood", "marginal_likelihood", "likelihood_report"]
+           "Likelihood", "marginal_likelihood", "likelihood_report",
+           "Disentanglement", "disentanglement", "disentanglement_report"]

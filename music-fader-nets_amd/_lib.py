@@ -64,6 +64,9 @@ FN_MIX_LERP, FN_MIX_SLERP, FN_MIX_STEP = 0, 1, 2
 FN_MIX_MAX_SEGS, FN_MIX_MIN_SIN = 4, 1e-4
 FN_MATCH_EMPTY = 1
 FN_POST_MAX_K, FN_IW_MAX_LAT, FN_IW_COLS = 8, 4, 4
+FN_DIS_MAX_N, FN_DIS_MAX_D, FN_DIS_MAX_A, FN_DIS_MAX_BINS = 1 << 22, 4096, 16, 64
+FN_DIS_RANGE_CHUNK, FN_DIS_HIST_CHUNK, FN_DIS_RANK_ROWS, FN_DIS_RANK_TILE = 1024, 4096, 1024, 1024
+FN_DIS_NONFINITE, FN_DIS_BAD_LEVEL, FN_DIS_MI_COLS = 1, 2, 3
 _f =C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int32)
 vp = C.c_void_p
@@ -303,6 +306,12 @@ SIGNATURES = {
     "fn_latent_mix": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FnMixSeg), C.c_int, vp, C.c_int64, vp, vp]),
     "fn_posterior_draw": (C.c_int, [C.POINTER(FnPostJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp]),
     "fn_iw_reduce": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "fn_column_range": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "fn_bin_columns": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, _i, C.c_int, vp, C.c_int64, vp, vp]),
+    "fn_joint_hist": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, C.c_int, vp, vp]),
+    "fn_column_ranks": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp]),
+    "fn_column_corr": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "fn_mi_scores": (C.c_int, [vp, C.c_int, vp, vp, vp]),
     "fn_token_score": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]),
     "fn_match_rows": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fn_time_logsoftmax": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp]),

@@ -81,7 +81,7 @@ def training_phase(trainer, step, n_epochs, vgm_train_dl, vgm_val_dl, train_dl, 
     return step
 
 
-def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True, iw_samples=0):
+def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True, iw_samples=0, disentangle=False):
     """``run(dl)`` of the reference's ``evaluation_phase()`` (trainer_gmm.py:479-601) over every loader of `loaders`, on
     report.reconstruction_report: a batch of eight fields ``(d, r, n, c, arousal, valence, r_density, n_density)`` is a supervised one (the
     reference's ``is_vgmidi``), a batch of six an unsupervised one.  Per loader the reference's lines
@@ -100,8 +100,17 @@ def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True, i
 
         IW: <nats_per_piece>  <nats_per_token>  <bits_per_token>  <elbo_per_piece>  <mean_ess>
 
-    with the report's dict under "iw"; with the default 0 nothing else is called or printed."""
+    with the report's dict under "iw"; with the default 0 nothing else is called or printed.
+    disentangle=True (ours): one more walk over the loader, disentangle.disentanglement_report of the posterior means against the two densities, and one
+    more line - per density the mutual information gap, the separated attribute predictability, the dimension that wins under mutual information and
+    that dimension's R^2 and Spearman rho -
+
+        DIS: r_density <mig>  <sap>  <winner>  <r2>  <rho>  n_density <mig>  <sap>  <winner>  <r2>  <rho>
+
+    with the DisentanglementReport under "dis"; with the default False nothing else is called or printed."""
     from .report import reconstruction_report
+    if not isinstance(disentangle, bool):
+        raise ValueError("disentangle: a bool, got %r" % (disentangle,))
     if isinstance(iw_samples, bool) or not isinstance(iw_samples, int) or iw_samples < 0:
         raise ValueError("iw_samples: an int >= 0, got %r" % (iw_samples,))
     if trainer.dist is not None and trainer.dist.world > 1:
@@ -138,6 +147,12 @@ def evaluation_phase(trainer, loaders, log=print, step=0, teacher_forced=True, i
             iw = res["iw"] = likelihood_report(trainer.model, dl, samples=iw_samples)
             log("IW: {:.4}  {:.4}  {:.4}  {:.4}  {:.4}".format(iw["nats_per_piece"], iw["nats_per_token"], iw["bits_per_token"], iw["elbo_per_piece"],
                                                                  iw["mean_ess"]))
+        if disentangle:
+            from .disentangle import disentanglement_report
+            dis = res["dis"] = disentanglement_report(trainer.model, dl)
+            r = dis.result
+            log("DIS: " + "  ".join("{} {:.4}  {:.4}  {}  {:.4}  {:.4}".format(r.names[a], r.mig[a], r.sap[a], int(r.winner["mi"][a]), r.r2[r.winner["mi"][a], a],
+                                                                               r.rho[r.winner["mi"][a], a]) for a in (0, 1)))
         results.append(res)
     return results
 

@@ -954,6 +954,76 @@ class HipOps:
         _lib.check(self.lib.fn_iw_reduce(pn, T, nll_ld, _p(t0), _p(t1), _p(logp), _p(logq), n_lat, ldo(logp), B, S, _p(lw), _p(out), ldo(out), self.stream()),
                    "fn_iw_reduce")
 
+    @staticmethod
+    def _image(t, dtype, name, N):
+        """a column-major image: a 2-D view [P][>= N] with unit inner stride -> (ptr, P, n_pad)"""
+        _chk(t, dtype, name)
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < N or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise RuntimeError("%s must be 2-D [columns][>= %d] with contiguous rows, got shape %s strides %s" % (name, N, tuple(t.shape), t.stride()))
+        return _p(t), t.shape[0], (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0)))
+
+    def column_range(self, x, lo, hi, status):
+        """fn_column_range: x a 2-D fp32 view [N][P] with unit inner stride; lo, hi contiguous fp32 [P]; status contiguous int32 [P] (the call initialises it)"""
+        px, N, P, ld = _mat(x, "x")
+        _dense(lo, name="lo"), _dense(hi, name="hi"), _dense(status, torch.int32, "status")
+        if N < 1 or P < 1 or lo.numel() != P or hi.numel() != P or status.numel() != P:
+            raise RuntimeError("column_range: x%s lo%s hi%s status%s" % (tuple(x.shape), tuple(lo.shape), tuple(hi.shape), tuple(status.shape)))
+        _lib.check(self.lib.fn_column_range(px, ld, N, P, _p(lo), _p(hi), _p(status), self.stream()), "fn_column_range")
+
+    def bin_columns(self, x, lo, hi, bins, img, status, card=None):
+        """fn_bin_columns: x a 2-D fp32 view [N][P]; lo, hi contiguous fp32 [P]; img a uint8 image [P][>= N]; status contiguous int32 [P] (OR-ed into);
+        card: None (all columns continuous) or P ints on the host, 0 = continuous, C = the levels 0 .. C-1"""
+        px, N, P, ld = _mat(x, "x")
+        _dense(lo, name="lo"), _dense(hi, name="hi"), _dense(status, torch.int32, "status")
+        pi, rows, n_pad = self._image(img, torch.uint8, "img", N)
+        if N < 1 or P < 1 or rows != P or lo.numel() != P or hi.numel() != P or status.numel() != P or (card is not None and len(card) != P):
+            raise RuntimeError("bin_columns: x%s lo%s hi%s img%s status%s card %r" % (
+                tuple(x.shape), tuple(lo.shape), tuple(hi.shape), tuple(img.shape), tuple(status.shape), card))
+        arr = None if card is None else (C.c_int32 * P)(*[int(c) for c in card])
+        _lib.check(self.lib.fn_bin_columns(px, ld, N, P, _p(lo), _p(hi), arr, int(bins), pi, n_pad, _p(status), self.stream()), "fn_bin_columns")
+
+    def joint_hist(self, bz, bf, N, counts):
+        """fn_joint_hist: bz, bf uint8 images [D][>= N], [A][>= N]; counts contiguous int32 [D][A][64][64] (the call zeroes it)"""
+        pz, D, ldz = self._image(bz, torch.uint8, "bz", N)
+        pf, A, ldf = self._image(bf, torch.uint8, "bf", N)
+        _dense(counts, torch.int32, "counts")
+        if N < 1 or counts.numel() != D * A * 4096:
+            raise RuntimeError("joint_hist: bz%s bf%s counts%s for N %d" % (tuple(bz.shape), tuple(bf.shape), tuple(counts.shape), N))
+        _lib.check(self.lib.fn_joint_hist(pz, ldz, D, pf, ldf, A, N, _p(counts), self.stream()), "fn_joint_hist")
+
+    def column_ranks(self, x, ranks):
+        """fn_column_ranks: x a 2-D fp32 view [N][P]; ranks an fp32 image [P][>= N]"""
+        px, N, P, ld = _mat(x, "x")
+        pr, rows, n_pad = self._image(ranks, torch.float32, "ranks", N)
+        if N < 1 or P < 1 or rows != P:
+            raise RuntimeError("column_ranks: x%s ranks%s" % (tuple(x.shape), tuple(ranks.shape)))
+        _lib.check(self.lib.fn_column_ranks(px, ld, N, P, pr, n_pad, self.stream()), "fn_column_ranks")
+
+    def column_corr(self, X, Y, mean_x, ss_x, mean_y, ss_y, cross):
+        """fn_column_corr: X (N, P), Y (N, Q) 2-D fp32 tensors of any positive strides (a transposed image is one); mean_x, ss_x contiguous fp64 [P],
+        mean_y, ss_y [Q], cross [P][Q]"""
+        _chk(X, name="X"), _chk(Y, name="Y")
+        if X.dim() != 2 or Y.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1 or Y.shape[1] < 1 or Y.shape[0] != X.shape[0]:
+            raise RuntimeError("column_corr: X (N, P) and Y (N, Q), got %s and %s" % (tuple(X.shape), tuple(Y.shape)))
+        N, P, Q = X.shape[0], X.shape[1], Y.shape[1]
+        strides = [max(1, s) if n == 1 else s for t in (X, Y) for s, n in zip(t.stride(), t.shape)]          # an extent of 1 is never stepped over
+        for t, n, nm in ((mean_x, P, "mean_x"), (ss_x, P, "ss_x"), (mean_y, Q, "mean_y"), (ss_y, Q, "ss_y"), (cross, P * Q, "cross")):
+            _dense(t, torch.float64, nm)
+            if t.numel() != n:
+                raise RuntimeError("column_corr: %s holds %d entries, not %d" % (nm, t.numel(), n))
+        if min(strides) < 1:
+            raise RuntimeError("column_corr: positive strides, got %s and %s" % (X.stride(), Y.stride()))
+        _lib.check(self.lib.fn_column_corr(_p(X), strides[0], strides[1], P, _p(Y), strides[2], strides[3], Q, N, _p(mean_x), _p(ss_x), _p(mean_y),
+                                           _p(ss_y), _p(cross), self.stream()), "fn_column_corr")
+
+    def mi_scores(self, counts, out, hits):
+        """fn_mi_scores: counts contiguous int32 [pairs][64][64]; out contiguous fp64 [pairs][3] (I, H_z, H_f); hits contiguous int32 [pairs]"""
+        _dense(counts, torch.int32, "counts"), _dense(out, torch.float64, "out"), _dense(hits, torch.int32, "hits")
+        pairs = hits.numel()
+        if pairs < 1 or counts.numel() != pairs * 4096 or out.numel() != pairs * _lib.FN_DIS_MI_COLS:
+            raise RuntimeError("mi_scores: counts%s out%s hits%s" % (tuple(counts.shape), tuple(out.shape), tuple(hits.shape)))
+        _lib.check(self.lib.fn_mi_scores(_p(counts), pairs, _p(out), _p(hits), self.stream()), "fn_mi_scores")
+
     def sweep_scores(self, r, n, status, values, which, r_std, n_std, scores, n_used):
         """fn_sweep_scores: r, n fp32 and status int32 contiguous [S][Vn]; values fp64 [Vn]; scores fp64 [4]; n_used int32 [1]"""
         _dense(r, name="r"), _dense(n, name="n"), _dense(status, torch.int32, "status"), _dense(values, torch.float64, "values")

@@ -170,9 +170,13 @@ def main(argv=None):
                     help="after training, the reference's evaluation_phase() over the four loaders: CE / Regularized / Acc lines (--model gmm, one process)")
     ap.add_argument("--iw-samples", type=int, default=0, metavar="N",
                     help="with --evaluate: one more line per loader, the importance-weighted log-likelihood from N posterior samples per piece (default 0: off)")
+    ap.add_argument("--disentangle", action="store_true",
+                    help="with --evaluate: one more line per loader, the disentanglement of the posterior means against the two densities (MIG, SAP, winner, R^2, rho)")
     opts = ap.parse_args(argv)
     if opts.iw_samples < 0 or (opts.iw_samples and not opts.evaluate):
         raise SystemExit("train: --iw-samples N >= 0 goes with --evaluate")
+    if opts.disentangle and not opts.evaluate:
+        raise SystemExit("train: --disentangle goes with --evaluate")
 
     import importlib
     pkg = importlib.import_module(__package__)
@@ -230,7 +234,7 @@ def main(argv=None):
                               name=args["name"], log=say, save=rank == 0)    # every rank runs the schedule, rank 0 writes the checkpoints
         if opts.evaluate:                                               # trainer_gmm.py:603-614
             say("Evaluate")
-            evaluation_phase(trainer, [dls[k] for k in ("train", "val", "vgm_train", "vgm_val")], log=say, step=step, iw_samples=opts.iw_samples)
+            evaluation_phase(trainer, [dls[k] for k in ("train", "val", "vgm_train", "vgm_val")], log=say, step=step, iw_samples=opts.iw_samples, disentangle=opts.disentangle)
     else:
         say("Train / Validation / Test")                                # trainer.py:74-75
         say(sizes["train"], sizes["val"], sizes["test"])
