@@ -241,7 +241,10 @@ typedef struct FnGruFwd {
  * fn_frag_floats(3H, H) floats) and frag_ws 3 * fn_frag_floats(B, H) floats (the state is exchanged as triples too).  H = 512, every
  * scan in full row groups of 64 (or 128) rows, saved gates, T >= 2 (h0_frag / h_last_frag are then triple images of 3/2 * fn_frag_floats(B, H)
  * floats); anything else returns FN_E_UNSUPPORTED (the caller repeats the call without the bit).  Same gate arithmetic; against the default kernels the states differ by fp32 rounding only
- * (tests/test_gpu_parity.py::test_forward_scan_bf16x6). */
+ * (tests/test_gpu_parity.py::test_forward_scan_bf16x6).
+ * "Exactly" has a domain: hi + mid + lo == x holds for x == 0 and 2^-110 <= |x| < 2^128 (1 - 2^-9).  Below 2^-110 the last remainder can have a
+ * bit under the smallest bf16 subnormal (2^-133), which is dropped; from 2^128 (1 - 2^-9) on (bits 0x7f7f8000) hi rounds to infinity.  Infinities
+ * and NaNs have no split.  tests/test_images_reference.py sweeps every mantissa at both ends, tests/test_gpu_images.py checks the kernels on it. */
 int fn_frag3_pack(const float* src, int rows, int K, int ld, void* dst, void* stream);
 size_t fn_frag_floats(int rows, int K);
 int fn_frag_pack(const float* src, int rows, int K, int ld, float* dst, void* stream);
