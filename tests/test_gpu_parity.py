@@ -1509,6 +1509,9 @@ def test_dropin_forward_backward_vs_reference(case, small, c0):
             ref = gold["gradsum_unsup/" + k]
             np.testing.assert_allclose(float(gcpu.abs().sum()), ref[1], rtol=5e-4, atol=1e-5, err_msg=k)
     np.testing.assert_allclose(math.sqrt(sq), gold["gradnorm_unsup_20000"][0], rtol=1e-3)
+    if case == "c0":          # ... and every 16 x 32 block of every gradient against the float64 oracle (helpers_step.py)
+        from helpers_step import c0_references, check_step_grads, cpu_state
+        check_step_grads({k: p.grad.detach().cpu().numpy() for k, p in m.named_parameters() if p.grad is not None}, c0_references(gold, cpu_state(m)))
 
 
 @pytest.mark.parametrize("arith", ["f32", "bf16x6"])
@@ -1538,6 +1541,9 @@ def test_fused_gradients_vs_reference(case, sup, chunk, arith, small, c0):
             ref = gold["gradsum_%s/%s" % (tag, k)]
             np.testing.assert_allclose(float(gk.abs().sum()), ref[1], rtol=5e-4, atol=1e-5, err_msg=k)
     np.testing.assert_allclose(tr.grad_norm(), gold["gradnorm_%s_20000" % tag][0], rtol=1e-3)
+    if case == "c0":          # ... and every 16 x 32 block of every gradient against the float64 oracle (helpers_step.py)
+        from helpers_step import c0_references, check_step_grads, cpu_state, flat_grads
+        check_step_grads(flat_grads(tr), c0_references(gold, cpu_state(m), sup))
 
 
 @pytest.mark.parametrize("arith", ["f32", "bf16x6"])
