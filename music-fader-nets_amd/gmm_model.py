@@ -318,7 +318,7 @@ class MusicAttrRegGMVAE(nn.Module):
         B, Tr = r.shape
         d = torch.zeros(B, 1, dtype=torch.int32, device=r.device)
         c = torch.zeros(B, 24, device=r.device)
-        dec = eng.decoders(d, r, n, c, z_r.float().contiguous(), z_n.float().contiguous())
+        dec = eng.decoders(d, r, n, c, z_r.float().contiguous(), z_n.float().contiguous(), save=False)     # no backward follows: no gates are written
         outs = []
         for e, Ce in (("r", 3), ("n", 16)):
             lp = torch.empty(B, Tr, Ce, device=r.device)

@@ -134,16 +134,20 @@ def _gru_final(x, sd, pfx, sfx, reverse):
     return h
 
 
-def encode(sd, x):
-    """gmm_model.py:82-98 -> (mu_r, sigma_r, mu_n, sigma_n); 'var' heads are used as std-devs."""
+def encode(sd, x, trace=None):
+    """gmm_model.py:82-98 -> (mu_r, sigma_r, mu_n, sigma_n); 'var' heads are used as std-devs.
+    trace: a dict that receives the intermediates (final encoder states, mu | log sigma); the arithmetic is the same with or without it."""
     res = []
     for e in ("r", "n"):
         hf = _gru_final(x, sd, "gru_%s." % e, "", False)
         hb = _gru_final(x, sd, "gru_%s." % e, "_reverse", True)
         xe = torch.cat([hf, hb], dim=1)           # h_n.transpose(0,1).view(B,-1) = [fwd | bwd]
         mu = xe @ sd["mu_%s.weight" % e].t() + sd["mu_%s.bias" % e]
-        sg = torch.exp(xe @ sd["var_%s.weight" % e].t() + sd["var_%s.bias" % e])
+        ls = xe @ sd["var_%s.weight" % e].t() + sd["var_%s.bias" % e]
+        sg = torch.exp(ls)
         res += [mu, sg]
+        if trace is not None:
+            trace["enc_h_" + e], trace["enc_h_%s_reverse" % e], trace["pre_" + e] = hf, hb, torch.cat([mu, ls], dim=1)
     return tuple(res)
 
 
@@ -158,11 +162,13 @@ def approx_qy_x(z, mu_lookup, logvar_lookup):
     return ll, torch.softmax(ll, dim=1)
 
 
-def sub_decoder(sd, e, attr_oh, z):
-    """gmm_model.py:100-117 for one attribute; log_softmax over dim=1 = the TIME axis."""
+def sub_decoder(sd, e, attr_oh, z, trace=None):
+    """gmm_model.py:100-117 for one attribute; log_softmax over dim=1 = the TIME axis.
+    trace: a dict that receives the initial state, the states and the pre-softmax logits, time-major."""
     B, Tr, _ = attr_oh.shape
     inp = torch.cat([attr_oh, z.unsqueeze(1).expand(B, Tr, z.shape[1])], dim=-1)
     h = z @ sd["linear_init_%s.weight" % e].t() + sd["linear_init_%s.bias" % e]
+    h_init = h
     p = "gru_d_%s." % e
     xp = inp @ sd[p + "weight_ih_l0"].t() + sd[p + "bias_ih_l0"]
     hs = []
@@ -171,17 +177,23 @@ def sub_decoder(sd, e, attr_oh, z):
         hs.append(h)
     hs = torch.stack(hs, dim=1)
     logits = hs @ sd["linear_out_%s.weight" % e].t() + sd["linear_out_%s.bias" % e]
+    if trace is not None:
+        trace["sd_h0_" + e], trace["sd_h_" + e], trace["sd_logits_" + e] = h_init, hs.transpose(0, 1), logits.transpose(0, 1)
     return torch.log_softmax(logits, dim=1)
 
 
-def global_decoder(sd, z, steps, teacher=None):
+def global_decoder(sd, z, steps, teacher=None, trace=None):
     """gmm_model.py:119-149.  teacher=(B,T) int tokens -> teacher forcing (train mode,
-    eps=100 makes `p < eps` always true, :139-142); None -> greedy argmax feedback (:147-148)."""
+    eps=100 makes `p < eps` always true, :139-142); None -> greedy argmax feedback (:147-148).
+    trace: a dict that receives h0g, rbg (the z part of layer 1's input product, formed for the trace alone) and, time-major, hx0, gx2, hx1, logits."""
     B = z.shape[0]
     tok = torch.full((B,), START_TOKEN, dtype=torch.long)
     hx0 = z @ sd["linear_init_global.weight"].t() + sd["linear_init_global.bias"]
     hx1 = None
     outs = []
+    tr = {k: [] for k in ("hx0", "gx2", "hx1", "logits")}
+    if trace is not None:
+        trace["h0g"], trace["rbg"] = hx0, z @ sd["grucell_g.weight_ih"][:, E:].t()
     for i in range(steps):
         inp = torch.cat([convert_to_one_hot(tok, E), z], dim=1)
         xp = inp @ sd["grucell_g.weight_ih"].t() + sd["grucell_g.bias_ih"]
@@ -190,28 +202,37 @@ def global_decoder(sd, z, steps, teacher=None):
             hx1 = hx0
         xp2 = hx0 @ sd["grucell_g_2.weight_ih"].t() + sd["grucell_g_2.bias_ih"]
         hx1 = gru_cell(xp2, hx1, sd["grucell_g_2.weight_hh"], sd["grucell_g_2.bias_hh"])
-        out = torch.log_softmax(hx1 @ sd["linear_out_g.weight"].t() + sd["linear_out_g.bias"], dim=1)
+        logits = hx1 @ sd["linear_out_g.weight"].t() + sd["linear_out_g.bias"]
+        out = torch.log_softmax(logits, dim=1)
         outs.append(out)
+        for k, v in (("hx0", hx0), ("gx2", xp2), ("hx1", hx1), ("logits", logits)):
+            tr[k].append(v)
         tok = teacher[:, i] if teacher is not None else out.max(1)[1]
+    if trace is not None:
+        trace.update({k: torch.stack(v, dim=0) for k, v in tr.items()})
     return torch.stack(outs, dim=1)
 
 
-def forward(sd, d, r, n, c, eps_r, eps_n, training=True):
+def forward(sd, d, r, n, c, eps_r, eps_n, training=True, trace=False):
     """gmm_model.py:220-259.  d/r/n are int token tensors (the one-hot tensors the reference receives are exactly
-    convert_to_one_hot of these).  training=False = after model.eval(): the global decoder feeds back its own argmax (:146-148)."""
+    convert_to_one_hot of these).  training=False = after model.eval(): the global decoder feeds back its own argmax (:146-148).
+    trace=True: returns (the same dict, intermediates by the names of the engine's buffers - pre_r / pre_n (mu | log sigma), enc_h_*, h0g, rbg,
+    hx0, gx2, hx1, logits, sd_h0_e, sd_h_e, sd_logits_e; per-step tensors time-major); no output is computed differently."""
+    tr = {} if trace else None
     x = convert_to_one_hot(d, E)
-    mu_r, sg_r, mu_n, sg_n = encode(sd, x)
+    mu_r, sg_r, mu_n, sg_n = encode(sd, x, tr)
     z_r = mu_r + sg_r * eps_r
     z_n = mu_n + sg_n * eps_n
     ll_r, qy_r = approx_qy_x(z_r, sd["mu_r_lookup.weight"], sd["logvar_r_lookup.weight"])
     ll_n, qy_n = approx_qy_x(z_n, sd["mu_n_lookup.weight"], sd["logvar_n_lookup.weight"])
-    r_out = sub_decoder(sd, "r", convert_to_one_hot(r, R), z_r)
-    n_out = sub_decoder(sd, "n", convert_to_one_hot(n, N), z_n)
+    r_out = sub_decoder(sd, "r", convert_to_one_hot(r, R), z_r, tr)
+    n_out = sub_decoder(sd, "n", convert_to_one_hot(n, N), z_n, tr)
     zc = torch.cat([z_r, z_n, c], dim=1)
-    out = global_decoder(sd, zc, d.shape[1], teacher=d if training else None)
-    return dict(out=out, r_out=r_out, n_out=n_out, mu_r=mu_r, sigma_r=sg_r, mu_n=mu_n, sigma_n=sg_n,
-                z_r=z_r, z_n=z_n, ll_r=ll_r, ll_n=ll_n, qy_r=qy_r, qy_n=qy_n,
-                y_r=qy_r.max(1)[1], y_n=qy_n.max(1)[1])
+    out = global_decoder(sd, zc, d.shape[1], teacher=d if training else None, trace=tr)
+    fw = dict(out=out, r_out=r_out, n_out=n_out, mu_r=mu_r, sigma_r=sg_r, mu_n=mu_n, sigma_n=sg_n,
+              z_r=z_r, z_n=z_n, ll_r=ll_r, ll_n=ll_n, qy_r=qy_r, qy_n=qy_n,
+              y_r=qy_r.max(1)[1], y_n=qy_n.max(1)[1])
+    return (fw, tr) if trace else fw
 
 
 # ----------------------------------------------------------------------------------------------

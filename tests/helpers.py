@@ -788,6 +788,8 @@ def check_epoch_v2_run(pkg, family, g, tmp_path, device="cpu", ops=None, rtol=5e
 # A *logical scan* is a dict of CPU fp32 tensors that states one whole scan of fn_gru_seq_fwd / fn_gru_seq_bwd (include/fadernets.h), unchunked:
 #   B, T, H, w_hh [3H][H], b_hh [3H], optional b_ih [3H], h0 [B][H], gx_dense [T][B][3H], gx_table [V][3H] + idx [B][>=T] int32 (+ reverse,
 #   idx_shift, start_token), gx_rowbias [B][3H]; for the backward optional dh_last [B][H], dh_ext [T][B][H] and the flags want_dh0, want_rowsums.
+#   gates=False: a forward-only scan, as every caller with save=False launches it - the descriptor gets gates = NULL, no backward runs, and
+#   h_all is the one output (the ping-pong and bf16 x 6 forward kernels need saved gates: such a launch takes other kernels, csrc/gru_plan.h).
 # run_scans() turns a list of them into the descriptors of a backend (FakeOps on a row subset, HipOps on the device), in one launch or in time
 # chunks with the hand-overs the decoder pipeline uses, and returns per scan the outputs named in SCAN_QUANTITIES on the CPU.
 # factor of check_scan_vs_f64 = the smallest power of two >= 2 x the worst err_kernel / e_ref measured on an MI355X (profiles/scan_fp64_errors.txt),
@@ -839,7 +841,7 @@ def scan_reference_f64(scans, rows=None, device="cpu"):
         f = lambda k: None if s.get(k) is None else s[k].to(device).double()
         W, b_hh, b_ih, tab = f("w_hh"), f("b_hh"), f("b_ih"), f("gx_table")
         rb = None if s.get("gx_rowbias") is None else s["gx_rowbias"][rw].to(device).double()
-        backward = s.get("dh_last") is not None or s.get("dh_ext") is not None
+        backward = (s.get("dh_last") is not None or s.get("dh_ext") is not None) and s.get("gates", True)
         with torch.enable_grad():
             pgx = (s["gx_dense"][:, rw].to(device).double() if s.get("gx_dense") is not None else torch.zeros(T, R, 3 * H, dtype=torch.float64, device=device)).requires_grad_(backward)
             phn = torch.zeros(T, R, H, dtype=torch.float64, device=device, requires_grad=backward)
@@ -862,7 +864,7 @@ def scan_reference_f64(scans, rows=None, device="cpu"):
                 hs.append(h)
                 gs.append((r.detach(), z.detach(), n.detach(), hn.detach()))
             o = {"h_all": torch.stack([x.detach() for x in hs])}
-            for j, k in enumerate(SCAN_FWD_QUANTITIES[1:]):
+            for j, k in enumerate(SCAN_FWD_QUANTITIES[1:] if s.get("gates", True) else ()):
                 o[k] = torch.stack([g_[j] for g_ in gs])
             if backward:
                 loss = torch.zeros((), dtype=torch.float64, device=device)
@@ -897,7 +899,8 @@ def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=
     running backwards over the chunks - what the decoder pipeline does (engine.py, _bwd_chunk).  x6: the arithmetic asked for, explicitly
     (HipOps: dw_x6 and x6= of both calls; a launch that cannot take it raises).  carry_fault(ci, tensor): test hook, edits the CPU carry that
     leaves backward chunk ci (FakeOps only).  h_all_off: h_all is a view that many floats behind the start of its allocation (1: 4 bytes off a
-    16-byte boundary).  The backward consumes the backend's OWN saved gates.  Returns per scan {quantity: CPU tensor}."""
+    16-byte boundary).  The backward consumes the backend's OWN saved gates.  A scan with gates=False is handed gates = None and gets no backward:
+    its one output is h_all.  Returns per scan {quantity: CPU tensor}."""
     fake = device == "cpu"
     fwd_kw, bwd_kw = dict(fwd_kw or {}), dict(bwd_kw or {})
     if not fake:
@@ -911,7 +914,7 @@ def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=
         B, T, H = (len(rw) if fake else s["B"]), s["T"], s["H"]
         sub.append((B, T, H))
         d = dict(B=B, T=T, H=H, reverse=int(s.get("reverse", 0)), b_hh=dev(s["b_hh"]), idx_shift=int(s.get("idx_shift", 0)), start_token=int(s.get("start_token", 0)),
-                 h_all=zeros(T * B * H + h_all_off)[h_all_off:].view(T, B, H), gates=zeros(T, ops.gates_floats(B, H)))
+                 h_all=zeros(T * B * H + h_all_off)[h_all_off:].view(T, B, H), gates=zeros(T, ops.gates_floats(B, H)) if s.get("gates", True) else None)
         w = dev(s["w_hh"])
         d["w_hh_frag"] = zeros(ops.frag_floats(3 * H, H))
         b = dict(B=B, T=T, H=H, w_hh_t_frag=zeros(ops.frag_floats(H, 3 * H)))
@@ -932,7 +935,7 @@ def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=
         if s.get("gx_dense") is not None:
             d["gx_dense"] = dev(take(s["gx_dense"], 1))
         fw.append(d)
-        if s.get("dh_last") is not None or s.get("dh_ext") is not None:
+        if (s.get("dh_last") is not None or s.get("dh_ext") is not None) and s.get("gates", True):
             b.update(h0=d.get("h0"), h_all=d["h_all"], gates=d["gates"], dh_last=None if s.get("dh_last") is None else dev(take(s["dh_last"])),
                      dh_ext=None if s.get("dh_ext") is None else dev(take(s["dh_ext"], 1)), dgx_all=zeros(T, B, 3 * H), dghn_all=zeros(T, B, H),
                      dh0=zeros(B, H) if s.get("want_dh0") else None, scratch=zeros(B, H))
@@ -951,7 +954,7 @@ def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=
             t1 = min(T, t0 + chunk)
             part = []
             for d, hb in zip(fw, hand):
-                c = dict(d, T=t1 - t0, h_all=d["h_all"][t0:t1], gates=d["gates"][t0:t1], idx_shift=d["idx_shift"] + t0)
+                c = dict(d, T=t1 - t0, h_all=d["h_all"][t0:t1], gates=None if d["gates"] is None else d["gates"][t0:t1], idx_shift=d["idx_shift"] + t0)
                 if d.get("gx_dense") is not None:
                     c["gx_dense"] = d["gx_dense"][t0:t1]
                 if t0 > 0:
@@ -989,9 +992,10 @@ def run_scans(ops, scans, rows=None, device="cpu", chunk=None, x6=False, fwd_kw=
     for s, rw, d, b, (B, T, H) in zip(scans, rws, fw, bw, sub):
         cut = (lambda t, dim=0: t.cpu()) if fake else (lambda t, dim=0: t.index_select(dim, rw.to(device)).cpu())
         o = {"h_all": cut(d["h_all"], 1)}
-        gt = d["gates"][:, : B * 4 * H].reshape(T, B, 4, H) if fake else _unblock_gates(d["gates"], B, H, rw).cpu()
-        for j, k in enumerate(SCAN_FWD_QUANTITIES[1:]):
-            o[k] = gt[:, :, j]
+        if d["gates"] is not None:
+            gt = d["gates"][:, : B * 4 * H].reshape(T, B, 4, H) if fake else _unblock_gates(d["gates"], B, H, rw).cpu()
+            for j, k in enumerate(SCAN_FWD_QUANTITIES[1:]):
+                o[k] = gt[:, :, j]
         if b is not None:
             for k in SCAN_BWD_QUANTITIES:
                 if b.get(k) is not None:
@@ -1061,6 +1065,7 @@ def check_scan_vs_f64(scans, got, rows, chunk=None, key=None, F=None, ref_device
              the fp32 CPU restatement's own distance from fp64 on the same inputs: the margin F covers another summation order and another
              draw of inputs, not a wrong term;
       (old)  the whole-tensor bound the suite already applies, unchanged: max |got - ref| <= 2e-5 (forward) / 5e-5 (backward) of the tensor's max.
+    A forward-only scan (gates=False) has h_all alone, checked at every step with the same bound and factor.
     Returns {(scan, quantity): (worst err / max(e_ref, 2**-23), step, block)}."""
     F = SCAN_F if F is None else F
     assert F <= SCAN_F_CAP
@@ -1148,6 +1153,11 @@ def _logical_scan(gen, B, T, H, kind, h0=True, rowbias=False, b_ih=True, dh_last
     return s
 
 
+def _forward_only(scans):
+    """the same logical scans as forward-only ones: no saved gates, hence no backward (a gradient seed they carry is not used)"""
+    return [dict(s, gates=False) for s in scans]
+
+
 def _ws_scans(gen, B, H, T=70, n=2):
     """the inputs of the 32-slice / per-step cases: a reverse table scan with h0, row bias, dh_last only and dL/dh0, beside (n = 2) a dense scan
     from a zero state with dh_ext only"""
@@ -1182,6 +1192,16 @@ SCAN_INPUTS = {
 for _B in (1, 33, 200):
     for _H in (64, 96, 512):
         SCAN_INPUTS["ws_%d_%d" % (_B, _H)] = (100 + _B + _H, (lambda g, B=_B, H=_H: _ws_scans(g, B, H, n=1 if (B, H) == (200, 512) else 2)), None)
+# forward only (gates = NULL): what save=False launches.  Small: each case takes seconds.
+SCAN_INPUTS.update({
+    # the encoder launch of Engine.encode(save=False): 4 scans x 256 rows, two reversed -> 128-row groups, no ping-pong without gates
+    "fo_enc": (31, lambda g: _forward_only([_logical_scan(g, 256, 6, 512, k, h0=False) for k in ("table", "table_rev", "table", "table_rev")]), None),
+    # the decoder pipeline's two layers, 7 steps in chunks of 2: fp32 fragment hand-over through both slots, a one-step tail on the per-step kernel
+    "fo_dec": (32, lambda g: _forward_only([_logical_scan(g, 256, 7, 512, "table_shift", rowbias=True), _logical_scan(g, 256, 7, 512, "dense", b_ih=False)]), 2),
+    "fo_33_96": (33, lambda g: _forward_only(_ws_scans(g, 33, 96, T=9)), None),
+    "fo_200_64": (34, lambda g: _forward_only(_ws_scans(g, 200, 64, T=9)), None),
+    "fo_step": (35, lambda g: _forward_only(_ws_scans(g, 33, 512, T=5)), None),
+})
 _SCAN_INPUT_CACHE = {}
 
 
@@ -1317,9 +1337,20 @@ def lib_scan_candidates(scans, variants=(0, 0), x6=False, cu_budget=(0, 0), pers
 # A case whose shape does not reach the kernels named here fails (scan_kernel_names, and on the GPU the library's own plan).
 def _sc(cid, inputs, fwd, bwd, x6=False, variant=0, bvariant=None, budget=0, persistent=True):
     """variant: of the forward and (bvariant None) the backward launches; budget: cu_budget of the backward launches, as engine.py gives the decoder
-    pipeline's backward half of the chip"""
+    pipeline's backward half of the chip.  fwd / bwd: the kernel the case is for (None: any), or {steps per launch: kernel} where the launches of a
+    chunked chain take different ones; a forward-only case (inputs with gates=False) runs no backward and names none."""
     return dict(id=cid, inputs=inputs, x6=x6, variants=(variant, variant if bvariant is None else bvariant), budget=(0, budget), persistent=persistent,
                 kernels=(fwd, bwd))
+
+
+def case_kernel(case, i, T=None):
+    """the forward (i = 0) / backward (i = 1) kernel a case is for, at T steps per launch"""
+    want = case["kernels"][i]
+    return want.get(T) if isinstance(want, dict) else want
+
+
+def case_forward_only(case):
+    return not all(s.get("gates", True) for s in scan_inputs(case["inputs"])[0])
 
 
 _P4, _P8 = "gru_fwd_persist_kernel<%s, 4>", "gru_bwd_persist_kernel<%s, 8>"
@@ -1361,4 +1392,15 @@ SCAN_CASES += [
     _sc("t1-falls-back", "t1", "gru_fwd_step_kernel", "gru_bwd_step_kernel"),
     _sc("eight-f32", "eight", "gru_fwd_pp_kernel<2>", "gru_bwd_rs_kernel<1>"),
     _sc("eight-x6-32rows", "eight", "gru_fwd_x6pp_kernel<2>", "gru_bwd_x6_kernel<1>", x6=True, bvariant=_V_X6ALT),
+]
+# forward only: gates = NULL reaches the weight-stationary kernels without ping-pong (all five tilings) and the per-step kernel, never pp / bf16 x 6
+SCAN_CASES += [
+    _sc("fo-enc", "fo_enc", _P4 % "4, 1, 2", None),
+    _sc("fo-dec", "fo_dec", {2: _P4 % "2, 2, 2", 1: "gru_fwd_step_kernel"}, None),
+    _sc("fo-33-96-rows16", "fo_33_96", _P4 % "1, 4, 1", None, variant=16),
+    _sc("fo-33-96-rows32", "fo_33_96", _P4 % "2, 2, 1", None, variant=32),
+    _sc("fo-200-64-rows16", "fo_200_64", _P4 % "1, 4, 1", None, variant=16),
+    _sc("fo-200-64-rows32", "fo_200_64", _P4 % "2, 2, 1", None, variant=32),
+    _sc("fo-200-64-rows64-alt", "fo_200_64", _P4 % "4, 1, 1", None, variant=64 | _V_ALT),
+    _sc("fo-step", "fo_step", "gru_fwd_step_kernel", None, persistent=False),
 ]

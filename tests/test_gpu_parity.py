@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from fake_ops import FakeOps
-from helpers import (NOISE_PARAMS, ONE_LAUNCH_BLOCKS, REPLAY_CASES, REPLAY_GRAPH_PATHS, SCAN_CASES, PlanRecorder, _unblock_gates, _ws_scans, batch_of, check_scan_vs_f64, chosen_kernels,
+from helpers import (NOISE_PARAMS, case_forward_only, case_kernel, ONE_LAUNCH_BLOCKS, REPLAY_CASES, REPLAY_GRAPH_PATHS, SCAN_CASES, PlanRecorder, _unblock_gates, _ws_scans, batch_of, check_scan_vs_f64, chosen_kernels,
                      grad_tolerances, load_golden,
                      make_model, oracle_grads_f64, relerr, replay_decode_check, replay_inputs, replay_line, replay_z, run_scans, scan_inputs, scan_kernel_names,
                      scan_lines, sd_from)
@@ -478,13 +478,17 @@ def test_scans_every_step_vs_fp64(ops, case):
     the whole and on half of the chip), the attribute decoders (64 steps, dL/dh0), the 32-slice kernels in every forced row block and switch at
     70 steps with ragged batches, the per-step kernels, T = 2 and T = 1, 8 scans of different lengths.  The arithmetic and the variant bits are
     asked for explicitly, so a launch that cannot take the bf16 x 6 kernel raises; a bf16 x 6 case must also differ in some bit from the fp32
-    kernels' result (it really ran).  Each case prints the lines of profiles/scan_fp64_errors.txt."""
+    kernels' result (it really ran).  The fo-* cases are forward only (gates = NULL, as every save=False caller launches): no backward runs, h_all is
+    checked at every step, and the plans must name a gru_fwd_persist_kernel tiling or the per-step kernel, never a ping-pong or bf16 x 6 one.
+    Each case prints the lines of profiles/scan_fp64_errors.txt."""
     scans, rows, chunk = scan_inputs(case["inputs"])
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     Ts = [None] if chunk is None else sorted({chunk, scans[0]["T"] % chunk or chunk})
     names = [scan_kernel_names(scans, case["variants"], case["x6"], case["budget"], case["persistent"], T=T, cus=cus) for T in Ts]
-    for nm in names:
-        for want, have in zip(case["kernels"], nm):
+    fo = case_forward_only(case)                                 # gates = NULL: forward launches only, h_all alone (helpers.run_scans)
+    for T, nm in zip(Ts, names):
+        for i, have in enumerate(nm):
+            want = case_kernel(case, i, T)
             assert want is None or want == have, (want, have)      # the shape reaches the kernel the case is for on this device
     kw = [dict(persistent=case["persistent"], cu_budget=case["budget"][i], variant=case["variants"][i]) for i in (0, 1)]
     try:
@@ -494,11 +498,17 @@ def test_scans_every_step_vs_fp64(ops, case):
         torch.cuda.synchronize()
         assert not ops.gru_sync_error()
         # the library's own plan on the real descriptors: the candidate every launch of the case took on this device is the kernel the case is for
-        for want, plans in zip(case["kernels"], (rec.fwd, rec.bwd)):
+        for i, plans in enumerate((rec.fwd, rec.bwd)):
+            if fo and i == 1:
+                assert not plans                                  # a forward-only case launches no backward
+                continue
             assert len(plans) == (1 if chunk is None else -(-scans[0]["T"] // chunk))
-            assert want is None or set(chosen_kernels(plans)) == {want}, (want, plans)
-        for i, plans in enumerate((rec.fwd, rec.bwd)):           # ... and what the hand restatement names (a case without named kernels included)
+            want = {case_kernel(case, i, T) for T in Ts}
+            assert None in want or set(chosen_kernels(plans)) == want, (want, plans)
+            # ... and what the hand restatement names (a case without named kernels included)
             assert set(chosen_kernels(plans)) == {nm[i] for nm in names}, (names, plans)
+        if fo:
+            assert not any(k.startswith(("gru_fwd_pp", "gru_fwd_x6")) for k in chosen_kernels(rec.fwd))
         if case["x6"]:
             ops.dw_x6 = False
             f32 = run_scans(ops, scans, rows, device=DEV, chunk=chunk, x6=False)
@@ -509,7 +519,8 @@ def test_scans_every_step_vs_fp64(ops, case):
         ops.dw_x6 = _x6_default()
     worst = check_scan_vs_f64(scans, got, rows, chunk, key=case["inputs"], ref_device=DEV)
     print()
-    for line in scan_lines(case["id"], names[0], worst):
+    label = tuple("+".join(sorted({nm[i] for nm in names})) for i in (0, 1))        # (a chain whose tail chunk takes another kernel names both)
+    for line in scan_lines(case["id"], label, worst):
         print(line)
 
 

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from fake_ops import FakeOps
-from helpers import (SCAN_BWD_QUANTITIES, SCAN_CASES, SCAN_F, SCAN_F_CAP, SCAN_INPUTS, check_scan_vs_f64, lib_scan_candidates, relerr, run_scans, scan_inputs,
+from helpers import (SCAN_BWD_QUANTITIES, SCAN_CASES, SCAN_F, SCAN_F_CAP, SCAN_INPUTS, case_forward_only, case_kernel, check_scan_vs_f64, lib_scan_candidates, relerr,
+                     run_scans, scan_inputs,
                      scan_kernel_candidates, scan_kernel_names,
                      scan_reference_f64, scan_references, scan_rows, scan_step_errors)
 
@@ -37,13 +38,15 @@ def test_factor_is_within_its_cap():
 @pytest.mark.parametrize("name", sorted(SCAN_INPUTS))
 def test_fake_ops_passes_and_inputs_satisfy_the_condition(name):
     """the fp32 restatement passes its own check (ratio 1 by construction) on every GPU case's inputs; scan_references asserts the input condition:
-    every per-step block maximum of the fp64 reference >= 2**-100, every e_ref finite and non-zero"""
+    every per-step block maximum of the fp64 reference >= 2**-100, every e_ref finite and non-zero.  A forward-only scan (gates=False) has h_all alone."""
     worst = _check(name, _fake(name), F=1)
     scans = scan_inputs(name)[0]
     for i, s in enumerate(scans):
         want = set(("h_all", "gate_r", "gate_z", "gate_n", "gate_hn", "dgx_all", "dghn_all"))
         want |= {"dh0"} if s.get("want_dh0") else set()
         want |= {"dgx_rowsum", "dghn_rowsum"} if s.get("want_rowsums", True) else set()
+        if not s.get("gates", True):
+            want = {"h_all"}
         assert {k for (j, k) in worst if j == i} == want, (i, sorted(worst))
     assert all(v[0] <= 1.0 for v in worst.values())
 
@@ -58,8 +61,11 @@ def test_every_gpu_case_names_inputs_and_reaches_its_kernels():
         for T in Ts:
             names = scan_kernel_names(scans, c["variants"], c["x6"], c["budget"], c["persistent"], T=T)
             seen.update(names)
-            for want, got in zip(c["kernels"], names):
+            for i, got in enumerate(names):
+                want = case_kernel(c, i, T)
                 assert want is None or want == got, (c["id"], T, want, got)
+            if case_forward_only(c):
+                assert case_kernel(c, 0, T) is not None and c["kernels"][1] is None and not names[0].startswith(("gru_fwd_pp", "gru_fwd_x6")), (c["id"], names)
     tilings = ("4, 1, 2", "4, 1, 1", "2, 2, 2", "2, 2, 1", "1, 4, 1")
     every = {"gru_fwd_x6pp_kernel<1>", "gru_fwd_x6pp_kernel<2>", "gru_fwd_x6_kernel<1>", "gru_fwd_x6_kernel<2>", "gru_fwd_pp_kernel<1>", "gru_fwd_pp_kernel<2>",
              "gru_bwd_x6_kernel<1>", "gru_bwd_x6_kernel<2>", "gru_bwd_rs_kernel<1>", "gru_bwd_rs_kernel<2>", "gru_fwd_step_kernel", "gru_bwd_step_kernel"}
@@ -77,6 +83,23 @@ def test_restated_dispatch_is_the_librarys_on_every_gpu_case():
             for aligned in ((True, True), (False, True), (True, False)):
                 kw = dict(variants=c["variants"], x6=c["x6"], cu_budget=c["budget"], persistent=c["persistent"], T=T, cus=256, aligned=aligned)
                 assert scan_kernel_candidates(scans, **kw) == lib_scan_candidates(scans, **kw), (c["id"], T, aligned)
+
+
+def test_a_forward_only_launch_is_refused_the_bf16x6_kernels():
+    """gates = NULL and the bf16 x 6 arithmetic asked for: the library refuses the call (no candidate, FN_E_UNSUPPORTED) and the restatement returns [] -
+    at every forward-only case, first and tail chunk; the same shapes WITH gates are taken where the case has 64-row groups at hidden 512.  The engine
+    asks fn_gru_fwd_x6_ok first and therefore runs a save=False pipeline on fp32."""
+    fo = [c for c in SCAN_CASES if case_forward_only(c)]
+    assert {c["inputs"] for c in fo} == {"fo_enc", "fo_dec", "fo_33_96", "fo_200_64", "fo_step"}
+    for c in fo:
+        scans, rows, chunk = scan_inputs(c["inputs"])
+        for T in [None] if chunk is None else sorted({chunk, scans[0]["T"] % chunk or chunk}):
+            kw = dict(variants=c["variants"], x6=True, persistent=c["persistent"], T=T, cus=256)
+            assert scan_kernel_candidates(scans, **kw)[0] == [] == lib_scan_candidates(scans, **kw)[0], (c["id"], T)
+    for name, T in (("fo_enc", None), ("fo_dec", 2)):
+        gated = [dict(s, gates=True) for s in scan_inputs(name)[0]]
+        mine = scan_kernel_candidates(gated, x6=True, T=T)[0]
+        assert mine == lib_scan_candidates(gated, x6=True, T=T)[0] and mine and mine[0].startswith("gru_fwd_x6"), (name, mine)
 
 
 def test_restated_dispatch_is_the_librarys_on_a_seeded_sweep():
